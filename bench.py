@@ -1,7 +1,16 @@
 #!/usr/bin/env python
 """Headline benchmark (BASELINE.json): images/sec of the Painter ViT-L forward+backward on 896x448 stitched pairs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the roofline figures derived from them,
+the loss of the last step, the build stamp).  Everything else below -- the sustained region and its clock / power samples, the
+profiled per-kernel pass, the optimizer step, the secondary configurations, the CPU baseline and the reference-on-GPU leg -- runs only
+with --full; their --no-* / --min-seconds / --profile-steps options apply there.  For N > 1 the gradient-exchange arrangements
+(`gradsync_variants`) are part of `value` and run either way.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed (loss, pred, a seeded sample and the norm of
+every parameter gradient; dump_outputs()) as DIR/<name>.npy.  Parameters, inputs and DropPath's draws come from fixed seeds, so two
+builds given the same arguments can be compared output for output.
 
 N > 1: one rank per GPU over RCCL.  Started without a launcher (WORLD_SIZE unset) the script re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (what the reference's
@@ -550,11 +559,63 @@ def relaunch_under_launcher(args):
     return subprocess.call(cmd, env=env)
 
 
-def main():
+DUMP_PRED_MAX = 12 << 20          # elements of `pred` written whole; a larger one is written as a seeded sample of this many
+DUMP_GRAD_PER_PARAM = 4096        # seeded sample of every parameter gradient
+DUMP_SEED = 20250101
+
+
+def _seeded_sample(t, n, seed):
+    """t flattened when it has at most n elements, else n elements at positions drawn (with a fixed seed) from its flat index range."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= n:
+        return flat
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(out_dir, loss, pred, model):
+    """What a caller of the timed step receives, as DIR/<name>.npy (float32 / float64):
+      loss.npy       [1]            the step's loss
+      pred.npy       pred_patch     (whole; a seeded sample of DUMP_PRED_MAX elements when it is larger)
+      grad_norm.npy  [n_params]     float64 L2 norm of every parameter gradient, named_parameters() order
+      grad_sample.npy               DUMP_GRAD_PER_PARAM elements of every parameter gradient at seeded positions, concatenated in that order
+    Parameters without a gradient are left out of both grad files.  -> {name: bytes written}"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    norms, samples = [], []
+    for i, (_, p) in enumerate(model.named_parameters()):
+        if p.grad is None:
+            continue
+        norms.append(p.grad.detach().double().norm())
+        samples.append(_seeded_sample(p.grad, DUMP_GRAD_PER_PARAM, DUMP_SEED + i).float())
+    arrays = {
+        "loss": loss.detach().float().reshape(1),
+        "pred": _seeded_sample(pred, DUMP_PRED_MAX, DUMP_SEED).float().reshape(pred.shape if pred.numel() <= DUMP_PRED_MAX else (-1,)),
+        "grad_norm": torch.stack(norms) if norms else torch.zeros(0, dtype=torch.float64),
+        "grad_sample": torch.cat(samples) if samples else torch.zeros(0),
+    }
+    written = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        written[name] = os.path.getsize(path)
+    return written
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="number of timed steps")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline number: the sustained region, the per-kernel profiled pass, the optimizer step, "
+                         "the secondary configurations, the CPU baseline and the reference-on-GPU leg (each still subject to its --no-* / "
+                         "--min-seconds / --profile-steps option).  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, pred, parameter gradients) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (BASELINE configs[1]: 8; --model vit_huge: 4 = global 32 on 8 GPUs)")
     ap.add_argument("--model", default="vit_large", choices=sorted(MODELS))
     ap.add_argument("--min-seconds", type=float, default=5.0, help="length of the second, sustained timed region (0 = skip)")
@@ -570,7 +631,14 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = DEBUG: run the N > 1 branch (relaunch, parameter broadcast, GradSync inside the backward, MAX-reduced timing) "
                          "with the ranks sharing however many GPUs are visible (RCCL refuses two ranks per device); the line says so")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(relaunch_under_launcher(args))
@@ -604,7 +672,10 @@ def main():
         parallel.broadcast_parameters(model)                # ... and adopt rank 0's parameters, as under the DDP wrapper
     cfg = model._cfg
     imgs, tgts, mask, valid = synthetic_inputs(args.batch, cfg.H, cfg.W, cfg.L, 1234 + rank, dev)
-    net = [model]                                            # what step() calls: the bare module, or the DDP wrapper around it
+    # DropPath draws from torch's default generators, whose start seed differs from process to process: seeded here (per rank, as
+    # main_train.py:190 seeds its ranks) so that the same arguments give the same steps -- and the same --dump-outputs -- every run
+    torch.manual_seed(1234 + rank)
+    net = [model]                                          # what step() calls: the bare module, or the DDP wrapper around it
 
     def step():
         for p in model.parameters():
@@ -612,12 +683,14 @@ def main():
         # as in plain training, where the optimizer has just rewritten the rel-pos tables: every step re-packs them (one launch for all
         # blocks); the bf16 weight copies stay -- painter_amd.optim.AdamW rewrites those inside its own pass, outside forward + backward
         model._hot.relpos_stale()
-        loss, _, _ = net[0](imgs, tgts, bool_masked_pos=mask, valid=valid)
+        loss, pred, _ = net[0](imgs, tgts, bool_masked_pos=mask, valid=valid)
         loss.backward()
-        return loss
+        return loss, pred
 
+    profile_steps = args.profile_steps if args.full else 0
     timer = KernelTimer(ops)
-    timer.install()                                          # inert (one attribute test per op call) until .active is set
+    if profile_steps > 0:
+        timer.install()                                      # inert (one attribute test per op call) until .active is set
 
     def barrier():
         if distributed:
@@ -625,13 +698,14 @@ def main():
         torch.cuda.synchronize()
 
     def timed_region():
-        """W untimed warm-up steps, then EXACTLY K steps between barriers; -> (seconds = MAX over ranks, last loss)."""
+        """W untimed warm-up steps, then EXACTLY K steps between barriers; -> (seconds = MAX over ranks, last loss).  With --dump-outputs,
+        rank 0 then writes what the last of the K steps computed (outside the timed interval; a later region overwrites it)."""
         for _ in range(args.warmup):
             step()
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            loss = step()
+            loss, pred = step()
         torch.cuda.synchronize()
         barrier()
         dt = time.perf_counter() - t0
@@ -639,6 +713,8 @@ def main():
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             dt = float(t.item())
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, loss, pred, model)
         return dt, float(loss.item())
 
     # N > 1: the gradient exchange is the only thing an 8-GPU node adds, and it has never met real RCCL ranks -- so the same K steps are
@@ -687,7 +763,7 @@ def main():
     clock_power = None
     if distributed:
         dt = variants[gs_best]["seconds"] if gs_best is not None else None
-    if args.min_seconds > 0 and dt is not None:
+    if args.full and args.min_seconds > 0 and dt is not None:
         n_sus = max(args.steps, int(args.min_seconds / (dt / args.steps)) + 1)
         sampler = ClockPowerSampler() if rank == 0 else None
         barrier()
@@ -732,7 +808,7 @@ def main():
     # ---- separate profiled pass (never compare a profiled arm with an un-profiled one: `value` above is un-instrumented)
     kernels = {}
     launch_check = None
-    if args.profile_steps > 0 and not distributed:          # single rank only: the extra steps would need every rank's all-reduce
+    if profile_steps > 0 and not distributed:               # single rank only: the extra steps would need every rank's all-reduce
         from painter_amd._lib import lib as _lib
         side = model._hot.use_side_stream
         model._hot.use_side_stream = False                  # one stream: an event pair brackets exactly its own kernels
@@ -744,7 +820,7 @@ def main():
         _lib.pa_debug_set(6, 0)
         step()
         timer.active = True
-        for _ in range(args.profile_steps):
+        for _ in range(profile_steps):
             step()
         torch.cuda.synchronize()
         timer.active = False
@@ -754,12 +830,12 @@ def main():
         peak = PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_F32_TFLOPS
         kernels = timer.results(peak)
         for v in kernels.values():
-            v["ms_per_step"] = round(v["kernel_ms_total"] / args.profile_steps, 3)
+            v["ms_per_step"] = round(v["kernel_ms_total"] / profile_steps, 3)
         # every nn.Linear is one bracket per pass: qkv, proj, fc1(+GELU), fc2 per block + decoder_embed = 4 * depth + 1 (round 2's
         # timer counted fc1 twice: ops.linear_gelu calls ops.linear_fwd)
-        want = (4 * len(model.blocks) + 1) * args.profile_steps
+        want = (4 * len(model.blocks) + 1) * profile_steps
         # (+ the patch-embed weight gradient where the bf16 im2col fast path is on: it is an ordinary nn.Linear weight gradient there)
-        extra_w = args.profile_steps if ops.patch_cols_ok(model.compute_dtype, args.batch, cfg.L, cfg.P, cfg.D) else 0
+        extra_w = profile_steps if ops.patch_cols_ok(model.compute_dtype, args.batch, cfg.L, cfg.P, cfg.D) else 0
         launch_check = {fam: {"launches": kernels.get(fam, {}).get("launches", 0), "expected": w_}
                         for fam, w_ in (("gemm256_fwd", want), ("gemm256_dgrad", want), ("gemm256_wgrad", want + extra_w))}
         bad = {f: v for f, v in launch_check.items() if v["launches"] != v["expected"]}
@@ -825,7 +901,7 @@ def main():
                          "traffic": traffic, "traffic_source": "profiles/roofline_traffic.json (rocprofv3 PMC passes of this bench on this library, tools/pmc_traffic.py; not re-measured inside this run)" if traffic is not None else None,
                          "traffic_meta": traffic_meta, "traffic_by_family": traffic_by_family, "launch_count_check": launch_check,
                          "dominant_kernel": dominant, "kernels": kernels,
-                         "profiled_pass": "separate pass of %d steps after the timed region, HIP events per launch, one stream, parameter-gradient kernels sized for the whole chip (as in profiles/*one_stream_kernel_stats.csv)" % args.profile_steps},
+                         "profiled_pass": ("separate pass of %d steps after the timed region, HIP events per launch, one stream, parameter-gradient kernels sized for the whole chip (as in profiles/*one_stream_kernel_stats.csv)" % profile_steps) if args.full else None},
             "loss": round(lossv, 6),
             "sustained": sustained,
             "extra": clock_power,
@@ -840,9 +916,9 @@ def main():
                 out["extra"]["gradsync_ddp_error"] = ddp_error
             if gs_errors:
                 out["extra"]["gradsync_errors"] = gs_errors
-        if n_ranks == 1 and args.dtype == "bf16" and not args.no_optimizer and args.model == "vit_large":
+        if args.full and n_ranks == 1 and args.dtype == "bf16" and not args.no_optimizer and args.model == "vit_large":
             out["optimizer_step"] = optimizer_step_ms(model, step)
-        if n_ranks == 1 and not distributed and args.dtype == "bf16" and args.model == "vit_large" and not args.no_secondary:
+        if args.full and n_ranks == 1 and not distributed and args.dtype == "bf16" and args.model == "vit_large" and not args.no_secondary:
             # the other single-GPU BASELINE configurations, after (never inside) the headline measurement; each a few seconds
             out["secondary"] = {}
             for key, fn in (("seggpt_n32", secondary_seggpt_n32), ("vit_huge", secondary_vit_huge)):
@@ -852,9 +928,9 @@ def main():
                     out["secondary"][key]["leg_seconds"] = round(time.perf_counter() - t0, 1)
                 except Exception as e:                  # a secondary leg never takes the line down
                     out["secondary"][key] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if n_ranks == 1 and not args.no_cpu_baseline:
+        if args.full and n_ranks == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
-        if n_ranks == 1 and not args.no_reference_gpu and args.model == "vit_large" and not args.eval:
+        if args.full and n_ranks == 1 and not args.no_reference_gpu and args.model == "vit_large" and not args.eval:
             try:
                 rg = reference_gpu_baseline(model, (imgs, tgts, mask, valid), dev)
             except Exception as e:                      # a baseline leg never takes the line down

@@ -119,3 +119,50 @@ def test_closing_profiles_of_the_round_carry_one_library_stamp():
     if built is not None and built not in shas:
         import pytest
         pytest.skip("closing artefacts are stamped %s, the library built here is %s (another path / toolchain, or kernels changed after the closing visit)" % (shas, built))
+
+
+def test_plain_run_is_lean_and_full_is_opt_in():
+    """`bench.py --gpus 1 --steps N --warmup W` times the headline steps only; everything else waits for --full.  --steps is the number of
+    timed steps and must be positive."""
+    import pytest
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--steps", "3", "--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_float_arrays_of_the_step_within_the_budget(tmp_path):
+    """--dump-outputs: loss, pred and the parameter gradients as float32 / float64 .npy files; a larger array becomes a seeded sample (the
+    same positions every run), and the whole dump of the ViT-L B = 8 step stays under 64 MB."""
+    import numpy as np
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(8, 16), torch.nn.Linear(16, 4))
+    m[1].bias.requires_grad_(False)                   # a parameter without a gradient is left out
+    x = torch.randn(5, 8)
+    pred = m(x)
+    loss = pred.square().mean()
+    loss.backward()
+    for d in ("a", "b"):
+        written = bench.dump_outputs(str(tmp_path / d), loss, pred, m)
+        assert set(written) == {"loss", "pred", "grad_norm", "grad_sample"}
+    for name in written:
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == np.float32(loss.item())
+    assert np.array_equal(np.load(tmp_path / "a" / "pred.npy"), pred.detach().numpy())
+    grads = [p.grad for p in m.parameters() if p.grad is not None]
+    assert np.allclose(np.load(tmp_path / "a" / "grad_norm.npy"), [float(g.double().norm()) for g in grads])
+    assert np.array_equal(np.load(tmp_path / "a" / "grad_sample.npy"), torch.cat([g.reshape(-1) for g in grads]).numpy())
+    # seeded sample of a large tensor: same positions every call, drawn from the whole tensor
+    big = torch.arange(100000, dtype=torch.float32)
+    s1, s2 = bench._seeded_sample(big, 1000, 5), bench._seeded_sample(big, 1000, 5)
+    assert s1.numel() == 1000 and torch.equal(s1, s2) and float(s1.max()) > 50000
+    # the ViT-L B = 8 step: pred [8, 1568, 768] whole + DUMP_GRAD_PER_PARAM elements of each gradient, under 64 MB (the deepest
+    # configuration, ViT-H/14 with 32 blocks, has the most parameter tensors)
+    from oracle import painter_oracle as O
+    n_params = max(len(O.param_shapes(O.vit_large_config())), len(O.param_shapes(O.vit_huge_config())))
+    assert n_params > 32 * 10
+    assert 8 * 1568 * 768 <= bench.DUMP_PRED_MAX
+    assert (bench.DUMP_PRED_MAX + n_params * (bench.DUMP_GRAD_PER_PARAM + 2) + 1) * 4 < 64 << 20

@@ -87,9 +87,15 @@ def test_staged_reference_subset_is_byte_identical_to_the_reference_and_is_what_
         b = open(os.path.join(root, rel), "rb").read()
         assert hashlib.sha256(a).hexdigest() == hashlib.sha256(b).hexdigest(), rel
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    # nothing of the reference is tracked by git: the staging area is ignored as a whole
-    out = subprocess.run(["git", "-C", repo, "check-ignore", "oracle/_ref/reference_subset.tar.gz"], capture_output=True, text=True)
-    assert out.returncode == 0
+    # nothing of the reference is tracked by git: the staging area is ignored as a whole.  Asked of the project's .gitignore in a
+    # throwaway repository, so that the answer does not depend on whether this tree is itself a git checkout
+    probe = tmp_path / "ignore_probe"
+    probe.mkdir()
+    (probe / ".gitignore").write_bytes(open(os.path.join(repo, ".gitignore"), "rb").read())
+    git = ["git", "-c", "core.excludesFile=", "-C", str(probe)]
+    assert subprocess.run(git + ["init", "-q"], capture_output=True, text=True).returncode == 0
+    out = subprocess.run(git + ["check-ignore", "-q", "oracle/_ref/reference_subset.tar.gz"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
     code = ("import os, sys; sys.path.insert(0, %r)\n"
             "real = os.path.isfile\n"
             "os.path.isfile = lambda p: False if str(p).startswith('/root/reference') else real(p)\n"

@@ -5,6 +5,9 @@
 set -u
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+# the benchmark sections (bench, benchfast, huge, benchselftest: full runs, bench.py --full) write under $VISIT_OUT, default visit_out/
+OUT=${VISIT_OUT:-visit_out}
+mkdir -p "$OUT"
 ulimit -c 0                     # a faulting GPU makes every python process abort: without this each abort writes a multi-GB core (minutes)
 # a faulty box shows up in the first H2D copy: check once, and do nothing else on such a box (round 3 lost 50 GPU-minutes to one)
 if ! timeout 120 python -c "import torch; x = torch.randn(1 << 20).cuda(); assert abs(float((x * 2).sum()) - 2 * float(x.sum())) < 1e-2; torch.cuda.synchronize(); print('gpu sanity ok', torch.cuda.get_device_name(0))"; then
@@ -19,9 +22,9 @@ for s in "$@"; do
   case $s in
     tests)     timeout 480 python -m pytest tests -m gpu -q -s > gpurun_out/tests.log 2>&1; echo "tests rc=$?"; tail -5 gpurun_out/tests.log ;;
     newtests)  timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_model_gpu.py -m gpu -q -s -k "head_dim_80 or h14 or loss_variants or patch_embed or vit_large or c_abi" > gpurun_out/newtests.log 2>&1; echo "newtests rc=$?"; tail -15 gpurun_out/newtests.log ;;
-    bench)     timeout 330 python bench.py --steps 20 --warmup 5 > gpurun_out/bench.json 2> gpurun_out/bench.err; echo "bench rc=$?"; cut -c1-600 gpurun_out/bench.json ;;
-    benchfast) timeout 240 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-optimizer > gpurun_out/benchfast.json 2> gpurun_out/benchfast.err; echo "benchfast rc=$?"; cut -c1-400 gpurun_out/benchfast.json ;;
-    huge)      timeout 200 python bench.py --model vit_huge --steps 5 --warmup 2 --no-cpu-baseline --min-seconds 2 > gpurun_out/bench_huge.json 2> gpurun_out/bench_huge.err; echo "huge rc=$?"; cut -c1-600 gpurun_out/bench_huge.json; tail -3 gpurun_out/bench_huge.err ;;
+    bench)     timeout 330 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-600 $OUT/bench.json ;;
+    benchfast) timeout 240 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-optimizer > $OUT/benchfast.json 2> $OUT/benchfast.err; echo "benchfast rc=$?"; cut -c1-400 $OUT/benchfast.json ;;
+    huge)      timeout 200 python bench.py --full --model vit_huge --steps 5 --warmup 2 --no-cpu-baseline --min-seconds 2 > $OUT/bench_huge.json 2> $OUT/bench_huge.err; echo "huge rc=$?"; cut -c1-600 $OUT/bench_huge.json; tail -3 $OUT/bench_huge.err ;;
     profile)   (cd /tmp && timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/gpurun_out/prof_two_stream -o two -- python $OLDPWD/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-optimizer --profile-steps 0 --min-seconds 0 > $OLDPWD/gpurun_out/prof_two.log 2>&1
                 PAINTER_AMD_SIDE_STREAM=0 timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/gpurun_out/prof_one_stream -o one -- python $OLDPWD/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-optimizer --profile-steps 0 --min-seconds 0 > $OLDPWD/gpurun_out/prof_one.log 2>&1); echo "profile done"; ls gpurun_out/prof_one_stream gpurun_out/prof_two_stream 2>/dev/null | head ;;
     pmc)       (cd /tmp && for c in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do
@@ -92,7 +95,7 @@ for s in "$@"; do
                timeout 500 python tools/step_knob_ab.py 3 6 "patch 4 x 8 (shipped):11=0" "patch 6 x 5:11=605" "patch 6 x 6:11=606" > gpurun_out/patchab.log 2>&1; tail -4 gpurun_out/patchab.log ;;
     stepbounds) timeout 600 python tools/step_bounds.py > gpurun_out/stepbounds.log 2>&1; echo "stepbounds rc=$?"; grep -v amdgpu.ids gpurun_out/stepbounds.log ;;
     layoutprobe) timeout 300 python tools/gemm_layout_probe.py > gpurun_out/layoutprobe.log 2>&1; echo "layoutprobe rc=$?"; grep -v amdgpu.ids gpurun_out/layoutprobe.log ;;
-    benchselftest) PAINTER_AMD_DDP_SELFTEST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29551 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-optimizer --no-reference-gpu --no-secondary --min-seconds 1 > gpurun_out/benchselftest.json 2> gpurun_out/benchselftest.err; echo "benchselftest rc=$?"; python -c "import json; ls_ = open('gpurun_out/benchselftest.json').read().strip().splitlines(); print('stdout lines', len(ls_), 'last is json', ls_[-1].startswith('{')); d = json.loads(ls_[-1]); print(d['value'], d['config']['rccl_ranks'], d['config']['grad_allreduce'][:40]); print(json.dumps(d['extra'], indent=0)[:1800])"; tail -3 gpurun_out/benchselftest.err ;;
+    benchselftest) PAINTER_AMD_DDP_SELFTEST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29551 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 400 python bench.py --full --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-optimizer --no-reference-gpu --no-secondary --min-seconds 1 > $OUT/benchselftest.json 2> $OUT/benchselftest.err; echo "benchselftest rc=$?"; python -c "import json; ls_ = open('$OUT/benchselftest.json').read().strip().splitlines(); print('stdout lines', len(ls_), 'last is json', ls_[-1].startswith('{')); d = json.loads(ls_[-1]); print(d['value'], d['config']['rccl_ranks'], d['config']['grad_allreduce'][:40]); print(json.dumps(d['extra'], indent=0)[:1800])"; tail -3 $OUT/benchselftest.err ;;
     multitest) timeout 900 python -m pytest tests/test_parallel_gpu.py tests/test_model_gpu.py -m gpu -q -x -k "bench_multi or selftest or ddp" > gpurun_out/multitest.log 2>&1; echo "multitest rc=$?"; tail -3 gpurun_out/multitest.log ;;
     mixedprobe) timeout 300 python tools/gemm_mixed_probe.py > gpurun_out/mixedprobe.log 2>&1; echo "mixedprobe rc=$?"; cat gpurun_out/mixedprobe.log ;;
     lnfwdab)   timeout 600 python tools/step_knob_ab.py 4 6 "LN forward, persistent waves (round 6):13=1" "one row per wave (round 5):13=0" > gpurun_out/lnfwdab.log 2>&1; echo "lnfwdab rc=$?"; tail -3 gpurun_out/lnfwdab.log ;;
