@@ -196,6 +196,14 @@ int64_t pa_patch_embed_wgrad_workspace_bytes(int D, int P);
 int pa_patch_embed_wgrad(int dtype, const void* dpe /*T [2BL, D]*/, const float* imgs, const float* tgts,
                          float* dw /*f32 [D, 3*P*P]*/, void* workspace, int batch, int Hp, int Wp, int P, int D,
                          hipStream_t stream);
+/* input gradient of the patch embedding: the conv has stride = kernel, so d(imgs ; tgts) is one GEMM dcols = dPE . Wp followed by the
+ * inverse of the im2col permutation, which the GEMM's epilogue applies while it stores (the zero-padding columns of Wp are dropped).
+ * dpe: T [2BL, D] from pa_tokens_bwd (its y-stream rows already carry the (1 - w) factor of the mask blend); w: T [D, ldw] as for
+ * pa_patch_embed_fwd.  dimgs / dtgts: f32 NCHW [B,3,Hp*P,Wp*P], either may be NULL (that stream's rows are then not contracted).
+ * addend (optional, f32 NCHW like dtgts): dtgts = dcols(y rows) + alpha * addend.  Every pixel is written exactly once per stream (no
+ * atomics, bitwise reproducible).  bf16 with P % 8 == 0 and D % 128 == 0: the 256x256 LDS-DMA kernel; every other case the generic engine. */
+int pa_patch_embed_dgrad(int dtype, const void* dpe, const void* w, int64_t ldw, float* dimgs, float* dtgts, const float* addend,
+                         float alpha, int batch, int Hp, int Wp, int P, int D, hipStream_t stream);
 /* get_abs_pos (util/vitdet_utils.py:128-157) as the constant bicubic operator M [L, S] (host-built), in row-sparse form
  * (painter_amd/hostmath.py sparse_rows: int32 column indices + f32 values, K entries per row, zero-padded): pos = M . pe with
  * (idx, val, K) of M; dpe = M^T . (gx + gy) with those of M^T.  pe/dpe point at pos_embed[0, skip_cls:, :] ([S, D]). */
@@ -251,6 +259,13 @@ int pa_loss_bwd(const float* pred, const float* tgts, const float* valid, const 
                 int P, int kind, float beta, hipStream_t stream);
 /* patchify (models_painter.py:355-368): f32 NCHW -> [B, L, P*P*3] */
 int pa_patchify(const float* img, float* out, int batch, int Hp, int Wp, int P, hipStream_t stream);
+/* gradient of pred when the returned prediction enters the objective, in one pass:
+ *   dpred = [dloss != NULL] the pa_loss_bwd term (same arithmetic, same bits) + [dpatch != NULL] unpatchify(dpatch)
+ * dpatch: f32 [B, L, P*P*3] (the gradient of pa_patchify's output); at least one of dloss / dpatch.  dpred_loss (optional, needs dloss)
+ * receives the loss term alone: every loss kind depends on pred - tgts only, so the loss's direct gradient w.r.t. tgts is -dpred_loss. */
+int pa_pred_bwd(const float* pred, const float* tgts, const float* valid, const unsigned char* mask, int mask_batch_stride,
+                const float* dloss, const float* loss_out, const float* dpatch, float* dpred, float* dpred_loss, int batch, int Hi,
+                int Wi, int P, int kind, float beta, hipStream_t stream);
 
 /* ---- Optimizer step: GradScaler.unscale_ + clip_grad_norm_ + AdamW over the layer-decay groups in two passes.
  * Replaces Painter/util/misc.py:256-268 (NativeScalerWithGradNormCount.__call__) acting on the torch.optim.AdamW of

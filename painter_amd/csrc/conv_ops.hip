@@ -268,6 +268,99 @@ extern "C" int pa_patch_embed_wgrad(int dtype, const void* dpe, const float* img
     return patch_wgrad_t<float>((const float*)dpe, imgs, tgts, dw, (float*)workspace, batch, Hp, Wp, P, D, st);
 }
 
+// ---- input gradient: dcols[t][k] = sum_d dPE[t][d] * Wp[d][k], stored straight to the pixel OpPatch reads for (t, k) (the inverse of
+// the im2col permutation: stride = kernel, so every pixel belongs to exactly one (token, k) -- one plain store each, no atomics).
+// Launch rows [r0, r0 + M) of the 2BL token rows (r0 = BL, M = BL: the y stream alone); columns >= 3*P*P (Wp's padding) are dropped.
+struct PatchPix {
+    float* img0; float* img1;                  // d imgs (x-stream rows), d tgts (y-stream rows)
+    const float* addend; float alpha;          // y stream: + alpha * addend[pixel] (NULL: nothing)
+    int r0, Bn, Hp, Wp, P;
+    // element offset of (token row g, channel 0, patch origin) in an NCHW image, and the stream
+    DEVI size_t base(int g, int& s) const {
+        const int L = Hp * Wp, BL = Bn * L;
+        s = g / BL;
+        const int r = g - s * BL, b = r / L, l = r - b * L, h = l / Wp, w = l - h * Wp;
+        return ((size_t)b * 3 * Hp * P + (size_t)h * P) * (size_t)(Wp * P) + (size_t)w * P;
+    }
+    DEVI size_t koff(int k) const {
+        const int PP = P * P, ch = k / PP, ph = (k - ch * PP) / P, pw = k % P;
+        return ((size_t)ch * Hp * P + ph) * (size_t)(Wp * P) + pw;
+    }
+};
+// generic engine (fp32 build, P = 14, D % 128 != 0): element-wise stores
+struct EpiPatchDgrad : PatchPix {
+    int M, N;                                  // N = 3*P*P
+    DEVI void operator()(const f32x16 (&acc)[2][2], int ib, int jb, int lane, int) const {
+        foreach_acc(acc, ib, jb, lane, [&](int i, int j, float v) {
+            if (i < M && j < N) {
+                int s;
+                const size_t o = base(r0 + i, s) + koff(j);
+                if (s == 1 && addend) v += alpha * addend[o];
+                (s ? img1 : img0)[o] = v;
+            }
+        });
+    }
+};
+// gemm256 (bf16, P % 8 == 0): the kernel's LDS-staged epilogue hands each lane columns j..j+3 and j+32..j+35 of one token row, and 8
+// lanes per row cover 64 columns; with HI_OFF = 32 every store instruction writes, for 8 consecutive tokens (= horizontally adjacent
+// patches), 16-byte pieces that join into whole image-row segments (4 lanes x 16 B per patch row, the next token's patch row right after).
+// The addend (d tgts: the loss's direct term) is loaded in row(), ahead of the stores.
+struct Epi4PatchDgrad : PatchPix {
+    int M, N;
+    static constexpr int HI_OFF = 32;
+    struct Col {};
+    struct Row { uint32_t olo, ohi; int s; float4 alo, ahi; };
+    DEVI Col col(int) const { return Col{}; }
+    DEVI Row row(int i, int j) const {
+        Row r{0u, 0u, 0, make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
+        if (i < M && j < N) {
+            const size_t b0 = base(r0 + i, r.s);
+            r.olo = (uint32_t)(b0 + koff(j));
+            if (j + 32 < N) r.ohi = (uint32_t)(b0 + koff(j + 32));
+            if (r.s == 1 && addend) {
+                r.alo = *reinterpret_cast<const float4*>(addend + r.olo);
+                if (j + 32 < N) r.ahi = *reinterpret_cast<const float4*>(addend + r.ohi);
+            }
+        }
+        return r;
+    }
+    DEVI static float4 axpy(float4 v, float a, float4 x) { return make_float4(v.x + a * x.x, v.y + a * x.y, v.z + a * x.z, v.w + a * x.w); }
+    DEVI void store(int i, int j, float4 lo, float4 hi, const Col&, const Row& r, int) const {
+        if (i >= M || j >= N) return;
+        float* o = r.s ? img1 : img0;
+        if (r.s == 1 && addend) { lo = axpy(lo, alpha, r.alo); hi = axpy(hi, alpha, r.ahi); }
+        *reinterpret_cast<float4*>(o + r.olo) = lo;
+        if (j + 32 < N) *reinterpret_cast<float4*>(o + r.ohi) = hi;
+    }
+};
+extern "C" int pa_patch_embed_dgrad(int dtype, const void* dpe, const void* w, int64_t ldw, float* dimgs, float* dtgts, const float* addend,
+                                    float alpha, int batch, int Hp, int Wp, int P, int D, hipStream_t st) {
+    const int K = 3 * P * P, Kp = (K + 7) / 8 * 8, BL = batch * Hp * Wp;
+    if (P < 1 || ldw < Kp || ldw % 8 || D % 8 || (dimgs == nullptr && dtgts == nullptr)) return (int)hipErrorInvalidValue;
+    if ((size_t)batch * 3 * Hp * P * Wp * P >= (1ull << 32)) return (int)hipErrorInvalidValue;        // 32-bit pixel offsets (Epi4PatchDgrad::Row)
+    const int r0 = dimgs ? 0 : BL, M = (dimgs && dtgts) ? 2 * BL : BL;
+    PatchPix pp{dimgs, dtgts, addend, alpha, r0, batch, Hp, Wp, P};
+    const size_t a0 = (size_t)r0 * D;
+    if (dtype == PA_BF16) {
+        const bf16* A = (const bf16*)dpe + a0;
+        if (P % 8 == 0 && g256::ok(M, K, D, false, true, D, ldw)) {
+            Epi4PatchDgrad ep;
+            static_cast<PatchPix&>(ep) = pp;
+            ep.M = M; ep.N = K;
+            return g256::launch<false, true>(A, (size_t)D, (const bf16*)w, (size_t)ldw, ep, M, K, D, 1, st);
+        }
+        EpiPatchDgrad ep;
+        static_cast<PatchPix&>(ep) = pp;
+        ep.M = M; ep.N = K;
+        return launch_gemm<bf16, 2, 2>(OpN<bf16>{A, (size_t)D, M, 0}, OpT<bf16>{(const bf16*)w, (size_t)ldw, Kp, 0}, ep, M, Kp, D, 1, 1, st);
+    }
+    EpiPatchDgrad ep;
+    static_cast<PatchPix&>(ep) = pp;
+    ep.M = M; ep.N = K;
+    return launch_gemm<float, 2, 2>(OpN<float>{(const float*)dpe + a0, (size_t)D, M, 0}, OpT<float>{(const float*)w, (size_t)ldw, Kp, 0}, ep,
+                                    M, Kp, D, 1, 1, st);
+}
+
 // ------------------------------------------------------------------------------- 3x3 conv operands (NHWC, C = 64)
 #define CV_C 64
 // B(row = pixel, k = tap*64 + cin) = X[b, y+ky-1, x+kx-1, cin]  (zero outside the image)

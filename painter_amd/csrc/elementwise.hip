@@ -310,6 +310,39 @@ extern "C" int pa_loss_bwd(const float* pred, const float* tgts, const float* va
     LAUNCH_CHECK();
 }
 
+// dpred = loss term (loss_bwd_kernel's expression) + unpatchify(dpatch); the loss term alone also to dpred_loss (-> d tgts)
+__global__ void pred_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ tgts, const float* __restrict__ valid,
+                                const unsigned char* __restrict__ mask, int mbs, const float* __restrict__ dloss, const float* __restrict__ lossden,
+                                const float* __restrict__ dpatch, float* __restrict__ dpred, float* __restrict__ dpred_loss, int HW, int Wi,
+                                int P, int Wp, int kind, float beta) {
+    const int b = blockIdx.y, n = 3 * HW;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const size_t idx = (size_t)b * n + e;
+    float g = 0.f;
+    if (dloss) {
+        const float mv = (float)pix_mask(mask, mbs, b, e % HW, Wi, P, Wp) * valid[idx];
+        g = dloss[0] / lossden[1] * mv * loss_grad_elem(pred[idx] - tgts[idx], kind, beta);
+        if (dpred_loss) dpred_loss[idx] = g;
+    }
+    if (dpatch) {      // patchify_kernel's index map, inverted: pixel (c, y, x) <- token (y / P, x / P), k = ((y % P) * P + x % P) * 3 + c
+        const int c = e / HW, rem = e - c * HW, y = rem / Wi, x = rem - y * Wi;
+        const int L = (HW / Wi / P) * Wp, l = (y / P) * Wp + x / P, k = ((y % P) * P + x % P) * 3 + c;
+        g += dpatch[((size_t)b * L + l) * (size_t)(3 * P * P) + k];
+    }
+    dpred[idx] = g;
+}
+extern "C" int pa_pred_bwd(const float* pred, const float* tgts, const float* valid, const unsigned char* mask, int mask_batch_stride,
+                           const float* dloss, const float* loss_out, const float* dpatch, float* dpred, float* dpred_loss, int batch, int Hi,
+                           int Wi, int P, int kind, float beta, hipStream_t st) {
+    if ((dloss == nullptr && dpatch == nullptr) || (dpred_loss != nullptr && dloss == nullptr) || P < 1 || Hi % P || Wi % P)
+        return (int)hipErrorInvalidValue;
+    const int HW = Hi * Wi;
+    PA_LAUNCH(pred_bwd_kernel, dim3((3 * HW + 255) / 256, batch), dim3(256), 0, st, pred, tgts, valid, mask, mask_batch_stride,
+              dloss, loss_out, dpatch, dpred, dpred_loss, HW, Wi, P, Wi / P, kind, beta);
+    LAUNCH_CHECK();
+}
+
 // ------------------------------------------------------------------------------- patchify (models_painter.py:355-368), pure index math
 __global__ void patchify_kernel(const float* __restrict__ img, float* __restrict__ out, int Hp, int Wp, int P, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

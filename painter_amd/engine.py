@@ -260,13 +260,17 @@ class HotPath:
                 self._wcache[key] = (p._version, ent[1])
 
     # ------------------------------------------------------------------ forward
-    def forward(self, P, imgs, tgts, mask_u8, valid, seg_type=None, merge_between_batch=-1, drop_scales=None, need_grad=True):
+    def forward(self, P, imgs, tgts, mask_u8, valid, seg_type=None, merge_between_batch=-1, drop_scales=None, need_grad=True, want=None):
+        """need_grad: save what a backward needs (any input, parameter or the prediction may need a gradient).  want: the parameter names
+        whose gradients the backward will be asked for (None = all): tensors that only serve frozen parameters' gradients are not kept --
+        the im2col operand (patch weight), the tap concat (decoder_embed.weight), decoder_embed's output (decoder_pred.0.weight)."""
         c, T = self.cfg, self.T
         dev = imgs.device
         B = imgs.shape[0]
         L, D = c.L, c.D
         S = _Saved()
         S.B, S.need_grad = B, need_grad
+        keep = lambda n: need_grad and (want is None or n in want)
         S.imgs, S.tgts, S.mask, S.valid = imgs, tgts, mask_u8, valid
         S.drop = drop_scales
         S.seg_type = seg_type if c.seggpt else None
@@ -279,7 +283,7 @@ class HotPath:
         if ops.patch_cols_ok(T, B, L, c.P, D):           # bf16, P % 8 == 0: materialised im2col operand + the 256 x 256 GEMM (kept for the weight gradient)
             cols = ops.patch_im2col(imgs, tgts, B, c.Hp, c.Wp, c.P)
             x = ops.patch_embed_fwd_cols(cols, self.w_patch(P), *tok_args, B, L, D)
-            if need_grad:
+            if keep("patch_embed.proj.weight"):
                 S.cols = cols
         else:
             x = ops.patch_embed_fwd(T, imgs, tgts, self.w_patch(P), *tok_args, B, c.Hp, c.Wp, c.P, D)
@@ -340,13 +344,22 @@ class HotPath:
                                 eps_den=0.0 if c.seggpt else 1e-2, kind=c.loss_func)
         pred_patch = ops.patchify(pred, c.Hp, c.Wp, c.P)
         if need_grad:
-            S.concat, S.E, S.y3, S.pred, S.loss_out, S.wf = concat, E, y3, pred, loss_out, wf
+            S.y3, S.pred, S.loss_out, S.wf = y3, pred, loss_out, wf
+            S.concat = concat if keep("decoder_embed.weight") else None
+            S.E = E if keep("decoder_pred.0.weight") else None
         return loss_out, pred, pred_patch, S
 
     # ------------------------------------------------------------------ backward
-    def backward(self, P, S, dloss, sync=None):
-        """-> {param name: fp32 grad}.  dloss: 0-d / [1] fp32 device tensor (may carry a GradScaler factor).
+    def backward(self, P, S, dloss, sync=None, want=None, want_imgs=False, want_tgts=False, dpatch=None):
+        """-> {param name: fp32 grad}, or (that dict, d imgs, d tgts) when want_imgs / want_tgts is set (None where not asked for).
+        dloss: 0-d / [1] fp32 device tensor (may carry a GradScaler factor), or None when the loss is not in the objective.
         sync: optional painter_amd.parallel.GradSync; buckets are handed over as soon as they are enqueued.
+        want: the parameter names whose gradients are needed (None = all).  The others get no entry and none of their separable work runs:
+        weight-gradient GEMMs + slab sums, the conv3x3 / patch-embed weight gradients, the rel-pos table reductions, the deferred LayerNorm
+        parameter reductions and separate column sums.  Bias sums fused into data-gradient kernels (the LayerNorm backward's dxT_colsum,
+        fc1's colsum_out) stay, so that the data-gradient chain runs the same kernels and gives the same bits.  With a GradSync every
+        gradient is computed and exchanged (want is ignored).
+        dpatch: f32 [B, L, P*P*3] gradient of the returned pred_patch, or None (then dpred is today's pa_loss_bwd).
 
         Two HIP streams: the data-gradient chain (dgrad GEMMs, attention backward, LayerNorm backward) runs on the caller's
         stream; every weight/bias gradient of an nn.Linear (wgrad GEMM + slab reduction + column sum) is enqueued on a side
@@ -355,8 +368,11 @@ class HotPath:
         B, L, D = S.B, c.L, c.D
         dev = S.imgs.device
         G = {}
+        if sync is not None:
+            want = None
+        need = (lambda n: True) if want is None else (lambda n: n in want)
         main = torch.cuda.current_stream(dev)
-        side = self.side_stream(dev) if self.use_side_stream else None
+        side = self.side_stream(dev) if self.use_side_stream and (want is None or len(want) > 0) else None
         keep = []
         self.trace = []
 
@@ -368,7 +384,17 @@ class HotPath:
 
         def param_grads(wname, bname, dy, x, bout=None):
             """G[wname] = dy^T.x, G[bname] = colsum(dy) (into `bout`, a slice of the block's flat small-gradient buffer, when given)
-            -- on the side stream when enabled."""
+            -- on the side stream when enabled.  Frozen parameters (outside `want`) cost nothing here."""
+            if not need(wname) and (bname in G or not need(bname)):
+                return
+            if not need(wname) or not need(bname):          # partly frozen layer: only what is asked for, in the caller's stream order
+                def one():
+                    if need(wname):
+                        G[wname] = ops.linear_wgrad(dy, x)
+                    if bname not in G and need(bname):
+                        G[bname] = ops.colsum(dy, out=bout)
+                on_side(one, *[t for t in (dy, x if need(wname) else None) if t is not None])
+                return
             tag = "dec" if wname.startswith("decoder") else wname.split(".")[-2]
             if side is None or (filt is not None and tag not in filt):
                 G[wname] = ops.linear_wgrad(dy, x)
@@ -419,7 +445,14 @@ class HotPath:
             with torch.cuda.stream(side):
                 sync.ready(G, names, flat=flat)
 
-        dpred = ops.loss_bwd(S.pred, S.tgts, S.valid, S.mask, dloss, S.loss_out, c.P, c.loss_func)
+        dpred_loss = None          # the loss's own term of dpred: its direct gradient w.r.t. tgts is -dpred_loss
+        if dpatch is None:
+            dpred = ops.loss_bwd(S.pred, S.tgts, S.valid, S.mask, dloss, S.loss_out, c.P, c.loss_func)
+            if want_tgts:
+                dpred_loss = dpred
+        else:
+            dpred, dpred_loss = ops.pred_bwd(S.pred, S.tgts, S.valid, S.mask, dloss, S.loss_out, dpatch, c.P, c.loss_func,
+                                             want_loss_term=want_tgts and dloss is not None)
         w1 = P["decoder_pred.3.weight"].reshape(3, c.dec)
         dy3, tg = ops.decoder_tail_bwd_pointwise(dpred, S.y3, P["decoder_pred.1.weight"], P["decoder_pred.1.bias"], w1, 1e-6)
         G["decoder_pred.1.weight"] = tg[0:64]
@@ -427,8 +460,14 @@ class HotPath:
         G["decoder_pred.3.weight"] = tg[128:320].reshape(3, c.dec, 1, 1)
         G["decoder_pred.3.bias"] = tg[320:323]
         npix = B * c.H * c.W
-        G["decoder_pred.0.weight"], G["decoder_pred.0.bias"] = on_side(
-            lambda: (ops.conv3x3_wgrad(dy3, S.E), ops.colsum(dy3.view(npix, c.dec))), dy3, S.E)
+        if want is None:
+            G["decoder_pred.0.weight"], G["decoder_pred.0.bias"] = on_side(
+                lambda: (ops.conv3x3_wgrad(dy3, S.E), ops.colsum(dy3.view(npix, c.dec))), dy3, S.E)
+        elif need("decoder_pred.0.weight") or need("decoder_pred.0.bias"):
+            G["decoder_pred.0.weight"], G["decoder_pred.0.bias"] = on_side(
+                lambda: (ops.conv3x3_wgrad(dy3, S.E) if need("decoder_pred.0.weight") else None,
+                         ops.colsum(dy3.view(npix, c.dec)) if need("decoder_pred.0.bias") else None),
+                *[t for t in (dy3, S.E) if t is not None])
         dE = ops.conv3x3_dgrad_unshuffle(dy3, S.wf, B, c.Hp, c.Wp, c.P)
         del dy3
         param_grads("decoder_embed.weight", "decoder_embed.bias", dE, S.concat)
@@ -477,7 +516,8 @@ class HotPath:
                 dx, gb = ops.layernorm_bwd(dconcat[:, k * D:(k + 1) * D], xt, mt, rt, P["norm.weight"], dres=dx, dx=dx, dxT=dyT,
                                            rowscale=ds_m, rows_per_sample=L, dxT_colsum=fl["fc2"])
                 G[pre + "mlp.fc2.bias"] = fl["fc2"]
-                dnorm = gb if dnorm is None else _add_(dnorm, gb)
+                if need("norm.weight") or need("norm.bias"):
+                    dnorm = gb if dnorm is None else _add_(dnorm, gb)
             elif i == c.merge_idx:
                 dx, dyT = ops.merge_bwd(T, dx, ds_m, L, B * L, D)
             else:
@@ -502,12 +542,16 @@ class HotPath:
             lnws, lndone = self.ln_workspace(dev, ops.layernorm_bwd_workspace_bytes(R, D), main, side if _SIDE_EXTRA else None)
             dx, fin = ops.layernorm_bwd(dln2, x1, mean2, rstd2, P[pre + "norm2.weight"], dres=dx, dx=dx, dxT=dyA,
                                         rowscale=ds_a, rows_per_sample=L, gb=fl["n2"].view(2, D), dxT_colsum=fl["proj"], defer=True, ws=lnws)
-            gb = on_side(fin)
-            lndone()
+            gb = None
+            if need(pre + "norm2.weight") or need(pre + "norm2.bias") or need(pre + "attn.proj.bias"):
+                gb = on_side(fin)
+                lndone()
+                G[pre + "norm2.weight"], G[pre + "norm2.bias"] = gb[0], gb[1]
             G[pre + "attn.proj.bias"] = fl["proj"]
             del dyT
-            tr("%d.dx_ln2" % i, dx); tr("%d.dyA" % i, dyA); tr("%d.gb2" % i, gb)
-            G[pre + "norm2.weight"], G[pre + "norm2.bias"] = gb[0], gb[1]
+            tr("%d.dx_ln2" % i, dx); tr("%d.dyA" % i, dyA)
+            if gb is not None:
+                tr("%d.gb2" % i, gb)
             # ---- attention branch: x1 = x0 + s_a * proj(attn(LN1(x0)))
             if ens_group > 0:
                 # SegGPT feature ensemble (forward: x1 = x0 + s_a * ens(proj(...))): the branch gradient is ens applied to s_a * dx (fp32: the
@@ -522,12 +566,14 @@ class HotPath:
             del dyA
             rcatT = self.relpos(pre, P, True)
             dqkv, dG = ops.attn_bwd_core(qkv, rcat, rcatT, ao, dao, lse, Bc, L, c.heads, c.Hp, c.Wp, c.scale, tables=atab, prep=_ATTN_PREP)
-            drcat = on_side(lambda: ops.attn_bwd_relpos(dG, qkv, nrp, Bc, L, c.heads, c.Hp, c.Wp, out=fl["rel"].view(nrp, hd)), dG, qkv)
+            if need(pre + "attn.rel_pos_h") or need(pre + "attn.rel_pos_w"):
+                # (the dQ kernel still writes its rel-pos partials / dG when the tables are frozen: only this reduction is skipped)
+                drcat = on_side(lambda: ops.attn_bwd_relpos(dG, qkv, nrp, Bc, L, c.heads, c.Hp, c.Wp, out=fl["rel"].view(nrp, hd)), dG, qkv)
+                nh, nw = 2 * c.Hp - 1, 2 * c.Wp - 1
+                G[pre + "attn.rel_pos_h"] = drcat[:nh]
+                G[pre + "attn.rel_pos_w"] = drcat[nh:nh + nw]
             del dG
             tr("%d.dqkv" % i, dqkv)
-            nh, nw = 2 * c.Hp - 1, 2 * c.Wp - 1
-            G[pre + "attn.rel_pos_h"] = drcat[:nh]
-            G[pre + "attn.rel_pos_w"] = drcat[nh:nh + nw]
             param_grads(pre + "attn.qkv.weight", pre + "attn.qkv.bias", dqkv, ln1, fl["qkv"])
             dln1 = ops.linear_dgrad(dqkv, self.w(pre + "attn.qkv.weight", P), out=dao)
             del dqkv
@@ -544,28 +590,33 @@ class HotPath:
             dx, fin = ops.layernorm_bwd(dln1, x0, mean1, rstd1, P[pre + "norm1.weight"], dres=dx, dx=dx, dxT=dyT_next,
                                         rowscale=ds_next if dyT_next is not None else None, rows_per_sample=L, gb=fl["n1"].view(2, D),
                                         dxT_colsum=cs_next, defer=True, ws=lnws)
-            gb = on_side(fin)
-            lndone()
-            G[pre + "norm1.weight"], G[pre + "norm1.bias"] = gb[0], gb[1]
+            if need(pre + "norm1.weight") or need(pre + "norm1.bias") or (cs_next is not None and need("blocks.%d.mlp.fc2.bias" % nxt)):
+                gb = on_side(fin)
+                lndone()
+                G[pre + "norm1.weight"], G[pre + "norm1.bias"] = gb[0], gb[1]
             tr("%d.dx_ln1" % i, dx)
             del x0, ln1, qkv, ao, x1, ln2, gaux, act, atab
             ready([n for n in G if n.startswith(pre)], flat=flat)
-        G["norm.weight"], G["norm.bias"] = dnorm[0], dnorm[1]
+        if dnorm is not None:
+            G["norm.weight"], G["norm.bias"] = dnorm[0], dnorm[1]
         # ---- token assembly + patch embed
         dpe, sums = ops.tokens_bwd(T, dx, S.mask, B, L, D)
-        if S.cols is not None:
-            G["patch_embed.proj.weight"] = ops.linear_wgrad(dpe, S.cols).view(D, 3, c.P, c.P)
-        else:
-            G["patch_embed.proj.weight"] = ops.patch_embed_wgrad(dpe, S.imgs, S.tgts, B, c.Hp, c.Wp, c.P, D).view(D, 3, c.P, c.P)
-        G["patch_embed.proj.bias"] = ops.colsum(dpe)
-        dposemb = torch.zeros_like(P["pos_embed"])
-        ops.pos_bwd(self.pos_operator(dev)[1], sums[0], sums[1], dposemb[0, c.cls:], c.src * c.src, D)
-        G["pos_embed"] = dposemb
-        G["segment_token_x"] = ops.colsum(sums[0]).view(1, 1, 1, D)
-        G["segment_token_y"] = ops.colsum(sums[1]).view(1, 1, 1, D)
-        G["mask_token"] = ops.colsum(sums[2]).view(1, 1, 1, D)
+        if need("patch_embed.proj.weight"):
+            if S.cols is not None:
+                G["patch_embed.proj.weight"] = ops.linear_wgrad(dpe, S.cols).view(D, 3, c.P, c.P)
+            else:
+                G["patch_embed.proj.weight"] = ops.patch_embed_wgrad(dpe, S.imgs, S.tgts, B, c.Hp, c.Wp, c.P, D).view(D, 3, c.P, c.P)
+        if need("patch_embed.proj.bias"):
+            G["patch_embed.proj.bias"] = ops.colsum(dpe)
+        if need("pos_embed"):
+            dposemb = torch.zeros_like(P["pos_embed"])
+            ops.pos_bwd(self.pos_operator(dev)[1], sums[0], sums[1], dposemb[0, c.cls:], c.src * c.src, D)
+            G["pos_embed"] = dposemb
+        for k_, nm in enumerate(("segment_token_x", "segment_token_y", "mask_token")):
+            if need(nm):
+                G[nm] = ops.colsum(sums[k_]).view(1, 1, 1, D)
         small_tail = []
-        if c.seggpt and S.seg_type is not None:
+        if c.seggpt and S.seg_type is not None and (need("type_token_cls") or need("type_token_ins")):
             # SegGPT's two segmentation-type tokens (models_seggpt.py:415-420: added to every token of both streams of the samples of their
             # type): gradient = sum of dx over those samples' rows -- per-sample row weights (1 where the type matches) through the
             # row-scale kernel, then a column sum.  Only reached when a SegGPT module is differentiated (the reference never does).
@@ -575,7 +626,7 @@ class HotPath:
             # there: the reference's DDP wrapper would refuse the unused parameter outright.)
             types_present = set(S.seg_type.reshape(-1).tolist())
             for t_, nm in ((0.0, "type_token_cls"), (1.0, "type_token_ins")):
-                if t_ not in types_present and sync is None:
+                if (t_ not in types_present and sync is None) or not need(nm):
                     continue
                 w = (S.seg_type.reshape(-1) == t_).to(torch.float32)
                 sel = ops.scale_cast(torch.float32, dx, torch.cat((w, w)).contiguous(), L)
@@ -583,6 +634,14 @@ class HotPath:
                 small_tail.append(nm)
         ready(["norm.weight", "norm.bias", "patch_embed.proj.weight", "patch_embed.proj.bias", "pos_embed",
                "segment_token_x", "segment_token_y", "mask_token"] + small_tail)
+        dimgs = dtgts = None
+        if want_imgs or want_tgts:
+            # input gradients (pa_patch_embed_dgrad): d tgts also carries the loss's direct term, -dpred_loss
+            dimgs, dtgts = ops.patch_embed_dgrad(dpe, self.w_patch(P), B, c.Hp, c.Wp, c.P, D, want_imgs, want_tgts,
+                                                 addend=dpred_loss if want_tgts else None, alpha=-1.0)
+        del dpred_loss
+        if want is not None:
+            G = {n: g for n, g in G.items() if g is not None and n in want}
         if side is not None:
             if getattr(self, "tail_probe", None) is not None:      # diagnostics (tools/step_tail.py): when each stream ran dry
                 self.tail_probe[0].record(main)
@@ -593,6 +652,8 @@ class HotPath:
             keep.clear()
         if sync is not None:
             sync.finish()
+        if want_imgs or want_tgts:
+            return G, dimgs, dtgts
         return G
 
 

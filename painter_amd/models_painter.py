@@ -16,6 +16,7 @@ from functools import partial
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from .engine import HotPath, HotPathConfig
 
@@ -105,36 +106,50 @@ class Block(nn.Module):
 
 # ------------------------------------------------------------------------------------------ autograd bridge
 class _HotPathFn(torch.autograd.Function):
-    """One autograd node for the whole network: forward and backward both run in libpainter_hip.so."""
+    """One autograd node for the whole network: forward and backward both run in libpainter_hip.so.
+
+    Differentiable inputs: imgs, tgts (positions 3, 4) and every parameter; both outputs (the loss and pred_patch) carry gradients back.
+    Only the parameters that require a gradient get one, and the frozen ones cost no separable backward work (HotPath.backward `want`).
+    valid, the mask and seg_type are NOT differentiable -- a deliberate gap: the reference's Painter writes `valid` in place under its
+    ignore rule (models_painter.py:448), which autograd refuses for a leaf that requires grad; SegGPT has no ignore rule, there the gap
+    is real and out of scope.  Double backward is not supported (once_differentiable: it raises)."""
 
     @staticmethod
     def forward(ctx, hp, names, opts, imgs, tgts, mask_u8, valid, seg_type, *params):
         P = dict(zip(names, params))
-        need = bool(opts.get("need_grad", True)) and any(ctx.needs_input_grad[8:])   # nothing is saved for inference
+        ng = ctx.needs_input_grad
+        want_params = [n for n, r in zip(names, ng[8:]) if r]
+        ctx.want_imgs, ctx.want_tgts = bool(ng[3]), bool(ng[4])
+        # nothing is saved for inference; frozen parameters' operands are not saved either (a GradSync exchanges every gradient)
+        need = bool(opts.get("need_grad", True)) and (len(want_params) > 0 or ctx.want_imgs or ctx.want_tgts)
+        hook = opts.get("grad_sync")
+        want = None if (hook is not None or len(want_params) == len(names)) else set(want_params)
         loss_out, pred, pred_patch, S = hp.forward(P, imgs, tgts, mask_u8, valid, seg_type, opts.get("merge", -1),
-                                                   opts.get("drop"), need_grad=need)
-        ctx.hp, ctx.S, ctx.names = hp, S, names
+                                                   opts.get("drop"), need_grad=need, want=want)
+        ctx.hp, ctx.S, ctx.names, ctx.want = hp, S, names, want
         ctx.save_for_backward(*params)
         ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(pred_patch)
-        hook = opts.get("grad_sync")
         ctx.grad_sync = hook
         return loss_out[0].clone(), pred_patch
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dloss, dpatch):
-        if dloss is None:
+        if dloss is None and dpatch is None:
             return (None,) * (8 + len(ctx.names))
         params = ctx.saved_tensors
         P = dict(zip(ctx.names, params))
-        dl = dloss.detach().to(torch.float32).reshape(1).contiguous()
-        G = ctx.hp.backward(P, ctx.S, dl, sync=ctx.grad_sync)
+        dl = None if dloss is None else dloss.detach().to(torch.float32).reshape(1).contiguous()
+        dp = None if dpatch is None else dpatch.detach().to(torch.float32).contiguous()
+        wi, wt = ctx.want_imgs, ctx.want_tgts
+        r = ctx.hp.backward(P, ctx.S, dl, sync=ctx.grad_sync, want=ctx.want, want_imgs=wi, want_tgts=wt, dpatch=dp)
+        G, dimgs, dtgts = r if (wi or wt) else (r, None, None)
         ctx.S = None
         grads = []
         for n, p_ in zip(ctx.names, params):
             g = G.get(n)
             grads.append(None if g is None else g.reshape(p_.shape))
-        return (None,) * 8 + tuple(grads)
+        return (None,) * 3 + (dimgs, dtgts) + (None,) * 3 + tuple(grads)
 
 
 class Painter(nn.Module):
@@ -287,8 +302,9 @@ class Painter(nn.Module):
             bool_masked_pos = bool_masked_pos.flatten(1).to(torch.bool).to(imgs.device)
         assert bool_masked_pos.shape[1] == L and bool_masked_pos.shape[0] in (1, B)
         mask_u8 = bool_masked_pos.contiguous().view(torch.uint8)
-        imgs_c = imgs.detach().to(torch.float32).contiguous()
-        tgts_c = tgts.detach().to(torch.float32).contiguous()
+        # (kept in the graph: a bf16 / fp16 input under autocast gets its gradient back in its own dtype)
+        imgs_c = imgs.to(torch.float32).contiguous()
+        tgts_c = tgts.to(torch.float32).contiguous()
         assert imgs_c.shape == (B, 3, self._cfg.H, self._cfg.W) and tgts_c.shape == imgs_c.shape, imgs_c.shape
         if valid is None:
             valid = torch.ones_like(tgts_c)

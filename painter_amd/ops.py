@@ -389,6 +389,21 @@ def patch_embed_wgrad(dpe, imgs, tgts, batch, Hp, Wp, P, D):
     return dw
 
 
+def patch_embed_dgrad(dpe, w, batch, Hp, Wp, P, D, want_imgs=True, want_tgts=True, addend=None, alpha=-1.0):
+    """-> (d imgs, d tgts): f32 NCHW [B, 3, Hp*P, Wp*P] each (None where not asked for) = the inverse im2col of dPE . w.
+    dpe: T [2BL, D] (tokens_bwd); w: T [D, ldw] as patch_embed_fwd takes it; addend (f32 NCHW, optional): d tgts += alpha * addend."""
+    T = dpe.dtype
+    assert dpe.shape == (2 * batch * Hp * Wp, D) and dpe.is_contiguous() and w.dtype == T and w.shape[0] == D and w.stride(1) == 1
+    shape = (batch, 3, Hp * P, Wp * P)
+    dimgs = torch.empty(shape, dtype=torch.float32, device=dpe.device) if want_imgs else None
+    dtgts = torch.empty(shape, dtype=torch.float32, device=dpe.device) if want_tgts else None
+    if addend is not None:
+        assert want_tgts and addend.shape == shape and addend.dtype == torch.float32 and addend.is_contiguous()
+    check(lib.pa_patch_embed_dgrad(code(T), p(dpe), p(w), w.stride(0), p(dimgs), p(dtgts), p(addend), float(alpha), batch, Hp, Wp, P, D,
+                                   stream()), "pa_patch_embed_dgrad")
+    return dimgs, dtgts
+
+
 def tokens_bwd(T, dx0, mask_u8, batch, L, D):
     dpe = torch.empty((2 * batch * L, D), dtype=T, device=dx0.device)
     sums = torch.empty((3, L, D), dtype=torch.float32, device=dx0.device)
@@ -488,6 +503,20 @@ def loss_bwd(pred, tgts, valid, mask_u8, dloss, loss_out, P, kind, beta=0.01):
     check(lib.pa_loss_bwd(p(pred), p(tgts), p(valid), p(mask_u8), mbs, p(dloss), p(loss_out), p(dpred), B, Hi, Wi, P,
                           LOSS_KINDS[kind], float(beta), stream()), "pa_loss_bwd")
     return dpred
+
+
+def pred_bwd(pred, tgts, valid, mask_u8, dloss, loss_out, dpatch, P, kind, want_loss_term=False, beta=0.01):
+    """-> (dpred, dpred_loss): dpred = loss_bwd's term (dloss given) + unpatchify(dpatch) (dpatch given) in one launch; dpred_loss (when
+    want_loss_term) the loss term alone -- minus the loss's direct gradient w.r.t. tgts."""
+    B, _, Hi, Wi = pred.shape
+    dpred = torch.empty_like(pred)
+    dpred_loss = torch.empty_like(pred) if want_loss_term else None
+    if dpatch is not None:
+        assert dpatch.shape == (B, (Hi // P) * (Wi // P), 3 * P * P) and dpatch.dtype == torch.float32 and dpatch.is_contiguous()
+    mbs = 0 if mask_u8.shape[0] == 1 else mask_u8.stride(0)
+    check(lib.pa_pred_bwd(p(pred), p(tgts), p(valid), p(mask_u8), mbs, p(dloss), p(loss_out), p(dpatch), p(dpred), p(dpred_loss), B, Hi, Wi,
+                          P, LOSS_KINDS[kind], float(beta), stream()), "pa_pred_bwd")
+    return dpred, dpred_loss
 
 
 def patchify(pred, Hp, Wp, P):
