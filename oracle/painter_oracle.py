@@ -79,10 +79,10 @@ def expand_mask(bool_masked_pos: torch.Tensor, p: int, dtype) -> torch.Tensor:
     return unpatchify(m, p)
 
 
-def rel_pos_index(q_size: int, k_size: int) -> torch.Tensor:
+def rel_pos_index(q_size: int, k_size: int, device=None) -> torch.Tensor:
     """Painter/util/vitdet_utils.py:88-93 (index built in float then .long())."""
-    q_coords = torch.arange(q_size)[:, None] * max(k_size / q_size, 1.0)
-    k_coords = torch.arange(k_size)[None, :] * max(q_size / k_size, 1.0)
+    q_coords = torch.arange(q_size, device=device)[:, None] * max(k_size / q_size, 1.0)
+    k_coords = torch.arange(k_size, device=device)[None, :] * max(q_size / k_size, 1.0)
     rel = (q_coords - k_coords) + (k_size - 1) * max(q_size / k_size, 1.0)
     return rel.long()
 
@@ -96,7 +96,7 @@ def get_rel_pos(q_size: int, k_size: int, rel_pos: torch.Tensor) -> torch.Tensor
         r = r.reshape(-1, max_rel_dist).permute(1, 0)
     else:
         r = rel_pos
-    return r[rel_pos_index(q_size, k_size)]
+    return r[rel_pos_index(q_size, k_size, r.device)]
 
 
 def abs_pos_operator(src: int, h: int, w: int, dtype=torch.float32) -> torch.Tensor:
@@ -204,7 +204,7 @@ def forward_encoder(P, cfg: OracleConfig, imgs, tgts, bool_masked_pos, seg_type=
     x = x + pos
     y = y + pos
     if cfg.seggpt:
-        type_emb = torch.zeros(B, 1, 1, C, dtype=x.dtype)
+        type_emb = torch.zeros(B, 1, 1, C, dtype=x.dtype, device=x.device)
         type_emb[seg_type.reshape(-1) == 0] = P["type_token_cls"].reshape(1, 1, C)
         type_emb[seg_type.reshape(-1) == 1] = P["type_token_ins"].reshape(1, 1, C)
         x = x + type_emb
@@ -244,8 +244,8 @@ def forward_loss(cfg: OracleConfig, pred, tgts, bool_masked_pos, valid):
     SegGPT: models_seggpt.py:448-469 (no ignore rule, no +1e-2)."""
     mask = expand_mask(bool_masked_pos, cfg.patch_size, pred.dtype)
     if not cfg.seggpt:
-        mean = torch.tensor(IMAGENET_MEAN, dtype=tgts.dtype)[None, :, None, None]
-        std = torch.tensor(IMAGENET_STD, dtype=tgts.dtype)[None, :, None, None]
+        mean = torch.tensor(IMAGENET_MEAN, dtype=tgts.dtype, device=tgts.device)[None, :, None, None]
+        std = torch.tensor(IMAGENET_STD, dtype=tgts.dtype, device=tgts.device)[None, :, None, None]
         inds_ign = ((tgts * std + mean) * (1 - 1.0 * mask)).sum((1, 2, 3)) < 100 * 3
         if inds_ign.sum() > 0:
             valid[inds_ign] = 0.0
@@ -269,7 +269,7 @@ def forward(P, cfg: OracleConfig, imgs, tgts, bool_masked_pos=None, valid=None, 
     -> (loss, patchify(pred), bool_masked_pos[bool])."""
     L = cfg.grid[0] * cfg.grid[1]
     if bool_masked_pos is None:
-        bool_masked_pos = torch.zeros((imgs.shape[0], L), dtype=torch.bool)
+        bool_masked_pos = torch.zeros((imgs.shape[0], L), dtype=torch.bool, device=imgs.device)
     else:
         bool_masked_pos = bool_masked_pos.flatten(1).to(torch.bool)
     latent = forward_encoder(P, cfg, imgs, tgts, bool_masked_pos, seg_type, merge_between_batch, drop_scales)

@@ -169,9 +169,12 @@ def test_gemm256_mixed_full_and_half_tiles_bit_identical_to_uniform_tiles(M, N, 
     """Round 6: multi-round launches run whole rounds of 256-row tiles followed by HALF tiles of 128 rows for the remaining rows (gemm256.h,
     MIXED: fc1 forward / fc2 data gradient 48 x 16 full + 2 x 16 half tiles, qkv forward 42 x 12 + 14 x 12, the decoder embedding 48 x 64 +
     2 x 64; a ragged M whose last half tile is mostly padding; a shape whose rule picks a mixed plan with many half tiles).  In a half tile
-    both wave rows work on the 128 rows of wave row 0 (row 0: phases 0 / 1, row 1: phases 2 / 3) -- same ascending K order per output element,
-    so every epilogue must return the bits of the uniform tiling (pa_debug_set(12, 1) = the round-5 plans), including the column sums the
-    fc2 data-gradient epilogue emits (one partial row per (row tile, wave row): another row count, same sums up to fp32 summation order)."""
+    a K tile is two phases -- the MFMA segments of phases 0 / 1 of the full tile's schedule, on wave row 0's unit -- with one barrier each,
+    all eight waves in step: the same ascending K order per output element, so every epilogue must return the bits of the uniform tiling
+    (pa_debug_set(12, 1) = the round-5 plans), including the column sums the fc2 data-gradient epilogue emits (one partial row per (row
+    tile, wave row): another row count, same sums up to fp32 summation order).  Besides the rule's own choice (which may or may not be
+    mixed, depending on PA_G256_HALF_COST and the rule), the mixed kernel is forced (pa_debug_set(12, 2) + pa_debug_set(14, nfull)) with
+    nfull = the most full rows that leave a half tile and with half the rows in half tiles."""
     from painter_amd._lib import lib
     T = torch.bfloat16
     x, w, b = gen((M, K), 1, 1.0, T), gen((N, K), 2, 0.05, T), gen((N,), 3)
@@ -190,16 +193,24 @@ def test_gemm256_mixed_full_and_half_tiles_bit_identical_to_uniform_tiles(M, N, 
         if pix and M == 12544:
             res.append(ops.linear_pixshuf(x, w, b, 8, 56, 28, 16, 64))
         return res, cs
+    plans = {"rule": {12: 0}, "forced_most_full": {12: 2, 14: (M - 1) // 256}, "forced_half_full": {12: 2, 14: M // 512}}
+    saved = {k: lib.pa_debug_get(k) for k in (4, 12, 14)}
     try:
+        assert lib.pa_debug_set(4, 0) == 0
         assert lib.pa_debug_set(12, 1) == 0
         ref, cs_ref = run()
-        assert lib.pa_debug_set(12, 0) == 0
-        got, cs_got = run()
+        outs = {}
+        for name, kv in plans.items():
+            for k, v in kv.items():
+                assert lib.pa_debug_set(k, v) == 0
+            outs[name] = run()
     finally:
-        lib.pa_debug_set(12, 0)
-    for a, r in zip(got, ref):
-        assert torch.equal(a, r)
-    assert relerr(cs_got, cs_ref) < 1e-5 and relerr(cs_got, got[4].double().sum(0)) < 4e-3
+        for k, v in saved.items():
+            lib.pa_debug_set(k, v)
+    for name, (got, cs_got) in outs.items():
+        for a, r in zip(got, ref):
+            assert torch.equal(a, r), name
+        assert relerr(cs_got, cs_ref) < 1e-5 and relerr(cs_got, got[4].double().sum(0)) < 4e-3, name
     assert relerr(ref[0].float(), x.float() @ w.float().t() + b) < 1e-2
 
 
@@ -945,3 +956,152 @@ def test_c_abi_of_the_hot_path_rejects_bad_shapes_instead_of_reading_out_of_boun
     with pytest.raises(RuntimeError):
         ops.linear_fwd(torch.zeros(4, 12, dtype=torch.bfloat16, device=DEV), torch.zeros(16, 12, dtype=torch.bfloat16, device=DEV), torch.zeros(16, device=DEV))
     torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------------------------------------ glue and loss kernels at full width
+def _glue_widths():
+    """(batch, L, D) of the two timed configurations: ViT-L (bench.py's per-GPU batch 8) and ViT-H/14 (per-GPU batch 4)."""
+    from oracle import painter_oracle as O
+    return [pytest.param(batch, cfg.grid[0] * cfg.grid[1], cfg.embed_dim, id=name)
+            for name, cfg, batch in (("vit_large", O.vit_large_config(), 8), ("vit_huge", O.vit_huge_config(), 4))]
+
+
+def dgen(shape, seed, scale=1.0, dtype=torch.float32):
+    """gen() drawn on the device (full-width operands)."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    return (torch.randn(shape, generator=g, device=DEV) * scale).to(dtype)
+
+
+def with_bf16_ties(x, seed):
+    """x with about 1 % of its entries replaced by fp32 values exactly half-way between two bf16 values (round-to-nearest-even decides)."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    pick = torch.rand(x.shape, generator=g, device=DEV) < 0.01
+    tie = ((x.view(torch.int32) & -65536) | 0x8000).view(torch.float32)
+    return torch.where(pick, tie, x)
+
+
+@pytest.mark.parametrize("T", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("batch,L,D", _glue_widths())
+def test_merge_scale_and_cast_kernels_bit_exact(T, batch, L, D):
+    """pa_merge_fwd, pa_merge_bwd (DropPath row scales that differ between the two halves, and none), pa_scale_cast and pa_cast_bf16 against
+    the same fp32 expression in torch, bit for bit; bf16 results against torch's round-to-nearest-even cast (exact ties included)."""
+    R = batch * L
+    x = dgen((2 * R, D), 1)
+    assert torch.equal(ops.merge_fwd(x, R, D), (x[:R] + x[R:]) * 0.5)
+    dm = with_bf16_ties(dgen((R, D), 2), 3)
+    rowscale = dgen((2 * batch,), 4).abs() + 0.5                    # one per sample of the 2B-sample batch in front of the merge
+    h = dm * 0.5
+    for rs in (rowscale, None):
+        dx, dxT = ops.merge_bwd(T, dm, rs, L, R, D)
+        assert torch.equal(dx, torch.cat([h, h]))
+        want = torch.cat([h, h]) if rs is None else torch.cat([h, h]) * rs.repeat_interleave(L)[:, None]
+        assert torch.equal(dxT, want.to(T)), rs is None
+    xs = with_bf16_ties(dgen((2 * R, D), 5), 6)
+    assert torch.equal(ops.scale_cast(T, xs, rowscale, L), (xs * rowscale.repeat_interleave(L)[:, None]).to(T))
+    assert torch.equal(ops.scale_cast(T, xs, None, L), xs.to(T))
+    if T == torch.bfloat16:
+        flat = with_bf16_ties(dgen((3 * D * D + 3,), 7), 8)         # an element count that is no multiple of 4: the scalar tail
+        assert torch.equal(ops.cast_bf16(flat), flat.to(torch.bfloat16))
+
+
+@pytest.mark.parametrize("batch,L,D", _glue_widths())
+def test_ensemble_resid_kernel_bit_exact(batch, L, D):
+    """pa_ensemble_resid (models_seggpt.py:220-232): x1 = x0 + a on the prompt half of the tokens, x0 + the group mean of a on the query
+    half (l >= L / 2) -- the kernel's fp32 expression (sum in sample order from 0, times 1 / G) in torch, bit for bit, for groups of 1,
+    2 and the whole batch."""
+    x0, a = dgen((batch * L, D), 1), dgen((batch * L, D), 2)
+    x3, a3 = x0.view(batch, L, D), a.view(batch, L, D)
+    half = L // 2
+    for group in (1, 2, batch):
+        want = (x3 + a3).clone()
+        inv = torch.tensor(1.0, dtype=torch.float32) / group
+        for g0 in range(0, batch, group):
+            m = torch.zeros((L - half, D), device=DEV)
+            for b in range(g0, g0 + group):
+                m = m + a3[b, half:]
+            want[g0:g0 + group, half:] = x3[g0:g0 + group, half:] + m * inv
+        got = ops.ensemble_resid(x0, a, batch, group, L, D)
+        assert torch.equal(got.view(batch, L, D), want), group
+        assert group > 1 or torch.equal(got, x0 + a)
+
+
+@pytest.mark.parametrize("T", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("batch,L,D", _glue_widths())
+def test_tokens_bwd_kernel_bit_exact(T, batch, L, D):
+    """pa_tokens_bwd (models_painter.py:392-409 backward): dPE of the x stream = dx, of the y stream = dy * (1 - mask), and the three
+    per-token sums over the batch (dx, dy, mask * dy: the segment-token, pos-embedding and mask-token gradients) -- in sample order,
+    bit for bit, with a mask per sample and with one mask shared by the batch (mask_batch_stride = 0)."""
+    R = batch * L
+    dx0 = dgen((2 * R, D), 1)
+    gx, gy = dx0[:R].view(batch, L, D), dx0[R:].view(batch, L, D)
+    g = torch.Generator(device=DEV).manual_seed(2)
+    for shared in (False, True):
+        mask = torch.rand((1 if shared else batch, L), generator=g, device=DEV) < 0.4
+        dpe, sums = ops.tokens_bwd(T, dx0, mask.to(torch.uint8), batch, L, D)
+        w = mask.float().expand(batch, L)[:, :, None]
+        assert torch.equal(dpe, torch.cat([gx, gy * (1 - w)]).reshape(2 * R, D).to(T)), shared
+        sx, sy, sm = (torch.zeros((L, D), device=DEV) for _ in range(3))
+        for b in range(batch):
+            sx, sy, sm = sx + gx[b], sy + gy[b], sm + w[b] * gy[b]
+        assert torch.equal(sums[0], sx) and torch.equal(sums[1], sy) and torch.equal(sums[2], sm), shared
+
+
+def _loss_case(cfg, batch, seed):
+    """Full-size loss inputs on a 2^-12 grid (pred - tgts is exact in fp32, as in the fp64 reference): sample 0's target is the normalised
+    black image (its unmasked sum is far below the ignore rule's 300), the others are not; `valid` carries a zero region and a
+    pose-style weight of 10."""
+    from oracle import painter_oracle as O
+    g = torch.Generator().manual_seed(seed)
+    H, W = cfg.img_size
+    q = 2.0 ** -12
+    tgts = torch.round(torch.randn(batch, 3, H, W, generator=g) / q) * q
+    black = -torch.tensor(O.IMAGENET_MEAN) / torch.tensor(O.IMAGENET_STD)
+    tgts[0] = (torch.round(black / q) * q)[:, None, None]
+    pred = tgts + torch.round(torch.randn(tgts.shape, generator=g) * (0.02 / q)) * q
+    valid = torch.ones_like(tgts)
+    valid[1, :, H // 4:H // 2, W // 8:W // 2] = 0.0
+    valid[-1, :, :H // 8] = 10.0
+    mask = torch.rand(batch, cfg.grid[0] * cfg.grid[1], generator=g) < 0.5
+    return pred, tgts, valid, mask
+
+
+@pytest.mark.parametrize("kind", ["smoothl1", "l1", "l2", "l1l2"])
+@pytest.mark.parametrize("model", ["vit_large", "vit_huge"])
+def test_loss_kernels_full_size_vs_fp64(model, kind):
+    """pa_loss_fwd (two-stage block sums over ~10^7 elements), pa_loss_bwd and pa_pred_bwd at the full image size of ViT-L (P = 16, B = 8)
+    and ViT-H/14 (P = 14, B = 4), every loss kind, against the oracle's loss and its autograd in fp64.  Painter mode: a mask per sample,
+    the ignore rule (fires on sample 0 only; `valid` is zeroed in place), denominator + 1e-2.  Shared mask (mask_batch_stride = 0) without
+    the rule and without the 1e-2, as SegGPT.  The denominator is a sum of small integers: exact."""
+    import dataclasses
+    from oracle import painter_oracle as O
+    base, batch = (O.vit_large_config(), 8) if model == "vit_large" else (O.vit_huge_config(), 4)
+    P = base.patch_size
+    pred, tgts, valid, mask = _loss_case(base, batch, 5)
+    dloss = torch.tensor([0.75], device=DEV)
+    dpatch = dgen((batch, mask.shape[1], 3 * P * P), 6)
+    errs = {}
+    for shared in (False, True):
+        cfg = dataclasses.replace(base, loss_func=kind, seggpt=shared)
+        m = mask[:1].expand(batch, -1) if shared else mask
+        mask_u8 = (mask[:1] if shared else mask).to(torch.uint8).to(DEV)
+        vd = valid.clone().to(DEV)
+        pd, td = pred.to(DEV), tgts.to(DEV)
+        out = ops.loss_fwd(pd, td, vd, mask_u8, P, ignore_rule=not shared, eps_den=0.0 if shared else 1e-2, kind=kind)
+        p64, v64 = pred.double().requires_grad_(True), valid.double()
+        lo = O.forward_loss(cfg, p64, tgts.double(), m, v64)
+        lo.backward()
+        assert torch.equal(vd.cpu().double(), v64), shared                          # the in-place ignore rule zeroed the same samples
+        assert shared or (float(v64[0].abs().max()) == 0.0 and all(float(v64[b].abs().max()) > 0 for b in range(1, batch)))
+        count = float((O.expand_mask(m, P, torch.float64) * v64).sum())
+        assert count < 2 ** 24 and float(out[1]) == float(torch.tensor(count, dtype=torch.float32) + torch.tensor(0.0 if shared else 1e-2))
+        tag = "shared" if shared else "painter"
+        errs["loss_" + tag] = abs(float(out[0]) - float(lo)) / abs(float(lo))
+        dpred = ops.loss_bwd(pd, td, vd, mask_u8, dloss, out, P, kind)
+        ref = 0.75 * p64.grad.to(DEV)
+        errs["loss_bwd_" + tag] = _rel64(dpred, ref)
+        dp2, dpl = ops.pred_bwd(pd, td, vd, mask_u8, dloss, out, dpatch, P, kind, want_loss_term=True)
+        assert torch.equal(dpl, dpred), shared                                       # the loss term is pa_loss_bwd's, bit for bit
+        errs["pred_bwd_" + tag] = _rel64(dp2, ref + O.unpatchify(dpatch.double(), P))
+    print("loss kernels %s %s:" % (model, kind), {k: "%.2e" % v for k, v in errs.items()})
+    assert max(v for k, v in errs.items() if k.startswith("loss_") and "bwd" not in k) < 1e-5, errs
+    assert max(v for k, v in errs.items() if "bwd" in k) < 1e-6, errs              # test_pred_bwd_kernel_vs_fp64's gate

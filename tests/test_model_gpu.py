@@ -16,7 +16,7 @@ from tests import golden_util as G
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
-    from painter_amd import models_painter, models_seggpt
+    from painter_amd import models_painter, models_seggpt, ops
 
 
 def build(cfg, seed, dtype, train=False):
@@ -596,6 +596,64 @@ def test_h14_generalised_taps_other_depth_vs_oracle(dtype):
     worst = max((G.rel_fro(p.grad.cpu(), Pg[n].grad), n) for n, p in m.named_parameters())
     assert worst[0] < tol_g, worst
     assert all(float(p.grad.abs().max()) > 0 for n, p in m.named_parameters() if "blocks.15." in n and "bias" not in n)
+
+
+DEV = "cuda"
+
+
+def _oracle_on_device(cfg, P, imgs, tgts, mask, valid, dtype, autocast=False):
+    """The oracle's loss, patchified pred and parameter gradients, run on the GPU in `dtype` (optionally under CUDA bf16 autocast)."""
+    Pd = {k: v.to(DEV, dtype).requires_grad_(True) for k, v in P.items()}
+    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+        lo, po, _ = O.forward(Pd, cfg, imgs.to(DEV, dtype), tgts.to(DEV, dtype), mask.to(DEV), valid.to(DEV, dtype))
+    lo.backward()
+    out = float(lo), po.detach().double(), {k: v.grad.double() for k, v in Pd.items()}
+    del Pd, lo, po
+    return out
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_vit_huge_full_width_vs_oracle_in_fp64(dtype):
+    """ViT-H/14 at full width (vit_huge_config(): embed 1280, 16 heads of 80, depth 32 with the generalised taps, 64 x 32 tokens) through
+    the class constructor, eval mode, B = 1, against the oracle in fp64 on the device.  fp32 build: the gates of
+    test_h14_generalised_taps_other_depth_vs_oracle.  bf16 build: the loss, the pred and every weight matrix's gradient within 1.25 x the
+    oracle's own CUDA bf16-autocast deviation from fp64 on the same case; the attention of all 32 blocks on the head_dim-80 generation-2
+    kernels."""
+    cfg = O.vit_huge_config()
+    m, P = build(cfg, 81, dtype)
+    c0 = ops.attn_launch_counts()
+    loss, pred, _, _ = run_painter(m, cfg, 1, 82, "random")
+    c1 = ops.attn_launch_counts()
+    loss = loss.item()
+    pred = pred.detach().double()
+    grads = {n: p.grad.double() for n, p in m.named_parameters()}
+    del m
+    torch.cuda.empty_cache()
+    imgs, tgts, mask, valid = O.synthetic_batch(cfg, 1, 82, "random")
+    lo, po, go = _oracle_on_device(cfg, P, imgs, tgts, mask, valid, torch.float64)
+    torch.cuda.empty_cache()
+    rf = lambda a, b: float((a - b).norm() / b.norm().clamp_min(1e-30))
+    e_loss, e_pred = abs(loss - lo) / abs(lo), rf(pred, po)
+    errs = {n: rf(grads[n], go[n]) for n in grads}
+    assert all(float(grads[n].abs().max()) > 0 for n in grads if "blocks.%d." % (cfg.depth - 1) in n and "bias" not in n)
+    if dtype == "fp32":
+        worst = max((v, n) for n, v in errs.items())
+        print("ViT-H/14 fp32 build vs fp64 oracle: loss %.2e, pred %.2e, worst gradient %.2e (%s)" % (e_loss, e_pred, worst[0], worst[1]))
+        assert e_loss < 1e-4 and e_pred < 2e-4 and worst[0] < 1e-3, (e_loss, e_pred, worst)
+        return
+    for k in ("fwd", "bwd"):
+        d = [c1[k][i] - c0[k][i] for i in range(3)]
+        assert d[1] >= cfg.depth and d[0] == 0 and d[2] == 0, (k, d)
+    la, pa, ga = _oracle_on_device(cfg, P, imgs, tgts, mask, valid, torch.float32, autocast=True)
+    y_loss, y_pred = abs(la - lo) / abs(lo), rf(pa, po)
+    mats = [n for n in grads if n.endswith("weight") and grads[n].dim() >= 2]
+    ratio = {n: errs[n] / rf(ga[n], go[n]) for n in mats}
+    worst = max((v, n) for n, v in ratio.items())
+    print("ViT-H/14 bf16 build vs fp64 oracle (oracle's own bf16 autocast): loss %.2e (%.2e), pred %.2e (%.2e); %d weight matrices, worst "
+          "gradient ratio %.2f (%s: %.2e vs %.2e)" % (e_loss, y_loss, e_pred, y_pred, len(mats), worst[0], worst[1], errs[worst[1]],
+                                                      rf(ga[worst[1]], go[worst[1]])))
+    assert e_loss <= 1.25 * y_loss and e_pred <= 1.25 * y_pred, (e_loss, y_loss, e_pred, y_pred)
+    assert worst[0] <= 1.25, worst
 
 
 # ------------------------------------------------------------------------------------------ loss variants, pose weighting
