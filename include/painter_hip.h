@@ -37,8 +37,8 @@ enum {
 };
 
 /* Bumped whenever an entry point's argument list changes (2: `tables` in pa_attn_fwd / pa_attn_bwd; 3: `head_dim` in the attention and
- * rel-pos entry points; 4: `dxT_colsum` in pa_layernorm_bwd, `relpos_part` in pa_attn_bwd, `dx_colsum` in pa_linear_dgrad; 5: the bf16 GELU side output is gelu'(pre), pa_debug_set(9) is a test knob of the conv3x3 weight gradient, pa_attn4_trace is gone, pa_attn_bwd takes `out` / `ldo`, pa_debug_get / pa_attn_launch_counts are new; 6: the bf16 GELU side output is an 8-bit code (uint8, row pitch ldo bytes), pa_debug_set knobs 10 .. 15).  painter_amd/_lib.py refuses a library whose pa_abi_version() differs from the header it parsed. */
-#define PA_ABI_VERSION 6
+ * rel-pos entry points; 4: `dxT_colsum` in pa_layernorm_bwd, `relpos_part` in pa_attn_bwd, `dx_colsum` in pa_linear_dgrad; 5: the bf16 GELU side output is gelu'(pre), pa_debug_set(9) is a test knob of the conv3x3 weight gradient, pa_attn4_trace is gone, pa_attn_bwd takes `out` / `ldo`, pa_debug_get / pa_attn_launch_counts are new; 6: the bf16 GELU side output is an 8-bit code (uint8, row pitch ldo bytes), pa_debug_set knobs 10 .. 15; 7: the *_skip entry points (DropPath skipping) and pa_debug_set knob 16 -- every earlier entry point keeps its argument list).  painter_amd/_lib.py refuses a library whose pa_abi_version() differs from the header it parsed. */
+#define PA_ABI_VERSION 7
 int pa_abi_version(void);
 /* diagnostics only (tools/): which = 0 start-up stagger of alternate workgroup rows of the 256x256 GEMM in shader cycles,
  * 1 drop that kernel's epilogue stores (never set by the product path); 2 = tile order of that kernel: 0 blocked 4 x 8 patches per XCD and, for
@@ -50,7 +50,9 @@ int pa_abi_version(void);
  * 8 = generation-3 attention: workgroups with idle waves dispatched last: 0 default (off since round 5), 1 off, 2 on;
  * 9 = tests: cap on the workgroups of the conv3x3 weight-gradient kernel (0 = 512), so that small images make a workgroup walk many tiles;
  * 10 = LayerNorm backward: 0 rows split over the workgroup's waves wherever D >= 1024 (default), 1 one wave per row everywhere (the kernel of
- * rounds 1 - 4) -- index 5 until round 5, where it collided with the ILV override; 11 .. 15 = round-6 experiment knobs (csrc/common.h). */
+ * rounds 1 - 4) -- index 5 until round 5, where it collided with the ILV override; 11 .. 15 = round-6 experiment knobs (csrc/common.h);
+ * 16 = DropPath skipping in the *_skip entry points: 0 default (on unless the environment has PAINTER_AMD_DROP_SKIP=0), 1 off (the factor vector
+ * is ignored: exactly the launches of the entry points without _skip), 2 on. */
 int pa_debug_set(int which, int value);
 int pa_debug_get(int which);      /* the value last set (-1: no such knob) -- callers that change a knob temporarily restore what they found */
 
@@ -66,6 +68,21 @@ int pa_linear_fwd(int dtype, int epilogue, const void* x /*T [M,K]*/, int64_t ld
                   const float* bias /*[N]*/, void* out, void* out2, int64_t ldo, const float* resid /*f32 [M,N] ld=ldo*/,
                   const float* rowscale /*[M/rows_per_sample] or NULL*/, int rows_per_sample, int M, int N, int K,
                   hipStream_t stream);
+/* DropPath skipping (ABI 7).  The *_skip entry points take the DropPath factor vector of the residual branch the call belongs to: rowskip f32
+ * [samples], one factor per `skip_rows_per_sample` contiguous rows (attention: one per sample of the batch).  A sample whose factor is exactly 0
+ * contributes nothing to anything that leaves the step (forward: its branch output is multiplied by 0; backward: its incoming gradient IS 0),
+ * so its work is not done, and everything it would have written is written with defined values instead:
+ *   pa_linear_fwd_skip / pa_linear_dgrad_skip (bf16 256 x 256 kernel only): a row tile whose rows all belong to dropped samples runs its epilogue on
+ *       a zero accumulator -- bias; gelu(bias) and its GELU' code; resid; zero rows and a zero column-sum partial.  A tile that touches a kept
+ *       sample runs in full, so rows of a dropped sample near its borders may hold the ordinary result.
+ *   pa_attn_fwd_skip / pa_attn_bwd_skip (28-token-wide bf16 kernels only): zeros in the sample's out rows, lse entries and table tiles; zero
+ *       dq / dk / dv rows, a zero rel-pos partial (or dG rows) and Delta field.
+ * Kernels that do not implement it (exact-fp32 build, other grids) ignore the vector: each call's skip is valid on its own.  rowskip = NULL, or
+ * knob 16 = off: the same launches as the entry point without _skip.  Results agree with the unskipped computation as numbers wherever the
+ * skipped branch is finite (the sign of an exact zero may differ; a dropped branch that overflowed no longer poisons its sample through 0 * inf). */
+int pa_linear_fwd_skip(int dtype, int epilogue, const void* x, int64_t ldx, const void* w, const float* bias, void* out, void* out2,
+                       int64_t ldo, const float* resid, const float* rowscale, int rows_per_sample, int M, int N, int K,
+                       const float* rowskip, int skip_rows_per_sample, hipStream_t stream);
 /* decoder_embed + pixel shuffle 'nhwpqc->nchpwq' (models_painter.py:423-428); output is NHWC [B, Hp*P, Wp*P, C] T */
 int pa_linear_pixshuf(int dtype, const void* x, int64_t ldx, const void* w /*T [P*P*C, K]*/, const float* bias,
                       void* out_nhwc, int batch, int Hp, int Wp, int P, int C, int K, hipStream_t stream);
@@ -77,6 +94,9 @@ int64_t pa_linear_dgrad_workspace_bytes(int M, int K);
 int pa_linear_dgrad(int dtype, const void* dy /*T [M,N]*/, int64_t lddy, const void* w /*T [N,K]*/,
                     const void* gelu_aux /*NULL, or what pa_linear_fwd(PA_EPI_BIAS_GELU) put into out2: f32 [M,K] ld=lddx | uint8 [M,K] pitch lddx bytes*/, void* dx /*T [M,K]*/, int64_t lddx, float* dx_colsum,
                     void* workspace, int M, int N, int K, hipStream_t stream);
+int pa_linear_dgrad_skip(int dtype, const void* dy, int64_t lddy, const void* w, const void* gelu_aux, void* dx, int64_t lddx, float* dx_colsum,
+                         void* workspace, int M, int N, int K, const float* rowskip /* of the rows of dy / dx */, int skip_rows_per_sample,
+                         hipStream_t stream);
 int64_t pa_linear_wgrad_workspace_bytes(int dtype, int M, int N, int K);
 int pa_linear_wgrad(int dtype, const void* dy /*T [M,N]*/, int64_t lddy, const void* x /*T [M,K]*/, int64_t ldx,
                     float* dw /*f32 [N,K]*/, void* workspace, int M, int N, int K, hipStream_t stream);
@@ -129,6 +149,9 @@ int pa_attn_launch_counts(long long* out6);
 int pa_attn_trace(int enable, unsigned long long* host_out);
 int pa_attn_fwd(int dtype, const void* qkv, int64_t ldq, const void* rcat, void* out, int64_t ldo, float* lse,
                 void* tables, int batch, int L, int heads, int Hp, int Wp, int head_dim, float scale, hipStream_t stream);
+int pa_attn_fwd_skip(int dtype, const void* qkv, int64_t ldq, const void* rcat, void* out, int64_t ldo, float* lse,
+                     void* tables, int batch, int L, int heads, int Hp, int Wp, int head_dim, float scale, const float* rowskip /*[batch] or NULL*/,
+                     hipStream_t stream);
 
 /* autograd of pa_attn_fwd (no reference source: torch autograd of the lines above).
  *   delta  : f32 [batch*heads, L] = rowsum(dO o O)                      (pa_attn_bwd_delta)
@@ -165,6 +188,10 @@ int pa_attn_bwd(int dtype, const void* qkv, int64_t ldq, const void* rcat, const
                 int64_t lddo, const float* lse, const float* delta, void* dqkv, void* dG, void* relpos_part, void* aux,
                 void* tables, const void* out, int64_t ldo, int batch, int L, int heads, int Hp, int Wp, int head_dim, float scale,
                 hipStream_t stream);
+int pa_attn_bwd_skip(int dtype, const void* qkv, int64_t ldq, const void* rcat, const void* rcatT, const void* dout,
+                     int64_t lddo, const float* lse, const float* delta, void* dqkv, void* dG, void* relpos_part, void* aux,
+                     void* tables, const void* out, int64_t ldo, int batch, int L, int heads, int Hp, int Wp, int head_dim, float scale,
+                     const float* rowskip /*[batch] or NULL*/, hipStream_t stream);
 int64_t pa_attn_bwd_relpos_workspace_bytes(int dtype, int batch, int L, int heads, int Hp, int Wp, int head_dim);
 int pa_attn_bwd_relpos_reduce(const void* relpos_part, float* drcat, void* workspace, int batch, int L, int heads, int Hp, int Wp,
                               int head_dim, hipStream_t stream);

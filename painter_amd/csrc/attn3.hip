@@ -52,23 +52,30 @@ namespace a3 {
 
 // =============================================================================================== forward
 // LDS: [K img | V img] x STAGES | thT 4 waves x [Hp][32 q] bf16 | 7 one-hot images (the per-wave T rows alias them during the prologue)
-template <int STAGES>
+template <int STAGES, bool SKIP = false>
 __global__ __launch_bounds__(NT, STAGES == 1 ? 4 : 2) void fwd_kernel(const bf16* __restrict__ qkv, size_t ldq, const bf16* __restrict__ rcat,
                                                                       bf16* __restrict__ out, size_t ldo, float* __restrict__ lse,
                                                                       unsigned char* __restrict__ tables, int L, int H, int Hp, int NRP,
-                                                                      float scale, int nblk, int xcd_map, int abl) {
+                                                                      float scale, int nblk, int xcd_map, int abl, const float* __restrict__ rowskip) {
+    // rowskip (may be NULL): the DropPath factors of this branch, f32 [samples].  A workgroup whose sample's factor is 0 reads nothing of
+    // it and writes zeros to its out rows, lse entries and table tiles (everything a later kernel may read stays defined)
     // abl (diagnostics, PA_ATTN3_FWD_ABL; results WRONG when set): 16 no key loop, 32 no table build in the prologue
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, ql = lane & 31;
     int blk, bh;
-    wg_coords(nblk, xcd_map, blk, bh, (L / 32) / NW);
+    bool drop = false;
+    if constexpr (SKIP) drop = wg_coords_skip(nblk, xcd_map, blk, bh, rowskip, H);          // kept samples first, balanced over the XCDs
+    else wg_coords(nblk, xcd_map, blk, bh, (L / 32) / NW);
     const int b = bh / H, h = bh % H, D = H * ATT_HD;
     const bf16* base = qkv + (size_t)b * L * ldq + h * ATT_HD;
     const bf16* kbase = base + D;
     const bf16* vbase = base + 2 * D;
     const int qt = blk * NW + wave;
-    const bool valid = qt * 32 < L;
+    // (workgroup-uniform.  A dropped sample's workgroup keeps the kernel's frame -- no wave is valid, the key loop has no trips -- and
+    // writes its zeros at the end: an early return in front of the prologue made the register allocator spill inside the key loop)
+    const bool valid = qt * 32 < L && !drop;
     const int q = qt * 32 + ql;
+    const int ntile = L / 32;
     unsigned char* thT = smem + STAGES * STAGE_QK + wave * Hp * 64;
     unsigned char* eimg = smem + STAGES * STAGE_QK + NW * Hp * 64;
     unsigned char* twimg = eimg + wave * 2048;
@@ -76,7 +83,6 @@ __global__ __launch_bounds__(NT, STAGES == 1 ? 4 : 2) void fwd_kernel(const bf16
     la.init(lane);
     EAddr ea;
     ea.init(lane);
-    const int ntile = L / 32;
     Stager ks, vs;
     ks.load(kbase, ldq, tid);
     vs.load(vbase, ldq, tid);
@@ -178,7 +184,7 @@ __global__ __launch_bounds__(NT, STAGES == 1 ? 4 : 2) void fwd_kernel(const bf16
         }
         __syncthreads();
     };
-    for (int a = 0; a < ((abl & 16) ? 0 : Hp / RPP); ++a) {
+    for (int a = 0; a < (((abl & 16) || drop) ? 0 : Hp / RPP); ++a) {
         body(std::integral_constant<int, 0>{}, a);
         body(std::integral_constant<int, 1>{}, a);
         body(std::integral_constant<int, 2>{}, a);
@@ -206,6 +212,14 @@ __global__ __launch_bounds__(NT, STAGES == 1 ? 4 : 2) void fwd_kernel(const bf16
         stage_rows(stg, oacc, 1.f / lt, lane);
         write_rows(stg, out + (size_t)(b * L + qt * 32) * ldo + h * ATT_HD, ldo, lane);   // same-wave LDS ops are ordered
     }
+    if (drop && qt * 32 < L) {
+        zero_rows(out + (size_t)(b * L + qt * 32) * ldo + h * ATT_HD, ldo, lane);
+        if (g == 0) lse[(size_t)bh * L + q] = 0.f;
+        if (tables != nullptr) {
+            unsigned char* tt = tables + ((size_t)bh * ntile + qt) * ttile_bytes(Hp);
+            for (int c = lane; c < ttile_bytes(Hp) / 16; c += 64) *reinterpret_cast<uint4*>(tt + c * 16) = zero4();
+        }
+    }
 }
 
 // =============================================================================================== backward: dQ, bias gradients
@@ -226,7 +240,9 @@ __global__ __launch_bounds__(NT, MINW) void bwd_dq_kernel(const bf16* __restrict
                                                           unsigned char* __restrict__ tables, bf16* __restrict__ dqkv,
                                                           bf16* __restrict__ dG, float* __restrict__ part, int L, int H, int Hp, int NRP,
                                                           float scale, int nblk, int xcd_map, int abl, int tile0, int pslot0,
-                                                          const bf16* __restrict__ oatt, size_t ldo) {
+                                                          const bf16* __restrict__ oatt, size_t ldo, const float* __restrict__ rowskip) {
+    // rowskip (may be NULL): the DropPath factors of this branch, f32 [samples].  A sample whose factor is 0 has dO = 0, hence dQ = dK = dV = 0
+    // and no rel-pos gradient: its workgroups read nothing and write zero dq rows, a zero rel-pos partial (or zero dG rows) and -Delta = 0
     // oatt (round 5, may be NULL): the forward's output O.  Given, this kernel computes Delta = rowsum(dO o O) of its own query rows in the
     // prologue (each lane holds half of its row's dO: 32 products + one half-wave exchange) and writes -Delta into the table tile for the
     // dKV launch behind it -- the prep launch that did this for every block (24 x 15 us per step on the main stream) is gone; the lse
@@ -247,8 +263,10 @@ __global__ __launch_bounds__(NT, MINW) void bwd_dq_kernel(const bf16* __restrict
         }
     };
     coarse(60);
-    int blk, bh;
-    wg_coords(nblk, xcd_map, blk, bh, (L / 32 - tile0) / NW);
+    int blk, bh, pslot = blockIdx.x;
+    bool drop = false;
+    if (rowskip != nullptr) drop = wg_coords_skip(nblk, xcd_map, blk, bh, rowskip, H, &pslot);          // kept samples first, balanced over the XCDs
+    else wg_coords(nblk, xcd_map, blk, bh, (L / 32 - tile0) / NW);
     const int b = bh / H, h = bh % H, D = H * ATT_HD;
     const bf16* base = qkv + (size_t)b * L * ldq + h * ATT_HD;
     const bf16* kbase = base + D;
@@ -257,6 +275,22 @@ __global__ __launch_bounds__(NT, MINW) void bwd_dq_kernel(const bf16* __restrict
     const bool valid = qt * 32 < L;
     const int q = qt * 32 + ql;
     const int qh = q / WP, qw = q % WP;
+    if (drop) {          // workgroup-uniform: the whole workgroup leaves before its first load
+        if (valid) {
+            zero_rows(dqkv + (size_t)(b * L + qt * 32) * ldq + h * ATT_HD, ldq, lane);
+            if (g == 0) *reinterpret_cast<float*>(tables + ((size_t)bh * (L / 32) + qt) * ttile_bytes(Hp) + 2048 + (Hp + 2) * 64 + ql * 4) = 0.f;
+            if constexpr (!FUSE) {
+                bf16* dgrow = dG + ((size_t)(b * L + qt * 32) * H + h) * NRP;
+                for (int c = lane; c < 32 * (NRP / 8); c += 64)
+                    *reinterpret_cast<uint4*>(dgrow + (size_t)(c / (NRP / 8)) * H * NRP + (c % (NRP / 8)) * 8) = zero4();
+            }
+        }
+        if constexpr (FUSE) {
+            float4* pw = reinterpret_cast<float4*>(part + (size_t)(pslot0 + pslot) * NRP * ATT_HD);
+            for (int c = tid; c < NRP * ATT_HD / 4; c += NT) pw[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return;
+    }
     unsigned char* thT = smem + 2 * STAGE_QK + wave * Hp * 64;
     unsigned char* eimg = smem + 2 * STAGE_QK + NW * Hp * 64;
     // Rcat^T [64 d][NRP] bf16, the A operand of the r-space step after the key loop, staged once per workgroup: fetching its fragments
@@ -550,7 +584,7 @@ __global__ __launch_bounds__(NT, MINW) void bwd_dq_kernel(const bf16* __restrict
         // 2 * NRP / 32 units (r-block, d-block) of one 32 x 32 accumulator over the workgroup's query blocks; wave w takes units w, w + 4, ...
         // Orientation: A = dG^T (rows r -> registers), B = Q^T (lanes = d), so that a store instruction writes 32 consecutive d of one row:
         // two 128-byte segments per instruction (the first form had lane = r: 64 rows, 16 bytes each, per instruction).
-        float* pw = part + (size_t)(pslot0 + blockIdx.x) * NRP * ATT_HD;
+        float* pw = part + (size_t)(pslot0 + pslot) * NRP * ATT_HD;
         for (int u = wave; u < 2 * (NRP / 32); u += NW) {
             const int rb = u >> 1, db = u & 1;
             f32x16 acc = zero16();
@@ -577,18 +611,30 @@ constexpr int DKV_TW = 2 * IMG, DKV_TH = DKV_TW + 2048, DKV_ND = DKV_TH + 512, D
 template <int MINW>
 __global__ __launch_bounds__(NT, MINW) void bwd_dkv_kernel(const bf16* __restrict__ qkv, size_t ldq, const bf16* __restrict__ dout,
                                                            size_t lddo, const unsigned char* __restrict__ tables, bf16* __restrict__ dqkv,
-                                                           int L, int H, int Hp, float scale, int nblk, int xcd_map, int abl, int tile0) {
+                                                           int L, int H, int Hp, float scale, int nblk, int xcd_map, int abl, int tile0,
+                                                           const float* __restrict__ rowskip) {
+    // rowskip (may be NULL): DropPath factors, f32 [samples]; a sample whose factor is 0 (dO = 0) gets zero dk / dv rows, nothing is read
     // abl (diagnostics, PA_ATTN3_DKV_ABL; results WRONG when set): 16 no query loop
     // tile0: first 32-key tile of every head this launch covers (0 in the product)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, ql = lane & 31;
     int blk, bh;
-    wg_coords(nblk, xcd_map, blk, bh, (L / 32 - tile0) / NW);
+    bool drop = false;
+    if (rowskip != nullptr) drop = wg_coords_skip(nblk, xcd_map, blk, bh, rowskip, H);          // kept samples first, balanced over the XCDs
+    else wg_coords(nblk, xcd_map, blk, bh, (L / 32 - tile0) / NW);
     const int b = bh / H, h = bh % H, D = H * ATT_HD;
     const bf16* qbase = qkv + (size_t)b * L * ldq + h * ATT_HD;
     const bf16* dobase = dout + (size_t)b * L * lddo + h * ATT_HD;
     const int kt = tile0 + blk * NW + wave;
     const bool valid = kt * 32 < L;
+    if (drop) {          // workgroup-uniform: the whole workgroup leaves before its first load
+        if (valid) {
+            bf16* orow = dqkv + (size_t)(b * L + kt * 32) * ldq + h * ATT_HD;
+            zero_rows(orow + D, ldq, lane);
+            zero_rows(orow + 2 * D, ldq, lane);
+        }
+        return;
+    }
     const int key = kt * 32 + ql;
     const int kh = key / WP, kw = key % WP;
     const int khlo = ((tile0 + blk * NW) * 32) / WP;  // first key row of the workgroup
@@ -843,18 +889,21 @@ static int a3_xcd_map_on() {
 }
 
 int attn3_fwd(const bf16* qkv, int64_t ldq, const bf16* rcat, bf16* out, int64_t ldo, float* lse, void* tables, int Bn, int L, int H,
-              int Hp, int Wp, float scale, hipStream_t st) {
+              int Hp, int Wp, float scale, hipStream_t st, const float* rowskip) {
     using namespace a3;
     const int NRP = pa_relpos_rows_padded(Hp, Wp);
+    if (Bn > 63) rowskip = nullptr;          // the kernels keep the dropped samples in a 64-bit mask
     // PA_ATTN3_FWD_STAGES: 1 (default) = single K/V stage, 4 workgroups per CU; 2 = double-buffered, one barrier per tile
     static const int stages = [] { const char* v = getenv("PA_ATTN3_FWD_STAGES"); return v ? atoi(v) : 1; }();
     const size_t smem = (size_t)(stages == 2 ? 2 : 1) * STAGE_QK + (size_t)NW * Hp * 64 + PH * EIMG;
     static bool done1 = false, done2 = false;
-    auto kern = stages == 2 ? fwd_kernel<2> : fwd_kernel<1>;
-    if (int e = set_smem(reinterpret_cast<const void*>(kern), stages == 2 ? done2 : done1)) return e;
+    // (the skipping build is an instantiation of its own: launches without a factor vector run the kernel they always ran)
+    static bool done1s = false, done2s = false;
+    auto kern = rowskip != nullptr ? (stages == 2 ? fwd_kernel<2, true> : fwd_kernel<1, true>) : (stages == 2 ? fwd_kernel<2> : fwd_kernel<1>);
+    if (int e = set_smem(reinterpret_cast<const void*>(kern), rowskip != nullptr ? (stages == 2 ? done2s : done1s) : (stages == 2 ? done2 : done1))) return e;
     const int nblk = (L / 32 + NW - 1) / NW;
     PA_LAUNCH(kern, dim3(nblk * Bn * H), dim3(NT), smem, st, qkv, (size_t)ldq, rcat, out, (size_t)ldo, lse,
-              reinterpret_cast<unsigned char*>(tables), L, H, Hp, NRP, scale, nblk, a3_xcd_map_on(), [] { const char* v = getenv("PA_ATTN3_FWD_ABL"); return v ? atoi(v) : 0; }());
+              reinterpret_cast<unsigned char*>(tables), L, H, Hp, NRP, scale, nblk, a3_xcd_map_on(), [] { const char* v = getenv("PA_ATTN3_FWD_ABL"); return v ? atoi(v) : 0; }(), rowskip);
     return (int)hipGetLastError();
 }
 
@@ -911,10 +960,11 @@ int attn3_relpos_reduce(const float* part, float* drcat, float* tmp, int Bn, int
 
 int attn3_bwd(const bf16* qkv, int64_t ldq, const bf16* rcatT, const bf16* dout, int64_t lddo, const float* lse, const float* delta,
               void* tables, bf16* dqkv, bf16* dG, float* part, int Bn, int L, int H, int Hp, int Wp, float scale, const bf16* out, int64_t ldo,
-              hipStream_t st) {
+              hipStream_t st, const float* rowskip) {
     using namespace a3;
     const int NRP = pa_relpos_rows_padded(Hp, Wp);
     if (part != nullptr && NRP > 16 * NSMAX) return (int)hipErrorInvalidValue;
+    if (Bn > 63) rowskip = nullptr;          // the kernels keep the dropped samples in a 64-bit mask
     if (part == nullptr && dG == nullptr) return (int)hipErrorInvalidValue;
     unsigned char* tb = reinterpret_cast<unsigned char*>(tables);
     int e;
@@ -946,7 +996,7 @@ int attn3_bwd(const bf16* qkv, int64_t ldq, const bf16* rcatT, const bf16* dout,
         if ((e = set_smem(reinterpret_cast<const void*>(kern), fuse ? donef : (g_attn_trace ? donet : (dq_w == 3 ? done3 : done2))))) return e;
         const char* ablv = getenv("PA_ATTN3_DQ_ABL");           // diagnostics, read per launch
         PA_LAUNCH(kern, dim3(nblk * Bn * H), dim3(NT), smem, st, qkv, (size_t)ldq, rcatT, dout, (size_t)lddo, lse, tb, dqkv, dG, part, L, H,
-                  Hp, NRP, scale, nblk, a3_xcd_map_on(), ablv ? atoi(ablv) : 0, tile0, 0, delta == nullptr ? out : nullptr, (size_t)ldo);
+                  Hp, NRP, scale, nblk, a3_xcd_map_on(), ablv ? atoi(ablv) : 0, tile0, 0, delta == nullptr ? out : nullptr, (size_t)ldo, rowskip);
         if ((e = (int)hipGetLastError())) return e;
     }
     const int tile0_kv = 0, nblk_kv = a3_blocks(L);
@@ -959,7 +1009,7 @@ int attn3_bwd(const bf16* qkv, int64_t ldq, const bf16* rcatT, const bf16* dout,
         static bool done2 = false, done3 = false;
         if ((e = set_smem(reinterpret_cast<const void*>(kern), dkv_w == 3 ? done3 : done2))) return e;
         PA_LAUNCH(kern, dim3(nblk_kv * Bn * H), dim3(NT), smem, st, qkv, (size_t)ldq, dout, (size_t)lddo, tb, dqkv, L, H, Hp, scale, nblk_kv,
-                  a3_xcd_map_on(), [] { const char* v = getenv("PA_ATTN3_DKV_ABL"); return v ? atoi(v) : 0; }(), tile0_kv);
+                  a3_xcd_map_on(), [] { const char* v = getenv("PA_ATTN3_DKV_ABL"); return v ? atoi(v) : 0; }(), tile0_kv, rowskip);
         if ((e = (int)hipGetLastError())) return e;
     }
     return 0;

@@ -576,16 +576,18 @@ extern "C" int64_t pa_attn_bwd_relpos_partials_bytes(int dtype, int batch, int L
     if (dtype != PA_BF16 || head_dim != ATT_HD || L != Hp * Wp) return 0;
     return attn3_relpos_partials_bytes(batch, L, heads, Hp, Wp);
 }
-extern "C" int pa_attn_bwd(int dtype, const void* qkv, int64_t ldq, const void* rcat, const void* rcatT, const void* dout, int64_t lddo,
-                           const float* lse, const float* delta, void* dqkv, void* dG, void* relpos_part, void* aux, void* tables,
-                           const void* out, int64_t ldo, int batch, int L, int heads, int Hp, int Wp, int head_dim, float scale, hipStream_t st) {
+// rowskip: DropPath factors f32 [batch] or NULL; only the generation-3 kernels use it (every other kernel computes the dropped samples too)
+extern "C" int pa_attn_bwd_skip(int dtype, const void* qkv, int64_t ldq, const void* rcat, const void* rcatT, const void* dout, int64_t lddo,
+                                const float* lse, const float* delta, void* dqkv, void* dG, void* relpos_part, void* aux, void* tables,
+                                const void* out, int64_t ldo, int batch, int L, int heads, int Hp, int Wp, int head_dim, float scale,
+                                const float* rowskip, hipStream_t st) {
     if (L != Hp * Wp || L % 32 || Hp % 4 || Wp % 4 || (head_dim != 64 && head_dim != 80)) return (int)hipErrorInvalidValue;
     if (dtype == PA_BF16 && head_dim == ATT_HD && tables != nullptr && attn3_ok(L, Hp, Wp)) {
         if (relpos_part != nullptr && attn3_relpos_partials_bytes(batch, L, heads, Hp, Wp) == 0) return (int)hipErrorInvalidValue;
         ++g_attn_counts[5];
         if (out != nullptr && ldo % 8) return (int)hipErrorInvalidValue;
         return attn3_bwd((const bf16*)qkv, ldq, (const bf16*)rcatT, (const bf16*)dout, lddo, lse, delta, tables, (bf16*)dqkv, (bf16*)dG,
-                         (float*)relpos_part, batch, L, heads, Hp, Wp, scale, (const bf16*)out, ldo, st);
+                         (float*)relpos_part, batch, L, heads, Hp, Wp, scale, (const bf16*)out, ldo, st, drop_skip_on() ? rowskip : nullptr);
     }
     if (relpos_part != nullptr || dG == nullptr || delta == nullptr) return (int)hipErrorInvalidValue;      // only the generation-3 kernels fuse the rel-pos gradient / read Delta from the tables
     if (dtype == PA_BF16 && attn2_ok(L, Hp, Wp, head_dim)) {
@@ -599,6 +601,12 @@ extern "C" int pa_attn_bwd(int dtype, const void* qkv, int64_t ldq, const void* 
     if (dtype == PA_BF16) return head_dim == 80 ? PA_ATTN_BWD(bf16, 80) : PA_ATTN_BWD(bf16, 64);
     return head_dim == 80 ? PA_ATTN_BWD(float, 80) : PA_ATTN_BWD(float, 64);
 #undef PA_ATTN_BWD
+}
+extern "C" int pa_attn_bwd(int dtype, const void* qkv, int64_t ldq, const void* rcat, const void* rcatT, const void* dout, int64_t lddo,
+                           const float* lse, const float* delta, void* dqkv, void* dG, void* relpos_part, void* aux, void* tables,
+                           const void* out, int64_t ldo, int batch, int L, int heads, int Hp, int Wp, int head_dim, float scale, hipStream_t st) {
+    return pa_attn_bwd_skip(dtype, qkv, ldq, rcat, rcatT, dout, lddo, lse, delta, dqkv, dG, relpos_part, aux, tables, out, ldo, batch, L, heads, Hp, Wp,
+                            head_dim, scale, nullptr, st);
 }
 
 // d[rel_pos_h ; rel_pos_w ; pad][NRP, hd] (fp32) = sum over heads, samples, queries of dG[., r] * q[., d]

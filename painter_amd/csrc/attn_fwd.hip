@@ -264,12 +264,14 @@ static int attn_fwd_t(const void* qkv, int64_t ldq, const void* rcat, void* out,
 extern "C" int64_t pa_attn_tables_bytes(int dtype, int batch, int L, int heads, int Hp, int Wp, int head_dim) {
     return dtype == PA_BF16 && head_dim == ATT_HD ? attn3_table_bytes(batch, L, heads, Hp, Wp) : 0;
 }
-extern "C" int pa_attn_fwd(int dtype, const void* qkv, int64_t ldq, const void* rcat, void* out, int64_t ldo, float* lse, void* tables,
-                           int batch, int L, int heads, int Hp, int Wp, int head_dim, float scale, hipStream_t st) {
+// rowskip: DropPath factors f32 [batch] or NULL; only the generation-3 kernels use it (every other kernel computes the dropped samples too)
+extern "C" int pa_attn_fwd_skip(int dtype, const void* qkv, int64_t ldq, const void* rcat, void* out, int64_t ldo, float* lse, void* tables,
+                                int batch, int L, int heads, int Hp, int Wp, int head_dim, float scale, const float* rowskip, hipStream_t st) {
     if (L != Hp * Wp || L % 32 || Hp % 4 || Wp % 4 || !head_dim_ok(head_dim)) return (int)hipErrorInvalidValue;
     if (dtype == PA_BF16 && head_dim == ATT_HD && attn3_ok(L, Hp, Wp)) {
         ++g_attn_counts[2];
-        return attn3_fwd((const bf16*)qkv, ldq, (const bf16*)rcat, (bf16*)out, ldo, lse, tables, batch, L, heads, Hp, Wp, scale, st);
+        return attn3_fwd((const bf16*)qkv, ldq, (const bf16*)rcat, (bf16*)out, ldo, lse, tables, batch, L, heads, Hp, Wp, scale, st,
+                         drop_skip_on() ? rowskip : nullptr);
     }
     if (dtype == PA_BF16 && attn2_ok(L, Hp, Wp, head_dim)) {
         ++g_attn_counts[1];
@@ -278,6 +280,10 @@ extern "C" int pa_attn_fwd(int dtype, const void* qkv, int64_t ldq, const void* 
     ++g_attn_counts[0];
     if (dtype == PA_BF16) return attn_fwd_t<bf16>(qkv, ldq, rcat, out, ldo, lse, batch, L, heads, Hp, Wp, head_dim, scale, st);
     return attn_fwd_t<float>(qkv, ldq, rcat, out, ldo, lse, batch, L, heads, Hp, Wp, head_dim, scale, st);
+}
+extern "C" int pa_attn_fwd(int dtype, const void* qkv, int64_t ldq, const void* rcat, void* out, int64_t ldo, float* lse, void* tables,
+                           int batch, int L, int heads, int Hp, int Wp, int head_dim, float scale, hipStream_t st) {
+    return pa_attn_fwd_skip(dtype, qkv, ldq, rcat, out, ldo, lse, tables, batch, L, heads, Hp, Wp, head_dim, scale, nullptr, st);
 }
 
 extern "C" int pa_attn_launch_counts(long long* out6) {

@@ -55,6 +55,44 @@ DEVI void wg_coords(int nblk, int xcd_map, int& blk, int& bh, int nfull = 0) {
     blk = v - bh * nblk;
 }
 
+// The same grid under DropPath skipping (rowskip: f32 [samples], factor 0 = dropped; generation 3).  A sample is H * nblk consecutive
+// (head, row block) pairs -- at B = 8 exactly the run ONE XCD gets above, so leaving the order alone a dropped sample only idles its XCD
+// while the other seven work as long as ever.  Here the KEPT samples are numbered densely and the XCD runs are laid over their pairs alone
+// (the first kept * H * nblk workgroups); the workgroups behind them belong to the dropped samples and only write zeros.
+// -> true for a workgroup of a dropped sample.  slot: the workgroup index this (head, row block) pair has in the plain order above -- the
+// dQ kernel's rel-pos partials stay where the fixed-order reduction finds them, whoever computes them.  (xcd_map bit 1 is ignored.)
+DEVI bool wg_coords_skip(int nblk, int xcd_map, int& blk, int& bh, const float* __restrict__ rowskip, int H, int* slot = nullptr) {
+    const int n = blockIdx.x, total = gridDim.x, per = nblk * H, ns = total / per;          // ns <= 63 (the launchers)
+    // bit s = sample s is dropped: one vector load + ballot per wave (a scalar walk over the factors cost ~3 us per workgroup)
+    const int lane = threadIdx.x & 63;
+    const float fv = lane < ns ? rowskip[lane] : 1.f;
+    const unsigned long long dmask = __ballot(fv == 0.f);
+    const int nk = (ns - __builtin_popcountll(dmask)) * per;
+    const bool drop = n >= nk;
+    const int v = drop ? n - nk : ((xcd_map & 1) ? xcd_run(n, nk) : n);
+    const int rank = v / per, rem = v - rank * per;          // rank among the kept (dropped) samples
+    int b = rank;
+    if (dmask != 0) {                                        // the rank-th clear (set) bit
+        unsigned long long m = drop ? dmask : ~dmask;
+        for (int c = 0; c < rank; ++c) m &= m - 1;
+        b = __builtin_ctzll(m);
+    }
+    bh = b * H + rem / nblk;
+    blk = rem % nblk;
+    if (slot != nullptr) {
+        const int u = bh * nblk + blk;                       // inverse of xcd_run(., total)
+        if (xcd_map & 1) {
+            const int xq = total >> 3, xr = total & 7, lim = xr * (xq + 1);
+            const int c = u < lim ? u / (xq + 1) : xr + (u - lim) / xq;
+            const int o = u < lim ? u - c * (xq + 1) : (u - lim) - (c - xr) * xq;
+            *slot = o * 8 + c;
+        } else {
+            *slot = u;
+        }
+    }
+    return drop;
+}
+
 // ---- tile image: 32 rows x 128 B, 16-B chunk index XORed with a bijection of row bits 1..3
 DEVI int vsw(int row) { return (((row >> 1) & 1) << 2) | (((row >> 2) & 1) << 1) | ((row >> 3) & 1); }
 
@@ -142,6 +180,15 @@ DEVI void write_rows(const unsigned char* stg, bf16* dst, size_t ld, int lane) {
     for (int i = 0; i < 4; ++i) {
         const int c = lane + 64 * i, row = c >> 3, ch = c & 7;
         *reinterpret_cast<uint4*>(dst + (size_t)row * ld + ch * 8) = *reinterpret_cast<const uint4*>(stg + row * 128 + ch * 16);
+    }
+}
+
+// zeros into a wave's 32 output rows of 128 B (a DropPath-dropped sample: nothing was computed, the rows stay defined)
+DEVI void zero_rows(bf16* dst, size_t ld, int lane) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i, row = c >> 3, ch = c & 7;
+        *reinterpret_cast<uint4*>(dst + (size_t)row * ld + ch * 8) = make_uint4(0, 0, 0, 0);
     }
 }
 

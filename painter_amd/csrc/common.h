@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -132,6 +133,14 @@ inline int g_conv_wgrad_groups = 0;
 // pa_debug_set(11 .. 15, v): round-6 experiment knobs, read where they are named: [0] = 11 gemm256 tile patch per XCD (0 = default,
 // TR * 16 + TC otherwise), [1] = 12 mixed 224-row + 128-row tiles for the multi-round GEMMs (0 = default on, 1 = off), [2] = 13, [3] = 14, [4] = 15 free
 inline int g_misc_knob[5] = {0, 0, 0, 0, 0};
+
+// pa_debug_set(16, v) / PAINTER_AMD_DROP_SKIP: DropPath skipping (the *_skip entry points: attention workgroups and GEMM row tiles of samples
+// whose factor is 0 do no work).  0 = default (on unless PAINTER_AMD_DROP_SKIP=0), 1 = off (the factor vector is ignored: what ran before), 2 = on
+inline int g_drop_skip = 0;
+static inline bool drop_skip_on() {
+    static const int env = [] { const char* v = getenv("PAINTER_AMD_DROP_SKIP"); return v ? atoi(v) : 1; }();
+    return g_drop_skip == 1 ? false : (g_drop_skip == 2 ? true : env != 0);
+}
 
 // host-side launch counters of the attention entry points, by kernel family: [0..2] pa_attn_fwd on the generic (attn_fwd.hip) /
 // generation-2 (attn2.hip) / generation-3 (attn3.hip) kernels, [3..5] pa_attn_bwd likewise (pa_attn_launch_counts; the model-level tests

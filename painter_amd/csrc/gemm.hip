@@ -398,9 +398,19 @@ extern "C" int pa_colsum(int dtype, const void* x, int64_t ld, int M, int N, flo
 template <typename T>
 static int linear_fwd_t(int epi, const T* x, int64_t ldx, const T* w, const float* bias, void* out, void* out2,
                         int64_t ldo, const float* resid, const float* rowscale, int rps, int M, int N, int K,
-                        hipStream_t st) {
+                        hipStream_t st, const float* rowskip = nullptr, int skip_rps = 1) {
     if constexpr (std::is_same<T, bf16>::value) {
         if (g256::ok(M, N, K, false, false, ldx, K)) {
+            if (rowskip != nullptr) {          // DropPath: row tiles that lie wholly in dropped samples run only their epilogue (gemm256.h, SKIP)
+                switch (epi) {
+                case PA_EPI_BIAS:
+                    return g256::launch_skip<false>(x, ldx, w, K, Epi4Bias<bf16>{(bf16*)out, (size_t)ldo, bias, M, N}, M, N, K, st, rowskip, skip_rps);
+                case PA_EPI_BIAS_GELU:
+                    return g256::launch_skip<false>(x, ldx, w, K, Epi4BiasGelu{(unsigned char*)out2, (bf16*)out, (size_t)ldo, bias, M, N}, M, N, K, st, rowskip, skip_rps);
+                case PA_EPI_BIAS_RESID:
+                    return g256::launch_skip<false>(x, ldx, w, K, Epi4BiasResid{(float*)out, resid, (size_t)ldo, bias, rowscale, rps, M, N}, M, N, K, st, rowskip, skip_rps);
+                }
+            }
             switch (epi) {
             case PA_EPI_BIAS:
                 return g256::launch<false, false>(x, ldx, w, K, Epi4Bias<bf16>{(bf16*)out, (size_t)ldo, bias, M, N}, M, N, K, 1, st);
@@ -428,13 +438,21 @@ static int linear_fwd_t(int epi, const T* x, int64_t ldx, const T* w, const floa
     return (int)hipErrorInvalidValue;
 }
 
+extern "C" int pa_linear_fwd_skip(int dtype, int epilogue, const void* x, int64_t ldx, const void* w, const float* bias,
+                                  void* out, void* out2, int64_t ldo, const float* resid, const float* rowscale,
+                                  int rows_per_sample, int M, int N, int K, const float* rowskip, int skip_rows_per_sample, hipStream_t st) {
+    if (K % (dtype == PA_BF16 ? 8 : 4)) return (int)hipErrorInvalidValue;
+    if (rowskip != nullptr && skip_rows_per_sample < 1) return (int)hipErrorInvalidValue;
+    if (!drop_skip_on()) rowskip = nullptr;
+    if (dtype == PA_BF16)
+        return linear_fwd_t<bf16>(epilogue, (const bf16*)x, ldx, (const bf16*)w, bias, out, out2, ldo, resid, rowscale, rows_per_sample, M, N, K, st,
+                                  rowskip, skip_rows_per_sample);
+    return linear_fwd_t<float>(epilogue, (const float*)x, ldx, (const float*)w, bias, out, out2, ldo, resid, rowscale, rows_per_sample, M, N, K, st);
+}
 extern "C" int pa_linear_fwd(int dtype, int epilogue, const void* x, int64_t ldx, const void* w, const float* bias,
                              void* out, void* out2, int64_t ldo, const float* resid, const float* rowscale,
                              int rows_per_sample, int M, int N, int K, hipStream_t st) {
-    if (K % (dtype == PA_BF16 ? 8 : 4)) return (int)hipErrorInvalidValue;
-    if (dtype == PA_BF16)
-        return linear_fwd_t<bf16>(epilogue, (const bf16*)x, ldx, (const bf16*)w, bias, out, out2, ldo, resid, rowscale, rows_per_sample, M, N, K, st);
-    return linear_fwd_t<float>(epilogue, (const float*)x, ldx, (const float*)w, bias, out, out2, ldo, resid, rowscale, rows_per_sample, M, N, K, st);
+    return pa_linear_fwd_skip(dtype, epilogue, x, ldx, w, bias, out, out2, ldo, resid, rowscale, rows_per_sample, M, N, K, nullptr, 1, st);
 }
 
 template <typename T>
@@ -467,18 +485,20 @@ extern "C" int64_t pa_linear_dgrad_workspace_bytes(int M, int K) {
 }
 template <typename T>
 static int linear_dgrad_t(const T* dy, int64_t lddy, const T* w, const typename GeluAux<T>::type* pre /* = gelu_aux: EpiBiasGelu */, T* dx, int64_t lddx, float* dx_colsum, float* ws, int M,
-                          int N, int K, hipStream_t st) {
+                          int N, int K, hipStream_t st, const float* rowskip = nullptr, int skip_rps = 1) {
     if constexpr (std::is_same<T, bf16>::value) {
         if (g256::ok(M, K, N, false, true, lddy, K)) {
+            // rowskip (DropPath): row tiles that lie wholly in dropped samples -- whose dY rows are zero -- run only their epilogue (gemm256.h, SKIP)
             if (pre && dx_colsum) {
                 Epi4DGeluCS ep;
                 ep.out = dx; ep.aux = pre; ep.ld = (size_t)lddx; ep.M = M; ep.N = K; ep.part = ws;
-                int e = g256::launch<false, true>(dy, lddy, w, K, ep, M, K, N, 1, st);
+                int e = rowskip ? g256::launch_skip<true>(dy, lddy, w, K, ep, M, K, N, st, rowskip, skip_rps) : g256::launch<false, true>(dy, lddy, w, K, ep, M, K, N, 1, st);
                 if (e) return e;
                 return pa_slab_reduce(ws, dx_colsum, K, 2 * g256::row_tiles_used(M, K, 1), K, 0, st);
             }
             if (pre) return g256::launch<false, true>(dy, lddy, w, K, Epi4DGelu{dx, pre, (size_t)lddx, M, K}, M, K, N, 1, st);
-            int e = g256::launch<false, true>(dy, lddy, w, K, Epi4Bias<bf16>{dx, (size_t)lddx, nullptr, M, K}, M, K, N, 1, st);
+            int e = rowskip ? g256::launch_skip<true>(dy, lddy, w, K, Epi4Bias<bf16>{dx, (size_t)lddx, nullptr, M, K}, M, K, N, st, rowskip, skip_rps)
+                            : g256::launch<false, true>(dy, lddy, w, K, Epi4Bias<bf16>{dx, (size_t)lddx, nullptr, M, K}, M, K, N, 1, st);
             if (e || dx_colsum == nullptr) return e;
             return pa_colsum(PA_BF16, dx, lddx, M, K, dx_colsum, ws, st);      // no GELU side input: a pass over the stored dX (the epilogue sums only exist beside it)
         }
@@ -491,12 +511,21 @@ static int linear_dgrad_t(const T* dy, int64_t lddy, const T* w, const typename 
     if (e || dx_colsum == nullptr) return e;
     return pa_colsum(std::is_same<T, bf16>::value ? PA_BF16 : PA_F32, dx, lddx, M, K, dx_colsum, ws, st);
 }
-extern "C" int pa_linear_dgrad(int dtype, const void* dy, int64_t lddy, const void* w, const void* gelu_aux,
-                               void* dx, int64_t lddx, float* dx_colsum, void* workspace, int M, int N, int K, hipStream_t st) {
+extern "C" int pa_linear_dgrad_skip(int dtype, const void* dy, int64_t lddy, const void* w, const void* gelu_aux,
+                                    void* dx, int64_t lddx, float* dx_colsum, void* workspace, int M, int N, int K,
+                                    const float* rowskip, int skip_rows_per_sample, hipStream_t st) {
     if (N % 8 || K % 4) return (int)hipErrorInvalidValue;
     if (dx_colsum != nullptr && (workspace == nullptr || K % 8 || lddx % 8)) return (int)hipErrorInvalidValue;
-    if (dtype == PA_BF16) return linear_dgrad_t<bf16>((const bf16*)dy, lddy, (const bf16*)w, (const unsigned char*)gelu_aux, (bf16*)dx, lddx, dx_colsum, (float*)workspace, M, N, K, st);
+    if (rowskip != nullptr && skip_rows_per_sample < 1) return (int)hipErrorInvalidValue;
+    if (!drop_skip_on()) rowskip = nullptr;
+    if (dtype == PA_BF16)
+        return linear_dgrad_t<bf16>((const bf16*)dy, lddy, (const bf16*)w, (const unsigned char*)gelu_aux, (bf16*)dx, lddx, dx_colsum, (float*)workspace, M, N, K, st,
+                                    rowskip, skip_rows_per_sample);
     return linear_dgrad_t<float>((const float*)dy, lddy, (const float*)w, (const float*)gelu_aux, (float*)dx, lddx, dx_colsum, (float*)workspace, M, N, K, st);
+}
+extern "C" int pa_linear_dgrad(int dtype, const void* dy, int64_t lddy, const void* w, const void* gelu_aux,
+                               void* dx, int64_t lddx, float* dx_colsum, void* workspace, int M, int N, int K, hipStream_t st) {
+    return pa_linear_dgrad_skip(dtype, dy, lddy, w, gelu_aux, dx, lddx, dx_colsum, workspace, M, N, K, nullptr, 1, st);
 }
 
 // dW[N,K] = dY[M,N]^T . X[M,K]    (contraction over M; both operands contraction-major), split-K + reduce
@@ -567,8 +596,9 @@ extern "C" int pa_linear_wgrad(int dtype, const void* dy, int64_t lddy, const vo
 extern "C" int pa_abi_version(void) { return PA_ABI_VERSION; }
 // knobs: 0-4 gemm256 (g256::g_dbg), 5 the G256_ILV_AB schedule override (experiment builds), 6 rel-pos splits, 7 fused rel-pos gradient,
 // 8 light attention workgroups last, 9 conv3x3 weight-gradient groups, 10 LayerNorm-backward variant (round 5 shared index 5 with the ILV
-// override: tools that swept one silently switched the other)
+// override: tools that swept one silently switched the other), 16 DropPath skipping (common.h, g_drop_skip)
 extern "C" int pa_debug_get(int which) {
+    if (which == 16) return g_drop_skip;
     if (which < 0 || which > 15) return -1;
     if (which == 9) return g_conv_wgrad_groups;
     if (which == 10) return g_ln_bwd_variant;
@@ -579,6 +609,7 @@ extern "C" int pa_debug_get(int which) {
     return g256::g_dbg[which];
 }
 extern "C" int pa_debug_set(int which, int value) {
+    if (which == 16) { g_drop_skip = value; return 0; }
     if (which < 0 || which > 15) return (int)hipErrorInvalidValue;
     if (which < 8) g256::g_dbg[which] = value;
     if (which == 9) g_conv_wgrad_groups = value;

@@ -158,11 +158,23 @@ constexpr int BM_SHORT = 224;
 // (profiles/r06_ab_mixed_tiles_first_attempt.log).  No branch may sit inside this kernel's K loop.
 // Tiles [0, nfull * tiles_n) are full (BMR rows), the rest are half tiles starting at row nfull * BMR; only for a K-major A operand, no K split.
 constexpr int BM_HALF = 128;
-template <bool AMM, bool BMM, int ILV, class Epi, bool SHORT = false, bool MIXED = false>
+// SKIP (DropPath): rowskip = the branch's per-sample factors (f32, one per `rps` contiguous rows of A / of the output).  A row tile -- full,
+// 224-row or half -- whose rows ALL belong to samples with factor 0 stages nothing and runs no K loop: its epilogue runs on the zero
+// accumulator, so every output stays defined (bias, gelu(bias), the residual, zero rows / a zero column-sum partial).  The decision is
+// workgroup-uniform and sits outside the K loop; a tile that touches a kept sample runs as ever.  SKIP = false (every launch without a
+// factor vector) compiles to the kernel it was before: `skipped` is a constant there.  Only for a K-major A operand.
+// Which workgroup takes which tile changes with it: a sample of the B = 8 step is an eighth of the rows, i.e. exactly the contiguous run of
+// tiles ONE XCD gets from the order below -- with the plain order a dropped sample just idles that XCD while the other seven work as long as
+// ever (measured: no gain at all).  So the KEPT row panels of a region (full tiles, half tiles) are numbered densely and the XCD runs and
+// patches are laid over them alone (the first kept * tiles_n workgroups); the workgroups behind them take the skipped tiles, whose
+// epilogue-only work is spread by the dispatcher.  The ranges of skipped panels come from one walk over the factor vector (scalar loads).
+template <bool AMM, bool BMM, int ILV, class Epi, bool SHORT = false, bool MIXED = false, bool SKIP = false>
 __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag, uint32_t lda, const bf16* __restrict__ Bg,
                                                       uint32_t ldb, Epi epi, int M, int N, int ktiles, int ktiles_per_split,
-                                                      int tiles_n, int stagger, int order, int nfull, int patch) {
+                                                      int tiles_n, int stagger, int order, int nfull, int patch,
+                                                      const float* __restrict__ rowskip, int rps) {
     static_assert(!(SHORT && AMM), "the 224-row tile is built for a K-major A operand");
+    static_assert(!(SKIP && AMM), "row tiles are skipped only for a K-major A operand");
     static_assert(!(MIXED && (AMM || SHORT)), "half tiles are built for a K-major A operand and 256-row full tiles");
     constexpr int BMR = SHORT ? BM_SHORT : BM;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -181,8 +193,41 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
     // tiles sharing an A row panel hit the same L2.
     // (MIXED: the full tiles and the half tiles are two regions of the grid, each ordered on its own)
     const bool htile = MIXED && (int)blockIdx.x >= nfull * tiles_n;
-    const int nwg = MIXED ? (htile ? (int)gridDim.x - nfull * tiles_n : nfull * tiles_n) : (int)gridDim.x;
+    int nwg = MIXED ? (htile ? (int)gridDim.x - nfull * tiles_n : nfull * tiles_n) : (int)gridDim.x;
     const int bid = htile ? (int)blockIdx.x - nfull * tiles_n : (int)blockIdx.x;
+    // SKIP: f(a, b) for every maximal range [a, b) of this region's row panels that lie wholly in dropped samples, ascending.  `dmask`: bit s =
+    // sample s is dropped (one vector load + ballot per wave: a scalar walk over the factors cost ~5 us per workgroup); with nobody dropped --
+    // two launches of three -- the walk has no trips and the tile order is the usual one
+    unsigned long long dmask = 0;
+    auto skipped_ranges = [&](auto&& f) {
+        const int r0 = htile ? nfull * BMR : 0, r1 = (MIXED && !htile) ? nfull * BMR : M;
+        const int np = htile ? (r1 - r0 + BM_HALF - 1) / BM_HALF : (r1 - r0 + BMR - 1) / BMR;
+        unsigned long long m = dmask;
+        while (m != 0) {
+            const int s0 = __builtin_ctzll(m), s1 = s0 + __builtin_ctzll(~(m >> s0));      // samples [s0, s1) are dropped (bit 63 is never set)
+            m &= ~0ull << s1;
+            const int ra = max(s0 * rps, r0), rb = min(min(s1 * rps, M), r1);                // the run's rows inside the region
+            if (rb <= ra) continue;
+            const int ua = ra - r0, ub = rb - r0;
+            const int a = htile ? (ua + BM_HALF - 1) / BM_HALF : (ua + BMR - 1) / BMR;
+            const int b = rb >= r1 ? np : (htile ? ub / BM_HALF : ub / BMR);                 // (the region's last panel may be short)
+            if (b > a) f(a, b);
+        }
+    };
+    bool skipped = false;
+    int kept_panels = 0;
+    if constexpr (SKIP) {
+        {
+            const int ns = (M + rps - 1) / rps;            // <= 63 (launch_skip)
+            const float fv = lane < ns ? rowskip[lane] : 1.f;
+            dmask = __ballot(fv == 0.f);
+        }
+        const int r0 = htile ? nfull * BMR : 0, r1 = (MIXED && !htile) ? nfull * BMR : M;
+        kept_panels = htile ? (r1 - r0 + BM_HALF - 1) / BM_HALF : (r1 - r0 + BMR - 1) / BMR;
+        skipped_ranges([&](int a, int b) { kept_panels -= b - a; });
+        nwg = kept_panels * tiles_n;           // the XCD runs and patches below cover the kept tiles alone
+        skipped = bid >= nwg;
+    }
     const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7;
     int tile = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
     int split = blockIdx.y;
@@ -202,10 +247,11 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
     // then row-major inside a block), so that the ~32 tiles an XCD has in flight form a TR x TC patch: per contraction step they pull
     // TR + TC operand panels through that XCD's L2 instead of 2 + tiles_n (fc1 forward, 16 column panels: FETCH_SIZE 251 -> ~165 MB
     // per launch; the weight matrix alone is twice the L2).  g_dbg[2] = 1 restores the plain row-major order (A/B).
-    int tm, tn;
-    if (order != 1) {
+    int tm = 0, tn = 0;
+    if (skipped) {
+    } else if (order != 1) {
         const int TR = patch > 0 ? patch / 100 : 4, TC = patch > 0 ? patch % 100 : 8;      // patch (PA_G256_PATCH / pa_debug_set(11, TR * 100 + TC)): experiments
-        const int tiles_m = MIXED ? (htile ? (M - nfull * BMR + BM_HALF - 1) / BM_HALF : nfull) : (M + BMR - 1) / BMR;
+        const int tiles_m = SKIP ? kept_panels : MIXED ? (htile ? (M - nfull * BMR + BM_HALF - 1) / BM_HALF : nfull) : (M + BMR - 1) / BMR;
         const int per_group = TR * tiles_n;
         const int gm = tile / per_group, rem = tile - gm * per_group;
         const int rg = min(TR, tiles_m - gm * TR);                   // row panels in this (possibly last, shorter) group
@@ -223,11 +269,24 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
         tm = tile / tiles_n;
         tn = tile - tm * tiles_n;
     }
+    if constexpr (SKIP) {
+        if (skipped) {                         // the d-th skipped tile of the region
+            const int d = bid - nwg;
+            int r = d / tiles_n;
+            tn = d - r * tiles_n;
+            bool found = false;
+            skipped_ranges([&](int a, int b) {
+                if (!found && r < b - a) { tm = a + r; found = true; }
+                if (!found) r -= b - a;
+            });
+        } else {                               // tm counts kept panels: step over the skipped ranges in front of it
+            skipped_ranges([&](int a, int b) { if (tm >= a) tm += b - a; });
+        }
+    }
     const int i0 = htile ? nfull * BMR + tm * BM_HALF : tm * BMR, j0 = tn * BN;
     const bool blk3 = !(SHORT && wr == 1);          // does this wave own the fourth 32-row block of its 128 rows?  (wave-uniform)
     const int kt0 = split * ktiles_per_split;
     const int nt = min(ktiles - kt0, ktiles_per_split);
-
     // ---- DMA sources: 8 per lane (4 units x 2), as byte offsets from a wave-uniform, per-tile advancing base
     uint32_t oa[2][2], ob[2][2];
 #pragma unroll
@@ -423,16 +482,18 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
     if constexpr (MIXED) {
         if (htile) {                       // workgroup-uniform, outside every loop
             ran_half = true;
-            piece_a(0, 0, 0, 0); piece_a(1, 0, 0, 0); stage_b(0, 0, 0); stage_b(1, 0, 0);      // tile 0 into stage 0
-            wait_vm<0>();
-            bar();
-            for (int T = 0; T < nt; T += 2) {
-                half_body(I0{}, T);
-                half_body(I1{}, T + 1);
+            if (!skipped) {
+                piece_a(0, 0, 0, 0); piece_a(1, 0, 0, 0); stage_b(0, 0, 0); stage_b(1, 0, 0);      // tile 0 into stage 0
+                wait_vm<0>();
+                bar();
+                for (int T = 0; T < nt; T += 2) {
+                    half_body(I0{}, T);
+                    half_body(I1{}, T + 1);
+                }
             }
         }
     }
-    if (!ran_half) {
+    if (!ran_half && !skipped) {
         // ---- prologue: tile 0 entirely, plus a0/b0 of tile 1   (nt is even and >= 2: see launch())
         stage_a(0, 0, 0);
         stage_b(0, 0, 0);
@@ -449,7 +510,7 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
             tile_body(I1{}, T + 1);
         }
     }
-    if (wr == 0 && !ran_half) bar();       // (the full loop's half-phase offset between the wave rows; the half-tile loop runs in step)
+    if (wr == 0 && !ran_half && !skipped) bar();       // (the full loop's half-phase offset between the wave rows; the half-tile loop runs in step)
     wait_vm<0>();          // the clamped tail DMAs must have landed before this workgroup's LDS is handed on
 
     // ---- epilogue.  A lane owns one output row of each 32x32 block; storing from there would touch 32 cache lines per
@@ -525,8 +586,9 @@ static inline int per_split(int ktiles, int nsplit) {
     int per = (ktiles + nsplit - 1) / nsplit;
     return per + (per & 1);
 }
-template <bool AMM, bool BMM, int ILV, bool SHORT, class Epi, bool MIXED = false>
-static int launch_ilv(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi epi, int M, int N, int K, int nsplit, hipStream_t st, int nfull = 0);
+template <bool AMM, bool BMM, int ILV, bool SHORT, class Epi, bool MIXED = false, bool SKIP = false>
+static int launch_ilv(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi epi, int M, int N, int K, int nsplit, hipStream_t st, int nfull = 0,
+                      const float* rowskip = nullptr, int rps = 1);
 #ifndef G256_ILV_DEFAULT
 #define G256_ILV_DEFAULT 2     // round 3 (tools/gemm_ilv_ab.py, MI355X): 2 is 4-15 % faster than 0 on the forward GEMMs, 4-6 % on the data gradients,
 #endif                         // 2 % on the weight gradients, bit-identical results; 1 = 0.  In the training step the gain shrinks to ~1 % (DVFS)
@@ -588,9 +650,20 @@ static int launch(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi epi,
     return launch_ilv<AMM, BMM, G256_ILV_DEFAULT, false>(A, lda, B, ldb, epi, M, N, K, nsplit, st);
 #endif
 }
-template <bool AMM, bool BMM, int ILV, bool SHORT, class Epi, bool MIXED>
-static int launch_ilv(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi epi, int M, int N, int K, int nsplit, hipStream_t st, int nfull) {
-    auto kern = gemm256_kernel<AMM, BMM, ILV, Epi, SHORT, MIXED>;
+// Un-split launch with a K-major A operand and a DropPath factor vector (rowskip != NULL, rps >= 1 rows per sample): the same tile plan as
+// launch(), on the SKIP instantiations
+template <bool BMM, class Epi>
+static int launch_skip(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi epi, int M, int N, int K, hipStream_t st, const float* rowskip, int rps) {
+    if ((M + rps - 1) / rps > 63) return launch<false, BMM>(A, lda, B, ldb, epi, M, N, K, 1, st);      // the kernel keeps the dropped samples in a 64-bit mask
+    const TilePlan tp = tile_plan(M, N, 1, false);
+    if (tp.mixed) return launch_ilv<false, BMM, G256_ILV_DEFAULT, false, Epi, true, true>(A, lda, B, ldb, epi, M, N, K, 1, st, tp.nfull, rowskip, rps);
+    if (tp.is_short) return launch_ilv<false, BMM, G256_ILV_DEFAULT, true, Epi, false, true>(A, lda, B, ldb, epi, M, N, K, 1, st, 0, rowskip, rps);
+    return launch_ilv<false, BMM, G256_ILV_DEFAULT, false, Epi, false, true>(A, lda, B, ldb, epi, M, N, K, 1, st, 0, rowskip, rps);
+}
+template <bool AMM, bool BMM, int ILV, bool SHORT, class Epi, bool MIXED, bool SKIP>
+static int launch_ilv(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi epi, int M, int N, int K, int nsplit, hipStream_t st, int nfull,
+                      const float* rowskip, int rps) {
+    auto kern = gemm256_kernel<AMM, BMM, ILV, Epi, SHORT, MIXED, SKIP>;
     static bool attr_done = false;
     if (!attr_done) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
@@ -606,7 +679,7 @@ static int launch_ilv(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi 
     const int splits = (ktiles + per - 1) / per;      // every split gets an even number (>= 2) of tiles
     if (g_dbg[1]) epi.M = 0;
     PA_LAUNCH(kern, dim3(tiles_m * tiles_n, splits), dim3(NT), LDS_BYTES, st, A, (uint32_t)lda, B, (uint32_t)ldb, epi, M, N,
-              ktiles, per, tiles_n, g_dbg[0], g_dbg[2], nfull, g_misc_knob[0] > 0 ? g_misc_knob[0] : env_patch);
+              ktiles, per, tiles_n, g_dbg[0], g_dbg[2], nfull, g_misc_knob[0] > 0 ? g_misc_knob[0] : env_patch, rowskip, rps);
     return (int)hipGetLastError();
 }
 // row tiles of the launch launch<AMM = false>(...) makes for this shape (partial rows of a column-sum epilogue = 2 x this)

@@ -297,11 +297,15 @@ class HotPath:
             if c.seggpt and merge_between_batch >= 0 and i >= merge_between_batch:
                 merge = 1 if c.merge_idx >= i else 2
             ds_a, ds_m = (None, None) if drop_scales is None else drop_scales[i]
+            # DropPath skipping: a sample whose factor is 0 gets 0 * (branch) added to its residual, so the kernels of the branch do not compute
+            # it (they read the factor vector themselves: no host synchronisation).  Not for the attention branch of an ensemble block: there a
+            # dropped sample's proj output still enters the other samples' group mean.
+            sk_a = None if merge > 0 else ds_a
             ln1, mean1, rstd1 = ops.layernorm_fwd(x, P[pre + "norm1.weight"], P[pre + "norm1.bias"], c.ln_eps, T)
-            qkv = ops.linear_fwd(ln1, self.w(pre + "attn.qkv.weight", P), P[pre + "attn.qkv.bias"], EPI_BIAS)
+            qkv = ops.linear_fwd(ln1, self.w(pre + "attn.qkv.weight", P), P[pre + "attn.qkv.bias"], EPI_BIAS, rowskip=sk_a, skip_rows_per_sample=L)
             rcat = self.relpos(pre, P, False)
-            ao, lse, atab = ops.attn_fwd(qkv, rcat, Bc, L, c.heads, c.Hp, c.Wp, c.scale, need_tables=True) if need_grad else \
-                ops.attn_fwd(qkv, rcat, Bc, L, c.heads, c.Hp, c.Wp, c.scale) + (None,)
+            ao, lse, atab = ops.attn_fwd(qkv, rcat, Bc, L, c.heads, c.Hp, c.Wp, c.scale, need_tables=True, rowskip=sk_a) if need_grad else \
+                ops.attn_fwd(qkv, rcat, Bc, L, c.heads, c.Hp, c.Wp, c.scale, rowskip=sk_a) + (None,)
             group = 0
             if merge > 0:
                 # x1 = x0 + s_a * ens(proj(...)) (models_seggpt.py:207-238).  Differentiable like the reference's Block.forward: mean over
@@ -319,11 +323,11 @@ class HotPath:
                     del e
             else:
                 x1 = ops.linear_fwd(ao, self.w(pre + "attn.proj.weight", P), P[pre + "attn.proj.bias"], EPI_BIAS_RESID,
-                                    resid=x, rowscale=ds_a, rows_per_sample=L)
+                                    resid=x, rowscale=ds_a, rows_per_sample=L, rowskip=sk_a)
             ln2, mean2, rstd2 = ops.layernorm_fwd(x1, P[pre + "norm2.weight"], P[pre + "norm2.bias"], c.ln_eps, T)
-            act, gaux = ops.linear_gelu(ln2, self.w(pre + "mlp.fc1.weight", P), P[pre + "mlp.fc1.bias"], need_aux=need_grad)
+            act, gaux = ops.linear_gelu(ln2, self.w(pre + "mlp.fc1.weight", P), P[pre + "mlp.fc1.bias"], need_aux=need_grad, rowskip=ds_m, rows_per_sample=L)
             x2 = ops.linear_fwd(act, self.w(pre + "mlp.fc2.weight", P), P[pre + "mlp.fc2.bias"], EPI_BIAS_RESID,
-                                resid=x1, rowscale=ds_m, rows_per_sample=L)
+                                resid=x1, rowscale=ds_m, rows_per_sample=L, rowskip=ds_m)
             if need_grad:
                 S.blocks.append((x, mean1, rstd1, ln1, qkv, rcat, ao, lse, x1, mean2, rstd2, ln2, gaux, act, Bc, atab, group))
             x = x2
@@ -500,6 +504,9 @@ class HotPath:
             S.blocks[i] = None
             R = Bc * L
             ds_a, ds_m = (None, None) if S.drop is None else S.drop[i]
+            # DropPath skipping (see forward): the dY rows of a dropped sample are exact zeros (the LayerNorm backward / merge_bwd multiplied
+            # them by the factor), so the branch's data-gradient kernels leave them out.  The ensemble mixes samples: no skipping there.
+            sk_a = None if ens_group > 0 else ds_a
             # the block's small gradients (LayerNorm affine, the four biases, the rel-pos tables) live in ONE flat buffer so that the
             # gradient exchange sends them as one message without a flattening copy: [norm1 g,b | norm2 g,b | qkv.b | proj.b | fc1.b | fc2.b | d rcat]
             nrp, hd = rcat.shape
@@ -527,13 +534,13 @@ class HotPath:
             tr("%d.dyT" % i, dyT)
             # (the GEMM's epilogue also sums the columns of the dpre it stores: fc1's bias gradient, no separate pass over [R, 4D])
             if _FC1_COLSUM == "epilogue":
-                dpre = ops.linear_dgrad(dyT, self.w(pre + "mlp.fc2.weight", P), gelu_aux=gaux, colsum_out=fl["fc1"])
+                dpre = ops.linear_dgrad(dyT, self.w(pre + "mlp.fc2.weight", P), gelu_aux=gaux, colsum_out=fl["fc1"], rowskip=ds_m, rows_per_sample=L)
                 G[pre + "mlp.fc1.bias"] = fl["fc1"]
             else:                                  # A/B: param_grads below sums the columns of dpre on the side stream
                 dpre = ops.linear_dgrad(dyT, self.w(pre + "mlp.fc2.weight", P), gelu_aux=gaux)
             tr("%d.dpre" % i, dpre)
             param_grads(pre + "mlp.fc1.weight", pre + "mlp.fc1.bias", dpre, ln2, fl["fc1"])
-            dln2 = ops.linear_dgrad(dpre, self.w(pre + "mlp.fc1.weight", P))
+            dln2 = ops.linear_dgrad(dpre, self.w(pre + "mlp.fc1.weight", P), rowskip=ds_m, rows_per_sample=L)
             tr("%d.dln2" % i, dln2)
             del dpre
             # dyT may still be read by the side stream: the attention branch's dY gets its own buffer
@@ -561,11 +568,11 @@ class HotPath:
                 dyA = da if T == torch.float32 else ops.cast_bf16(da, out=dyA)
                 del da
             param_grads(pre + "attn.proj.weight", pre + "attn.proj.bias", dyA, ao, fl["proj"])
-            dao = ops.linear_dgrad(dyA, self.w(pre + "attn.proj.weight", P), out=dln2)
+            dao = ops.linear_dgrad(dyA, self.w(pre + "attn.proj.weight", P), out=dln2, rowskip=sk_a, rows_per_sample=L)
             tr("%d.dao" % i, dao)
             del dyA
             rcatT = self.relpos(pre, P, True)
-            dqkv, dG = ops.attn_bwd_core(qkv, rcat, rcatT, ao, dao, lse, Bc, L, c.heads, c.Hp, c.Wp, c.scale, tables=atab, prep=_ATTN_PREP)
+            dqkv, dG = ops.attn_bwd_core(qkv, rcat, rcatT, ao, dao, lse, Bc, L, c.heads, c.Hp, c.Wp, c.scale, tables=atab, prep=_ATTN_PREP, rowskip=sk_a)
             if need(pre + "attn.rel_pos_h") or need(pre + "attn.rel_pos_w"):
                 # (the dQ kernel still writes its rel-pos partials / dG when the tables are frozen: only this reduction is skipped)
                 drcat = on_side(lambda: ops.attn_bwd_relpos(dG, qkv, nrp, Bc, L, c.heads, c.Hp, c.Wp, out=fl["rel"].view(nrp, hd)), dG, qkv)
@@ -575,7 +582,7 @@ class HotPath:
             del dG
             tr("%d.dqkv" % i, dqkv)
             param_grads(pre + "attn.qkv.weight", pre + "attn.qkv.bias", dqkv, ln1, fl["qkv"])
-            dln1 = ops.linear_dgrad(dqkv, self.w(pre + "attn.qkv.weight", P), out=dao)
+            dln1 = ops.linear_dgrad(dqkv, self.w(pre + "attn.qkv.weight", P), out=dao, rowskip=sk_a, rows_per_sample=L)
             del dqkv
             nxt = i - 1
             dyT_next = None

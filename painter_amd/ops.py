@@ -41,8 +41,29 @@ def _req(t, dtype=None):
 
 
 # ------------------------------------------------------------------------------------------- linear
-def linear_fwd(x, w, bias, epilogue=EPI_BIAS, out=None, out2=None, resid=None, rowscale=None, rows_per_sample=1):
-    """x [M,K] T (row stride free), w [N,K] T contiguous, bias [N] f32."""
+def _skip_args(rowskip, skip_rows_per_sample, M):
+    """DropPath skipping (include/painter_hip.h, ABI 7): rowskip = the branch's factor vector, f32 [M / skip_rows_per_sample]."""
+    if rowskip is None:
+        return 0, 1
+    assert rowskip.dtype == torch.float32 and rowskip.is_cuda and rowskip.is_contiguous() and skip_rows_per_sample >= 1
+    assert rowskip.numel() * skip_rows_per_sample >= M, (rowskip.numel(), skip_rows_per_sample, M)
+    return rowskip.data_ptr(), int(skip_rows_per_sample)
+
+
+def drop_skip(mode=None):
+    """The run-time switch of DropPath skipping (pa_debug_set knob 16): 0 default (on unless PAINTER_AMD_DROP_SKIP=0), 1 off, 2 on.
+    -> the value found; sets `mode` when given."""
+    old = int(lib.pa_debug_get(16))
+    if mode is not None:
+        check(lib.pa_debug_set(16, int(mode)), "pa_debug_set")
+    return old
+
+
+def linear_fwd(x, w, bias, epilogue=EPI_BIAS, out=None, out2=None, resid=None, rowscale=None, rows_per_sample=1, *, rowskip=None,
+               skip_rows_per_sample=None):
+    """x [M,K] T (row stride free), w [N,K] T contiguous, bias [N] f32.
+    rowskip (f32 [M / skip_rows_per_sample], default skip_rows_per_sample = rows_per_sample): the DropPath factors of the branch this GEMM
+    belongs to; row tiles that lie wholly in samples whose factor is 0 are not computed (their outputs: the epilogue of a zero accumulator)."""
     M, K = x.shape
     N = w.shape[0]
     T = x.dtype
@@ -53,12 +74,17 @@ def linear_fwd(x, w, bias, epilogue=EPI_BIAS, out=None, out2=None, resid=None, r
         out = torch.empty((M, N), dtype=odt, device=x.device)
     if epilogue == EPI_BIAS_RESID:
         assert resid is not None and resid.dtype == torch.float32 and resid.stride(0) == out.stride(0)
-    check(lib.pa_linear_fwd(code(T), epilogue, p(x), x.stride(0), p(w), p(bias), p(out), p(out2), out.stride(0),
-                            p(resid), p(rowscale), rows_per_sample, M, N, K, stream()), "pa_linear_fwd")
+    if rowskip is None:
+        check(lib.pa_linear_fwd(code(T), epilogue, p(x), x.stride(0), p(w), p(bias), p(out), p(out2), out.stride(0),
+                                p(resid), p(rowscale), rows_per_sample, M, N, K, stream()), "pa_linear_fwd")
+    else:
+        sk, srps = _skip_args(rowskip, rows_per_sample if skip_rows_per_sample is None else skip_rows_per_sample, M)
+        check(lib.pa_linear_fwd_skip(code(T), epilogue, p(x), x.stride(0), p(w), p(bias), p(out), p(out2), out.stride(0),
+                                     p(resid), p(rowscale), rows_per_sample, M, N, K, sk, srps, stream()), "pa_linear_fwd_skip")
     return out
 
 
-def linear_gelu(x, w, bias, need_aux=True):
+def linear_gelu(x, w, bias, need_aux=True, *, rowskip=None, rows_per_sample=1):
     """-> (act = gelu(x W^T + b), aux): aux is what linear_dgrad(gelu_aux=...) needs of the pre-activation -- the pre-activation itself in the
     exact-fp32 build, the 8-bit code of gelu'(pre) (uint8 [M, N]; gelu_aux_decode) in the bf16 build (include/painter_hip.h, PA_EPI_BIAS_GELU)."""
     M = x.shape[0]
@@ -66,7 +92,7 @@ def linear_gelu(x, w, bias, need_aux=True):
     act = torch.empty((M, N), dtype=x.dtype, device=x.device)
     aux = torch.empty((M, N), dtype=gelu_aux_dtype(x.dtype), device=x.device) if need_aux else None
     assert aux is None or aux.stride(0) == act.stride(0)
-    linear_fwd(x, w, bias, EPI_BIAS_GELU, out=act, out2=aux)
+    linear_fwd(x, w, bias, EPI_BIAS_GELU, out=act, out2=aux, rowskip=rowskip, skip_rows_per_sample=rows_per_sample)
     return act, aux
 
 
@@ -96,10 +122,12 @@ def linear_pixshuf(x, w, bias, batch, Hp, Wp, P, C):
     return out
 
 
-def linear_dgrad(dy, w, gelu_aux=None, out=None, colsum_out=None):
+def linear_dgrad(dy, w, gelu_aux=None, out=None, colsum_out=None, *, rowskip=None, rows_per_sample=1):
     """dX[M,K] = dY[M,N] . W[N,K]  (* gelu'(pre) when gelu_aux, the second result of linear_gelu() in the same dtype, is given).
     colsum_out (f32 [K], optional): receives the column sums of dX as stored -- the bias gradient of the layer whose dY dX is -- from the
-    GEMM's epilogue (bf16 fast path) instead of a separate pass."""
+    GEMM's epilogue (bf16 fast path) instead of a separate pass.
+    rowskip (f32 [M / rows_per_sample]): the DropPath factors of the branch; dY rows of a sample whose factor is 0 are zero, row tiles
+    that lie wholly in such samples are not computed (dX rows zero)."""
     M, N = dy.shape
     K = w.shape[1]
     T = dy.dtype
@@ -112,8 +140,13 @@ def linear_dgrad(dy, w, gelu_aux=None, out=None, colsum_out=None):
     if colsum_out is not None:
         assert colsum_out.shape == (K,) and colsum_out.dtype == torch.float32 and colsum_out.is_contiguous()
         ws = workspace(lib.pa_linear_dgrad_workspace_bytes(M, K), dy.device, slot=2)
-    check(lib.pa_linear_dgrad(code(T), p(dy), dy.stride(0), p(w), p(gelu_aux), p(out), out.stride(0), p(colsum_out), p(ws), M, N, K, stream()),
-          "pa_linear_dgrad")
+    if rowskip is None:
+        check(lib.pa_linear_dgrad(code(T), p(dy), dy.stride(0), p(w), p(gelu_aux), p(out), out.stride(0), p(colsum_out), p(ws), M, N, K, stream()),
+              "pa_linear_dgrad")
+    else:
+        sk, srps = _skip_args(rowskip, rows_per_sample, M)
+        check(lib.pa_linear_dgrad_skip(code(T), p(dy), dy.stride(0), p(w), p(gelu_aux), p(out), out.stride(0), p(colsum_out), p(ws), M, N, K,
+                                       sk, srps, stream()), "pa_linear_dgrad_skip")
     return out
 
 
@@ -219,9 +252,10 @@ def relpos_pack_batch(tabs, nblocks, Hp, Wp, hd, dtype, rcat=None, rcatT=None):
     return rcat, rcatT
 
 
-def attn_fwd(qkv, rcat, batch, L, heads, Hp, Wp, scale, need_tables=False):
+def attn_fwd(qkv, rcat, batch, L, heads, Hp, Wp, scale, need_tables=False, *, rowskip=None):
     """qkv [batch*L, 3*heads*hd] T -> (out [batch*L, heads*hd] T, lse [batch*heads, L] f32[, tables]).
-    need_tables: also return the per-query bias tables the backward reuses (None when the kernels in use do not export them)."""
+    need_tables: also return the per-query bias tables the backward reuses (None when the kernels in use do not export them).
+    rowskip (f32 [batch]): DropPath factors of the attention branch; a sample whose factor is 0 is not computed (out, lse, tables: zeros)."""
     T = qkv.dtype
     hd = rcat.shape[1]
     assert qkv.shape[1] == 3 * heads * hd
@@ -232,8 +266,12 @@ def attn_fwd(qkv, rcat, batch, L, heads, Hp, Wp, scale, need_tables=False):
         nb = lib.pa_attn_tables_bytes(code(T), batch, L, heads, Hp, Wp, hd)
         if nb > 0:
             tables = torch.empty((nb,), dtype=torch.uint8, device=qkv.device)
-    check(lib.pa_attn_fwd(code(T), p(qkv), qkv.stride(0), p(rcat), p(out), out.stride(0), p(lse), p(tables), batch, L, heads,
-                          Hp, Wp, hd, float(scale), stream()), "pa_attn_fwd")
+    if rowskip is None:
+        check(lib.pa_attn_fwd(code(T), p(qkv), qkv.stride(0), p(rcat), p(out), out.stride(0), p(lse), p(tables), batch, L, heads,
+                              Hp, Wp, hd, float(scale), stream()), "pa_attn_fwd")
+    else:
+        check(lib.pa_attn_fwd_skip(code(T), p(qkv), qkv.stride(0), p(rcat), p(out), out.stride(0), p(lse), p(tables), batch, L, heads,
+                                   Hp, Wp, hd, float(scale), _skip_args(rowskip, 1, batch)[0], stream()), "pa_attn_fwd_skip")
     return (out, lse, tables) if need_tables else (out, lse)
 
 
@@ -255,13 +293,14 @@ def relpos_pack_t(rel_pos_h, rel_pos_w, Hp, Wp, dtype):
     return rcatT
 
 
-def attn_bwd_core(qkv, rcat, rcatT, out, dout, lse, batch, L, heads, Hp, Wp, scale, tables=None, prep="fused"):
+def attn_bwd_core(qkv, rcat, rcatT, out, dout, lse, batch, L, heads, Hp, Wp, scale, tables=None, prep="fused", *, rowskip=None):
     """-> (dqkv T [batch*L, 3*heads*hd], dG): the data gradients and what attn_bwd_relpos() turns into the rel-pos table gradients --
     either the per-query bias gradients dG T [batch*L, heads*NRP], or (28-token-wide bf16 kernels with `tables`) the per-workgroup
     fp32 partial sums of the table gradient itself, a uint8 scratch tensor (the dQ kernel contracts them; dG never exists).
     tables: what attn_fwd(need_tables=True) returned (it carries the lse fields; the backward writes its delta field into it).
     prep (where the tables can carry Delta): "fused" = the dQ kernel computes Delta = rowsum(dO o O) itself (no extra launch: round 5),
-    "launch" = the round-4 route, one pa_attn_bwd_prep launch in front (A/B, tests)."""
+    "launch" = the round-4 route, one pa_attn_bwd_prep launch in front (A/B, tests).
+    rowskip (f32 [batch]): DropPath factors of the attention branch; a sample whose factor is 0 (its dout rows are zero) is not computed."""
     T = qkv.dtype
     dev = qkv.device
     nrp, hd = rcat.shape
@@ -286,9 +325,14 @@ def attn_bwd_core(qkv, rcat, rcatT, out, dout, lse, batch, L, heads, Hp, Wp, sca
     else:
         dG = torch.empty((batch * L, heads * nrp), dtype=T, device=dev)
     aux = workspace(lib.pa_attn_bwd_aux_bytes(batch, L, heads, Hp, Wp), dev, slot=1)
-    check(lib.pa_attn_bwd(code(T), p(qkv), qkv.stride(0), p(rcat), p(rcatT), p(dout), dout.stride(0), p(lse), p(delta),
-                          p(dqkv), p(dG), p(part), p(aux), p(tables), p(o_arg), 0 if o_arg is None else o_arg.stride(0), batch, L, heads, Hp, Wp, hd,
-                          float(scale), stream()), "pa_attn_bwd")
+    if rowskip is None:
+        check(lib.pa_attn_bwd(code(T), p(qkv), qkv.stride(0), p(rcat), p(rcatT), p(dout), dout.stride(0), p(lse), p(delta),
+                              p(dqkv), p(dG), p(part), p(aux), p(tables), p(o_arg), 0 if o_arg is None else o_arg.stride(0), batch, L, heads, Hp, Wp, hd,
+                              float(scale), stream()), "pa_attn_bwd")
+    else:
+        check(lib.pa_attn_bwd_skip(code(T), p(qkv), qkv.stride(0), p(rcat), p(rcatT), p(dout), dout.stride(0), p(lse), p(delta),
+                                   p(dqkv), p(dG), p(part), p(aux), p(tables), p(o_arg), 0 if o_arg is None else o_arg.stride(0), batch, L, heads, Hp, Wp,
+                                   hd, float(scale), _skip_args(rowskip, 1, batch)[0], stream()), "pa_attn_bwd_skip")
     return dqkv, (dG if part is None else part)
 
 
