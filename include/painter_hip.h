@@ -37,8 +37,8 @@ enum {
 };
 
 /* Bumped whenever an entry point's argument list changes (2: `tables` in pa_attn_fwd / pa_attn_bwd; 3: `head_dim` in the attention and
- * rel-pos entry points; 4: `dxT_colsum` in pa_layernorm_bwd, `relpos_part` in pa_attn_bwd, `dx_colsum` in pa_linear_dgrad; 5: the bf16 GELU side output is gelu'(pre), pa_debug_set(9) is a test knob of the conv3x3 weight gradient, pa_attn4_trace is gone, pa_attn_bwd takes `out` / `ldo`, pa_debug_get / pa_attn_launch_counts are new; 6: the bf16 GELU side output is an 8-bit code (uint8, row pitch ldo bytes), pa_debug_set knobs 10 .. 15; 7: the *_skip entry points (DropPath skipping) and pa_debug_set knob 16 -- every earlier entry point keeps its argument list).  painter_amd/_lib.py refuses a library whose pa_abi_version() differs from the header it parsed. */
-#define PA_ABI_VERSION 7
+ * rel-pos entry points; 4: `dxT_colsum` in pa_layernorm_bwd, `relpos_part` in pa_attn_bwd, `dx_colsum` in pa_linear_dgrad; 5: the bf16 GELU side output is gelu'(pre), pa_debug_set(9) is a test knob of the conv3x3 weight gradient, pa_attn4_trace is gone, pa_attn_bwd takes `out` / `ldo`, pa_debug_get / pa_attn_launch_counts are new; 6: the bf16 GELU side output is an 8-bit code (uint8, row pitch ldo bytes), pa_debug_set knobs 10 .. 15; 7: the *_skip entry points (DropPath skipping) and pa_debug_set knob 16 -- every earlier entry point keeps its argument list; 8: the pa_painter_* / pa_palette_argmin entry points of Painter task inference -- every earlier entry point keeps its argument list).  painter_amd/_lib.py refuses a library whose pa_abi_version() differs from the header it parsed. */
+#define PA_ABI_VERSION 8
 int pa_abi_version(void);
 /* diagnostics only (tools/): which = 0 start-up stagger of alternate workgroup rows of the 256x256 GEMM in shader cycles,
  * 1 drop that kernel's epilogue stores (never set by the product path); 2 = tile order of that kernel: 0 blocked 4 x 8 patches per XCD and, for
@@ -408,6 +408,44 @@ int pa_resized_crop_u8_batch(const pa_crop_job* jobs, void* mid, int n_jobs, int
 int64_t pa_pair_valid_workspace_bytes(int batch);
 int pa_pair_valid(const float* tgts, float* valid, const void* modes, const void* thres, void* workspace, int batch, int plane,
                   hipStream_t stream);
+
+/* ---- Painter task inference, pre-/post-processing on the device.  Replaces the numpy / CPU-torch work around the model call in the
+ * eight scripts Painter/eval/<task>/painter_inference_*.py (ade20k_semantic/..._segm.py, coco_panoptic/..._pano_semseg.py and ..._pano_inst.py,
+ * mmpose_custom/..._pose.py, nyuv2_depth/..._depth.py, derain/..._derain.py, lol/..._lol.py, sidd/..._sidd.py) and the colour -> class
+ * decode of ade20k_semantic/ADE20kSemSegEvaluatorCustom.py, for a batch of pictures per launch.  uint8 / int32 outputs are bit-exact with
+ * the scripts' host path (float64 throughout, CPU torch's bilinear operation order); the bicubic float64 output agrees to ~1e-13. ---- */
+/* painter_inference_segm.py:150-162 for n_queries pictures: imgs[n] = [prompt ; query_n], tgts[n] = [prompt_target ; prompt_target]
+ * along H ("tgt is not available"), (v / 255 - mean) / std in float64, written as float32 NCHW [n_queries][3][2*res_h][res_w].
+ * prompt, prompt_target: uint8 [res_h][res_w][3]; queries: uint8 [n_queries][res_h][res_w][3]. */
+int pa_painter_stitch(const void* prompt, const void* prompt_target, const void* queries, float* imgs, float* tgts, int n_queries,
+                      int res_h, int res_w, hipStream_t stream);
+/* One output picture of a decode launch.  The decode entry points take pred = the model's float32 tokens
+ * [n_samples][2*res_h/patch * res_w/patch][patch*patch*3] and jobs = DEVICE array of n_jobs records; the source of a job is the lower
+ * half of unpatchify(pred[sample]); max_h / max_w = the largest out_h / out_w of the table.  A job whose sample is outside
+ * [0, n_samples) writes nothing. */
+typedef struct pa_decode_job {
+    void* out;                  /* device address of this picture's output, densely packed */
+    void* out2;                 /* pa_painter_decode_f64: optional uint8 [out_h][out_w][3], or NULL; unused otherwise */
+    int32_t sample;
+    int32_t out_h, out_w;
+    int32_t reserved;
+} pa_decode_job;
+/* ..._segm.py:88-92, ..._pano_semseg.py:88-92 (nearest = 0: F.interpolate bilinear), ..._pano_inst.py:88-92, ..._pose.py:86-91 (nearest = 1):
+ * out = uint8 [out_h][out_w][3] = trunc(resize(clip((y * std + mean) * 255, 0, 255))). */
+int pa_painter_decode_u8(const float* pred, const pa_decode_job* jobs, int n_jobs, int n_samples, int max_h, int max_w, int res_h,
+                         int res_w, int patch, int nearest, hipStream_t stream);
+/* ..._depth.py:69-73: out = int32 [out_h][out_w] = trunc(mean over channels of bilinear(clip((y * std + mean) * 10000, 0, 10000))). */
+int pa_painter_decode_depth(const float* pred, const pa_decode_job* jobs, int n_jobs, int n_samples, int max_h, int max_w, int res_h,
+                            int res_w, int patch, hipStream_t stream);
+/* ..._derain.py:76-79, ..._lol.py:65-68, ..._sidd.py:81-84: out = float64 [out_h][out_w][3] = bicubic (A = -0.75, align_corners = False,
+ * border indices clamped) resize of y * std + mean, no clip; out2 (if not NULL) = uint8(clip(out, 0, 1) * 255), the picture they save. */
+int pa_painter_decode_f64(const float* pred, const pa_decode_job* jobs, int n_jobs, int n_samples, int max_h, int max_w, int res_h,
+                          int res_w, int patch, hipStream_t stream);
+/* ADE20kSemSegEvaluatorCustom.py:114-141: out = int32 [h][w] = index of the FIRST minimum over the n_colours (<= 4096) palette rows of
+ * sum_c d(pixel_c - colour_c) in float32; dist_type 0 d = abs, 1 d = square, 2 d = (abs + square) / 2.  image: uint8 [h][w][3];
+ * palette: float32 [n_colours][3]. */
+int pa_palette_argmin(const void* image, const float* palette, void* out_i32, int h, int w, int n_colours, int dist_type,
+                      hipStream_t stream);
 
 #ifdef __cplusplus
 }

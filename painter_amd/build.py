@@ -21,8 +21,9 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 if os.environ.get("PA_SLP") != "1":
     FLAGS = FLAGS + ["-fno-slp-vectorize"]
 FLAGS = FLAGS + os.environ.get("PA_EXTRA_FLAGS", "").split()
-# seggpt_io.hip / pair_io.hip reproduce host float arithmetic (numpy, Pillow) bit for bit: no fused multiply-add there.
-EXTRA = {"seggpt_io.hip": ["-ffp-contract=off"], "pair_io.hip": ["-ffp-contract=off"]}
+# seggpt_io.hip / pair_io.hip / painter_io.hip reproduce host float arithmetic (numpy, Pillow, CPU torch) bit for bit: no fused
+# multiply-add there except the explicit fma() calls of painter_io.hip's bilinear resize.
+EXTRA = {"seggpt_io.hip": ["-ffp-contract=off"], "pair_io.hip": ["-ffp-contract=off"], "painter_io.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

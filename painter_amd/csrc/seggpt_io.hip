@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include "../../include/painter_hip.h"
 #include "common.h"
+#include "image_io.h"          // kMean / kStd, normalise(), decoded_scaled(): shared with painter_io.hip
 
 #pragma clang fp contract(off)
 
@@ -24,9 +25,6 @@ namespace {
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;          // Pillow Resample.c
 constexpr int MAXC = 4;
-
-__device__ __constant__ double kMean[3] = {0.485, 0.456, 0.406};      // seggpt_engine.py:9
-__device__ __constant__ double kStd[3] = {0.229, 0.224, 0.225};       // seggpt_engine.py:10
 
 DEVI uint8_t clip8(int acc) {
     const int v = acc >> PRECISION_BITS;
@@ -115,14 +113,6 @@ __global__ __launch_bounds__(256) void gather_u8_kernel(const uint8_t* __restric
     for (int c = 0; c < C; ++c) d[c] = s[c];
 }
 
-// (v / div - mean) / std, one rounding per operation, then narrowed to float32 (numpy float64 -> torch .float()).
-DEVI float normalise(uint8_t u, double div, int c) {
-    double v = (double)u / div;
-    v = v - kMean[c];
-    v = v / kStd[c];
-    return (float)v;
-}
-
 // grid: x = blocks of 256 columns, y = row of the stitched 2R x W canvas, z = prompt.  Reads 3-byte pixels, writes three coalesced
 // float32 planes for imgs and tgts.
 __global__ __launch_bounds__(256) void stitch_kernel(const uint8_t* __restrict__ prompts, const uint8_t* __restrict__ targets,
@@ -147,16 +137,7 @@ __global__ __launch_bounds__(256) void stitch_kernel(const uint8_t* __restrict__
 // Element (r, x, c) of the LOWER res_h x res_w half of unpatchify(pred) (models_seggpt.py:376-389), then seggpt_engine.py:52:
 // clip((v * std + mean) * 255, 0, 255) in float64.
 DEVI double decoded(const float* __restrict__ pred, int r, int x, int c, int res_h, int wp, int P) {
-    const int row = res_h + r;
-    const int token = (row / P) * wp + x / P;
-    const int within = ((row % P) * P + x % P) * 3 + c;
-    double o = (double)pred[(size_t)token * (P * P * 3) + within];
-    o = o * kStd[c];
-    o = o + kMean[c];
-    o = o * 255.0;
-    o = o < 0.0 ? 0.0 : o;                  // torch.clip: max with 0, then min with 255 (NaN propagates through both selects)
-    o = o > 255.0 ? 255.0 : o;
-    return o;
+    return decoded_scaled(pred, r, x, c, res_h, wp, P, 255.0);
 }
 
 __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ pred, double* __restrict__ out, int res_h, int res_w, int P) {

@@ -1,0 +1,243 @@
+"""Painter task inference with the pre- and post-processing on the MI355X, batched.
+
+The reference's eight task scripts (Painter/eval/*/painter_inference_*.py) run one picture at a time and do everything around the
+forward on the host: `PIL.resize`, `/ 255.`, `np.concatenate`, `- mean`, `/ std` in float64 on two 896 x 448 x 3 canvases, three
+4.8 MB uploads, and after the forward `unpatchify`, `.cpu()` of the whole canvas, de-normalise / clip in float64 and
+`F.interpolate` (bilinear, nearest or bicubic) on the CPU to the picture's own size.  Here a picture crosses PCIe once in each
+direction (uint8 in; uint8 / int32 / float64 at its own size out) and every array operation in between is a kernel of
+csrc/painter_io.hip (resize: csrc/seggpt_io.hip):
+
+    upload uint8 -> Pillow-exact resize -> stitch with the prompt pair -> ONE forward of up to `batch_size` pictures ->
+    ONE decode launch over a job table (pictures of different sizes included) -> ONE copy back
+
+The uint8 / int32 outputs are the bytes the scripts write (tests/test_painter_eval_gpu.py, against tests/painter_eval_host.py and
+the digests the unmodified scripts produced); the float64 output of the three restoration tasks agrees with CPU torch's bicubic to
+~1e-13 (torch's own operation order is not reproduced there).
+
+Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
+(`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
+`cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
+canvases the script built, or pass an already resized 448 x 448 uint8 query to `run`); PSNR / SSIM; the detectron2 / mmpose
+evaluators apart from the colour -> class decode (`class_map`).
+
+There is no CPU fallback: a CPU device or a missing libpainter_hip.so raises.
+"""
+import ctypes
+
+import numpy as np
+import torch
+from PIL import Image
+
+from ._lib import check, lib
+from .seggpt_engine import DeviceIO, _stream
+
+# resize = F.interpolate mode after the forward; scale, clip = `torch.clip((y * std + mean) * scale, 0, scale)` or none;
+# kind = u8: `.int()` -> uint8 [H][W][3] PNG | depth: `.mean(-1).int()` -> int32 [H][W] PNG | f64: float64 [H][W][3] returned
+TASKS = {
+    "ade20k_semseg": dict(resize="bilinear", scale=255.0, clip=True, kind="u8"),          # ade20k_semantic/painter_inference_segm.py
+    "coco_pano_semseg": dict(resize="bilinear", scale=255.0, clip=True, kind="u8"),       # coco_panoptic/painter_inference_pano_semseg.py
+    "coco_pano_inst": dict(resize="nearest", scale=255.0, clip=True, kind="u8"),          # coco_panoptic/painter_inference_pano_inst.py
+    "coco_pose": dict(resize="nearest", scale=255.0, clip=True, kind="u8"),               # mmpose_custom/painter_inference_pose.py
+    "nyuv2_depth": dict(resize="bilinear", scale=10000.0, clip=True, kind="depth"),       # nyuv2_depth/painter_inference_depth.py
+    "derain": dict(resize="bicubic", scale=1.0, clip=False, kind="f64"),                  # derain/painter_inference_derain.py
+    "lol": dict(resize="bicubic", scale=1.0, clip=False, kind="f64"),                     # lol/painter_inference_lol.py
+    "sidd": dict(resize="bicubic", scale=1.0, clip=False, kind="f64"),                    # sidd/painter_inference_sidd.py
+}
+DIST_TYPES = {"abs": 0, "square": 1, "mean": 2}
+_OUT = {"u8": (torch.uint8, 3), "depth": (torch.int32, 1), "f64": (torch.float64, 3)}       # dtype, channels
+
+
+class DecodeJob(ctypes.Structure):
+    """pa_decode_job of include/painter_hip.h."""
+    _fields_ = [("out", ctypes.c_void_p), ("out2", ctypes.c_void_p), ("sample", ctypes.c_int32), ("out_h", ctypes.c_int32),
+                ("out_w", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+def _task(name):
+    if name not in TASKS:
+        raise KeyError("painter_engine: unknown task %r (one of %s)" % (name, ", ".join(TASKS)))
+    return TASKS[name]
+
+
+def _unwrap(model):
+    return model.module if hasattr(model, "module") else model          # the scripts wrap the model in DistributedDataParallel
+
+
+def _require_cuda(device):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("painter_amd.painter_engine runs its image kernels on an MI355X only (no CPU fallback); got %s" % device)
+    return device
+
+
+def _forward(model, imgs, tgts):
+    """The model call of the scripts' run_one_image (painter_inference_segm.py:76-84): second half of the canvas masked, everything
+    valid; eval mode, no_grad.  -> float32 tokens [N][L][p*p*3]."""
+    n = model.patch_embed.num_patches
+    masked = torch.zeros(1, n, device=imgs.device)
+    masked[:, n // 2:] = 1
+    return model(imgs, tgts, masked, torch.ones_like(tgts))[1]
+
+
+class DecodePlan:
+    """Everything a decode launch needs that depends only on the task and the output sizes: the flat output buffer(s), one view
+    (offset, shape) per picture and the job table on the device."""
+
+    def __init__(self, task, sizes, device, saved=False, samples=None):
+        self.task, self.spec = task, _task(task)
+        dtype, ch = _OUT[self.spec["kind"]]
+        self.views, total = [], 0
+        for (w, h) in sizes:
+            w, h = int(w), int(h)
+            assert w >= 1 and h >= 1, (w, h)
+            self.views.append((total, (h, w, 3) if ch == 3 else (h, w)))
+            total += h * w * ch
+        self.out = torch.empty(total, dtype=dtype, device=device)
+        self.out8 = torch.empty(total, dtype=torch.uint8, device=device) if saved and self.spec["kind"] == "f64" else None
+        n = len(self.views)
+        jobs = (DecodeJob * n)()
+        for i, (off, shape) in enumerate(self.views):
+            jobs[i].out = self.out.data_ptr() + off * self.out.element_size()
+            jobs[i].out2 = None if self.out8 is None else self.out8.data_ptr() + off
+            jobs[i].sample = i if samples is None else int(samples[i])
+            jobs[i].out_h, jobs[i].out_w = shape[0], shape[1]
+        # pinned + asynchronous: the copy is ordered on the stream and the host does not wait for work enqueued earlier
+        self._table_host = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).pin_memory()
+        self.table = self._table_host.to(device, non_blocking=True)
+        self.n_jobs = n
+        self.max_h, self.max_w = max(v[1][0] for v in self.views), max(v[1][1] for v in self.views)
+
+    def launch(self, pred, res_h, res_w, patch):
+        """ONE launch over pred = float32 CUDA tokens [N][L][p*p*3]."""
+        pred = pred.detach().to(torch.float32).contiguous()
+        assert pred.is_cuda and pred.dim() == 3 and \
+            tuple(pred.shape[1:]) == ((2 * res_h // patch) * (res_w // patch), patch * patch * 3), tuple(pred.shape)
+        args = (pred.data_ptr(), self.table.data_ptr(), self.n_jobs, int(pred.shape[0]), self.max_h, self.max_w, res_h, res_w, patch)
+        if self.spec["kind"] == "u8":
+            check(lib.pa_painter_decode_u8(*args, 1 if self.spec["resize"] == "nearest" else 0, _stream()), "pa_painter_decode_u8")
+        elif self.spec["kind"] == "depth":
+            check(lib.pa_painter_decode_depth(*args, _stream()), "pa_painter_decode_depth")
+        else:
+            check(lib.pa_painter_decode_f64(*args, _stream()), "pa_painter_decode_f64")
+        return self
+
+    def pictures(self):
+        """The copy back (and the one synchronisation) -> one numpy array per picture."""
+        return _split(self.out, self.views)
+
+    def saved_pictures(self):
+        """f64 tasks planned with `saved`: the uint8 pictures the restoration scripts save, `uint8(clip(out, 0, 1) * 255)`."""
+        return _split(self.out8, self.views)
+
+
+def decode(task, pred, sizes, res_h, res_w, patch, saved=False):
+    """Plan and launch in one call: sizes = [(width, height)] per sample of pred, as the scripts pass them.  -> the DecodePlan
+    (`.pictures()`, `.saved_pictures()`)."""
+    assert len(sizes) == pred.shape[0], (len(sizes), tuple(pred.shape))
+    return DecodePlan(task, sizes, pred.device, saved=saved).launch(pred, res_h, res_w, patch)
+
+
+def _split(flat, views):
+    a = flat.cpu().numpy()
+    return [a[off:off + int(np.prod(shape))].reshape(shape) for off, shape in views]
+
+
+def class_map(picture, palette, dist_type="abs", device="cuda"):
+    """ADE20kSemSegEvaluatorCustom.post_process_segm_output (:114-141): uint8 [H][W][3] picture (numpy or CUDA tensor), palette
+    [K][3] -> int32 [H][W] numpy, the index of the nearest palette colour (first minimum)."""
+    device = _require_cuda(picture.device if torch.is_tensor(picture) else device)
+    if dist_type not in DIST_TYPES:
+        raise NotImplementedError(dist_type)
+    img = picture if torch.is_tensor(picture) else torch.from_numpy(np.ascontiguousarray(picture)).to(device)
+    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.is_contiguous(), (img.dtype, tuple(img.shape))
+    pal = torch.as_tensor(np.asarray(palette), dtype=torch.float32).to(device).contiguous()
+    assert pal.dim() == 2 and pal.shape[1] == 3, tuple(pal.shape)
+    h, w = int(img.shape[0]), int(img.shape[1])
+    out = torch.empty((h, w), dtype=torch.int32, device=device)
+    check(lib.pa_palette_argmin(img.data_ptr(), pal.data_ptr(), out.data_ptr(), h, w, int(pal.shape[0]), DIST_TYPES[dist_type], _stream()),
+          "pa_palette_argmin")
+    return out.cpu().numpy()
+
+
+class PainterEngine:
+    """One prompt pair, one task, any number of query pictures.  prompt_img / prompt_tgt: RGB uint8 arrays of any size, resized once
+    (`Image.resize((input_size, input_size))`, Pillow-exact) and kept on the device."""
+
+    def __init__(self, model, device, task, prompt_img, prompt_tgt, input_size=448, batch_size=8):
+        self.device = _require_cuda(device)
+        self.task, self.spec = task, _task(task)
+        self.model = _unwrap(model)
+        self.res = int(input_size)
+        self.batch_size = int(batch_size)
+        assert self.batch_size >= 1
+        self.io = DeviceIO(self.device, res=self.res, hres=self.res, patch=int(self.model.patch_size))
+        self.prompt = self.io.resize(self.io.upload(prompt_img), (self.res, self.res))
+        self.prompt_tgt = self.io.resize(self.io.upload(prompt_tgt), (self.res, self.res))
+
+    def stitch(self, queries):
+        """queries: uint8 CUDA [N][res][res][3] -> (imgs, tgts) float32 [N][3][2*res][res]."""
+        n = queries.shape[0]
+        assert queries.is_cuda and queries.dtype == torch.uint8 and queries.is_contiguous() and \
+            tuple(queries.shape) == (n, self.res, self.res, 3), (queries.dtype, tuple(queries.shape))
+        imgs = torch.empty((n, 3, 2 * self.res, self.res), dtype=torch.float32, device=self.device)
+        tgts = torch.empty_like(imgs)
+        check(lib.pa_painter_stitch(self.prompt.data_ptr(), self.prompt_tgt.data_ptr(), queries.data_ptr(), imgs.data_ptr(), tgts.data_ptr(),
+                                    n, self.res, self.res, _stream()), "pa_painter_stitch")
+        return imgs, tgts
+
+    @torch.no_grad()
+    def _run_batch(self, pictures, sizes, saved):
+        """Host copies (the uint8 pictures, the job table) are all enqueued BEFORE the forward, while the stream holds nothing but
+        this batch's own resizes; from the forward's first launch to the copy back the host only enqueues kernels."""
+        io = self.io
+        queries = torch.stack([io.resize(io.upload(p), (self.res, self.res)) for p in pictures])
+        plan = DecodePlan(self.task, sizes, self.device, saved=saved)
+        imgs, tgts = self.stitch(queries)
+        y = _forward(self.model, imgs, tgts)
+        plan.launch(y, self.res, self.res, io.patch)
+        return plan.pictures(), (plan.saved_pictures() if saved else None)
+
+    def _run(self, pictures, sizes, saved):
+        if sizes is None:
+            sizes = [(p.shape[1], p.shape[0]) for p in pictures]
+        assert len(sizes) == len(pictures)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            outs, outs8 = [], []
+            for i in range(0, len(pictures), self.batch_size):
+                o, o8 = self._run_batch(pictures[i:i + self.batch_size], sizes[i:i + self.batch_size], saved)
+                outs.extend(o)
+                outs8.extend(o8 or [])
+        finally:
+            self.model.train(was_training)
+        return outs, outs8
+
+    def run(self, pictures, sizes=None):
+        """pictures: list of RGB uint8 arrays [H][W][3] of any sizes -> one array per picture at its own size, or at sizes[i] =
+        (width, height): uint8 [H][W][3], int32 [H][W] or float64 [H][W][3] by task."""
+        return self._run(pictures, sizes, False)[0]
+
+    def run_restoration(self, pictures, sizes=None):
+        """derain / lol / sidd: -> (float64 arrays as `run` returns them, the uint8 pictures those scripts save), both written by the
+        one decode launch (a second copy back carries the uint8 pictures)."""
+        if self.spec["kind"] != "f64":
+            raise ValueError("painter_engine: task %r saves its output as it is; run_restoration is for derain / lol / sidd" % self.task)
+        return self._run(pictures, sizes, True)
+
+
+@torch.no_grad()
+def run_one_image(img, tgt, size, model, out_path, device, task):
+    """The scripts' `run_one_image(img, tgt, size, model, out_path, device)` plus the task name: img, tgt = the normalised float
+    arrays [2*res][res][3] the script built, size = (width, height).  Decodes on the device and writes the file the script writes
+    (u8 / depth tasks); the three restoration tasks return the float64 array [H][W][3] as theirs do."""
+    device = _require_cuda(device)
+    spec = _task(task)
+    m = _unwrap(model)
+    x = torch.as_tensor(np.asarray(img)).unsqueeze(0).permute(0, 3, 1, 2).float().to(device).contiguous()
+    t = torch.as_tensor(np.asarray(tgt)).unsqueeze(0).permute(0, 3, 1, 2).float().to(device).contiguous()
+    y = _forward(m, x, t)
+    output = decode(task, y, [size], x.shape[2] // 2, x.shape[3], int(m.patch_size)).pictures()[0]
+    if spec["kind"] == "f64":
+        return output
+    Image.fromarray(output).save(out_path)
