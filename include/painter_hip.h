@@ -274,6 +274,41 @@ int64_t pa_conv3x3_wgrad_workspace_bytes(int batch, int Hi, int Wi);
 int pa_conv3x3_wgrad(int dtype, const void* dy3, const void* x_nhwc, float* dw /*f32 [64,64,3,3]*/, void* workspace,
                      int batch, int Hi, int Wi, hipStream_t stream);
 
+/* ---- decoder backward over the token rows the loss mask leaves live (bf16 256 x 256 / tile kernels only) ----
+ * The loss is taken over masked patches only, so the gradient dE that enters decoder_embed is exactly zero on every token whose patch and
+ * eight grid neighbours are unmasked (the tail is point-wise per pixel, the 3x3 conv has a one-pixel halo).  Nothing is read back to the host:
+ * every kernel takes the live-row count through a device pointer, grids and buffers are sized for all B*L rows.
+ *   pa_live_rows        token (b, i, j) is live when any mask byte of sample b in [i-1, i+1] x [j-1, j+1] is set (mask_batch_stride 0 = one
+ *                       [1, L] mask for all samples).  rowmap int32 [B*L]: compact index or -1; live int32 [B*L]: token by compact index,
+ *                       ascending; count int32 [1].  valid / the ignore rule are not consulted (they only zero more rows).
+ *   pa_conv3x3_dgrad_unshuffle_live   pa_conv3x3_dgrad_unshuffle into the compact dE, bf16 [roundup(B*L, 128), P*P*64]: token row t at row
+ *                       rowmap[t], nothing for dead tokens; rows [count, roundup(count, 128)) are zeroed, rows beyond are not touched.
+ *   pa_gather_rows      dst row r = src row live[r] (r < count), zeros for r in [count, roundup(count, 128)); src NULL: the zero rows only.
+ *                       Row pitches and the copied row length in bytes, multiples of 16; dst holds roundup(M, 128) rows.
+ *   pa_linear_dgrad_live   dx[live[r]] = dy[r] . W for r < count (dy: compact bf16 [>= count rows, N]; each row in the dense launch's K order:
+ *                       the same bits), exact zeros in the rows of dx whose rowmap entry is -1.  M = B*L rows of dx.
+ *   pa_linear_wgrad_live   dW f32 [N, K] = dy^T . x over the first roundup(count, 128) rows of the compact dy [M, N] / x [M, K] (M % 128 == 0;
+ *                       the rows between count and that bound must be zero in both); count = 0 writes a zero dW.
+ *   pa_colsum_live      pa_colsum over the first count rows.
+ *   pa_fill_dead_rows   zero the first row_bytes of the rows r of x (pitch_bytes apart, both % 16) with rowmap[r] < 0.
+ *   pa_decoder_live_ok  host-only: 1 when the kernels take this decoder (Kin = decoder_embed's input width) and the switch is on --
+ *                       pa_debug_set(17, v) / PAINTER_AMD_DECODER_ROWS: 0 default (on unless the environment says 0), 1 off, 2 on.
+ * Non-finite values in a dead region no longer reach the gradients through 0 * inf (the same caveat as the DropPath skip). */
+int pa_live_rows_max(void);       /* the largest B*L pa_live_rows takes (one workgroup, its flags in LDS) */
+int pa_live_rows(const unsigned char* mask, int mask_batch_stride, int* rowmap, int* live, int* count, int batch, int Hp, int Wp,
+                 hipStream_t stream);
+int pa_conv3x3_dgrad_unshuffle_live(const void* dy3, const void* wf, void* dE_compact, const int* rowmap, const int* count, int batch,
+                                    int Hp, int Wp, int P, hipStream_t stream);
+int pa_gather_rows(const void* src, int64_t src_row_bytes, void* dst, int64_t dst_row_bytes, int64_t row_bytes, const int* live,
+                   const int* count, int M, hipStream_t stream);
+int pa_linear_dgrad_live(const void* dy, int64_t lddy, const void* w, void* dx, int64_t lddx, const int* live, const int* rowmap,
+                         const int* count, int M, int N, int K, hipStream_t stream);
+int pa_linear_wgrad_live(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, const int* count, int M, int N, int K,
+                         hipStream_t stream);
+int pa_colsum_live(int dtype, const void* x, int64_t ld, int M, int N, float* out, void* workspace, const int* count, hipStream_t stream);
+int pa_fill_dead_rows(void* x, int64_t pitch_bytes, int64_t row_bytes, const int* rowmap, int M, hipStream_t stream);
+int pa_decoder_live_ok(int dtype, int batch, int Hp, int Wp, int P, int Kin);
+
 /* ---- forward_loss (models_painter.py:433-462; SegGPT models_seggpt.py:448-469) ----
  * out: f32 [2] = {loss, denominator}.  ignore_rule = 1 (Painter): samples whose unmasked de-normalised target sums
  * below 300 get valid := 0 IN PLACE (models_painter.py:444-448).  kind: 0 smoothl1(beta) 1 l1 2 l2 3 l1l2. */

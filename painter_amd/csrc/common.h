@@ -142,6 +142,14 @@ static inline bool drop_skip_on() {
     return g_drop_skip == 1 ? false : (g_drop_skip == 2 ? true : env != 0);
 }
 
+// pa_debug_set(17, v) / PAINTER_AMD_DECODER_ROWS: the decoder backward over the token rows the loss mask leaves live (pa_decoder_live_ok; the engine
+// asks it once per backward).  0 = default (on unless PAINTER_AMD_DECODER_ROWS=0), 1 = off (the dense decoder backward: what ran before), 2 = on
+inline int g_decoder_rows = 0;
+static inline bool decoder_rows_on() {
+    static const int env = [] { const char* v = getenv("PAINTER_AMD_DECODER_ROWS"); return v ? atoi(v) : 1; }();
+    return g_decoder_rows == 1 ? false : (g_decoder_rows == 2 ? true : env != 0);
+}
+
 // host-side launch counters of the attention entry points, by kernel family: [0..2] pa_attn_fwd on the generic (attn_fwd.hip) /
 // generation-2 (attn2.hip) / generation-3 (attn3.hip) kernels, [3..5] pa_attn_bwd likewise (pa_attn_launch_counts; the model-level tests
 // assert with them WHICH kernels a configuration ran on)

@@ -17,6 +17,7 @@
 #pragma once
 #include "common.h"
 #include <type_traits>
+#include <utility>
 
 namespace c64 {
 
@@ -67,6 +68,9 @@ template <class RowFn> DEVI void px_write_rows(const unsigned char* stg, int lan
 // x: NHWC [B, Hi, Wi, 64] bf16; w: [64 out][9 taps][64 in] bf16; Hi % 4 == 0, Wi % 64 == 0.
 // Epi(acc[2][2], 0, first pixel (linear index) of the wave's 64-pixel run, lane, 0): acc[bi][bj][r] = out channel bi*32 + acc_row(r),
 // pixel bj*32 + (lane & 31).
+// An epilogue may declare `bool dead_tile(b, y0, x0) const` (workgroup-uniform): the workgroup of a tile nobody needs leaves before its loads.
+template <class Epi, class = void> struct epi_dead_tile { static constexpr bool value = false; };
+template <class Epi> struct epi_dead_tile<Epi, std::void_t<decltype(std::declval<const Epi&>().dead_tile(0, 0, 0))>> { static constexpr bool value = true; };
 template <class Epi>
 __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w, Epi epi, int Hi, int Wi) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -77,6 +81,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const bf16* __rest
     t /= ntx;
     const int by = t % nty, b = t / nty;
     const int x0 = bx * TW, y0 = by * FTH;
+    if constexpr (epi_dead_tile<Epi>::value) {
+        if (epi.dead_tile(b, y0, x0)) return;
+    }
     const bf16* img = x + (size_t)b * Hi * Wi * 64;
 
     constexpr int HC = TW + 2, NCH = (FTH + 2) * HC * 8, NLD = (NCH + 255) / 256;

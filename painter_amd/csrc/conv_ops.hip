@@ -569,6 +569,76 @@ struct EpiUnshufPx {
         }
     }
 };
+// the same into the COMPACT dE of the live token rows (elementwise.hip, live_rows_kernel): a token's row goes to row rowmap[token], a dead
+// token's row -- exactly zero in the dense dE -- is not stored, and a workgroup whose 4 x 64 pixel tile touches dead tokens only does nothing.
+struct EpiUnshufPxLive {
+    bf16* out; const int* rowmap; int Hp, Wp, P;
+    DEVI bool dead_tile(int b, int y0, int x0) const {
+        const int h0 = y0 / P, h1 = (y0 + c64::FTH - 1) / P, w0 = x0 / P, w1 = (x0 + c64::TW - 1) / P;
+        for (int h = h0; h <= h1; ++h)
+            for (int w = w0; w <= w1; ++w)
+                if (rowmap[((size_t)b * Hp + h) * Wp + w] >= 0) return false;
+        return true;
+    }
+    DEVI void operator()(const f32x16 (&acc)[2][2], int, int jb, int lane, int, unsigned char* stg) const {
+        const int Wi = Wp * P, HW = Hp * P * Wi, g = lane >> 5;
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) {
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg)
+                    c64::px_stage4(stg + bj * 4096, lane & 31, bi * 32 + 8 * rg + 4 * g,
+                                   make_uint2(pack_bf16x2(acc[bi][bj][rg * 4], acc[bi][bj][rg * 4 + 1]), pack_bf16x2(acc[bi][bj][rg * 4 + 2], acc[bi][bj][rg * 4 + 3])));
+            const int p0 = jb + bj * 32;
+            c64::px_write_rows(stg + bj * 4096, lane, [&](int px) -> bf16* {
+                const int pix = p0 + px;
+                const int b = pix / HW, rem = pix % HW, y = rem / Wi, x = rem % Wi;
+                const int h = y / P, p = y % P, w = x / P, q = x % P;
+                const int m = rowmap[((size_t)b * Hp + h) * Wp + w];
+                if (m < 0) return nullptr;
+                return out + (size_t)m * (size_t)(P * P * CV_C) + (size_t)(p * P + q) * CV_C;
+            });
+        }
+    }
+};
+struct EpiUnshufLive {      // (the gather engine's orientation: EpiUnshuf<bf16> with the row looked up)
+    bf16* out; const int* rowmap; int Hp, Wp, P, M;
+    DEVI void operator()(const f32x16 (&acc)[2][2], int ib, int jb, int lane, int) const {
+        const int Wi = Wp * P, HW = Hp * P * Wi;
+        foreach_acc(acc, ib, jb, lane, [&](int i, int j, float v) {
+            if (i < M && j < CV_C) {
+                const int b = i / HW, rem = i % HW, y = rem / Wi, x = rem % Wi;
+                const int h = y / P, p = y % P, w = x / P, q = x % P;
+                const int m = rowmap[((size_t)b * Hp + h) * Wp + w];
+                if (m >= 0) out[(size_t)m * (size_t)(P * P * CV_C) + (size_t)(p * P + q) * CV_C + j] = from_f<bf16>(v);
+            }
+        });
+    }
+};
+extern "C" int pa_gather_rows(const void* src, int64_t src_row_bytes, void* dst, int64_t dst_row_bytes, int64_t row_bytes, const int* live,
+                              const int* count, int M, hipStream_t st);
+// dE_compact: bf16 [roundup(B*Hp*Wp, 128), P*P*64]; rows [0, *count) written, rows [*count, roundup(*count, 128)) zeroed, the rest untouched
+extern "C" int pa_conv3x3_dgrad_unshuffle_live(const void* dy3, const void* wf, void* dE_compact, const int* rowmap, const int* count, int batch,
+                                               int Hp, int Wp, int P, hipStream_t st) {
+    const int Hi = Hp * P, Wi = Wp * P, N = batch * Hi * Wi;
+    if (rowmap == nullptr || count == nullptr || P < 1 || batch < 1 || Hp < 1 || Wp < 1) return (int)hipErrorInvalidValue;
+    const int64_t rb = (int64_t)P * P * CV_C * 2;
+    int e = pa_gather_rows(nullptr, 0, dE_compact, rb, rb, nullptr, count, batch * Hp * Wp, st);
+    if (e) return e;
+    if (c64::ok(batch, Hi, Wi))
+        return c64::launch_tile((const bf16*)dy3, (const bf16*)wf, EpiUnshufPxLive{(bf16*)dE_compact, rowmap, Hp, Wp, P}, batch, Hi, Wi, st);
+    OpConv<bf16> A{(const bf16*)dy3, Hi, Wi, N};          // image sizes the tile kernel does not take: the gather engine, as the dense entry point
+    OpN<bf16> B{(const bf16*)wf, (size_t)9 * CV_C, CV_C, 0};
+    return launch_gemm<bf16, 4, 1>(A, B, EpiUnshufLive{(bf16*)dE_compact, rowmap, Hp, Wp, P, N}, N, CV_C, 9 * CV_C, 1, 1, st);
+}
+extern "C" int pa_live_rows_max(void);
+extern "C" int pa_decoder_live_ok(int dtype, int batch, int Hp, int Wp, int P, int Kin) {      // host-only: does the live-row route take this decoder?
+    if (!decoder_rows_on() || dtype != PA_BF16 || batch < 1 || Hp < 1 || Wp < 1 || P < 1) return 0;
+    const int M = batch * Hp * Wp, Mp = (M + 127) / 128 * 128, N = P * P * CV_C;
+    if (N % 256 || Kin % 256 || M > pa_live_rows_max()) return 0;
+    return (g256::ok(M, Kin, N, false, true, N, Kin) && g256::ok(N, Kin, Mp, true, true, N, Kin)) ? 1 : 0;
+}
 template <typename T>
 static int conv_dgrad_t(const T* dy3, const T* wf, T* dE, int Bn, int Hp, int Wp, int P, hipStream_t st) {
     const int Hi = Hp * P, Wi = Wp * P, N = Bn * Hi * Wi;

@@ -525,6 +525,98 @@ extern "C" int pa_decoder_tail_bwd_pointwise(int dtype, const float* dpred, cons
     return pa_slab_reduce(part, grads, TAILP, nb, TAILP, 0, st);
 }
 
+// ------------------------------------------------------------------------------- live token rows of the decoder backward
+// The loss is taken over masked patches only (models_painter.py:452-460), the decoder tail behind decoder_embed is point-wise per pixel and
+// the 3x3 convolution has a one-pixel halo: the gradient that enters decoder_embed is exactly zero on every token whose patch and eight grid
+// neighbours are all unmasked.  Token (b, i, j) is LIVE when any mask byte of sample b in [i-1, i+1] x [j-1, j+1] is set (no wrap across
+// grid rows, no leak across samples).  `valid` and the ignore rule are not consulted: they only zero more rows.
+//   rowmap[B*L]: compact index of a live token, -1 for a dead one;  live[B*L]: token by compact index, ascending;  count[0]: live tokens.
+// One workgroup.  Pass 1: token t = thread + 1024 k -- nine independent, coalesced mask loads each, the flag goes to LDS.  Pass 2: every
+// thread takes a run of consecutive tokens; the runs' counts are scanned through LDS (the first version did the mask loads inside the
+// runs, one dependent byte load after the other: 63 us at the head of the ViT-L backward).
+#define LIVE_NT 1024
+#define LIVE_MAX_ROWS 49152          // flags in LDS, one byte per token (beside the 8 KB of scan buffers)
+__global__ __launch_bounds__(LIVE_NT) void live_rows_kernel(const unsigned char* __restrict__ mask, int mbs, int* __restrict__ rowmap, int* __restrict__ live,
+                                                            int* __restrict__ count, int Bn, int Hp, int Wp) {
+    __shared__ int sc[2][LIVE_NT];
+    extern __shared__ unsigned char flag[];
+    const int L = Hp * Wp, n = Bn * L, per = (n + LIVE_NT - 1) / LIVE_NT;
+    for (int t = threadIdx.x; t < n; t += LIVE_NT) {
+        const int b = t / L, l = t - b * L, i = l / Wp, j = l - i * Wp;
+        const unsigned char* m = mask + (size_t)b * mbs;
+        unsigned int any = 0;
+#pragma unroll
+        for (int di = -1; di <= 1; ++di)
+#pragma unroll
+            for (int dj = -1; dj <= 1; ++dj) {
+                const int ii = i + di, jj = j + dj;
+                const bool in = ii >= 0 && ii < Hp && jj >= 0 && jj < Wp;
+                any |= in ? (unsigned int)m[in ? ii * Wp + jj : 0] : 0u;
+            }
+        flag[t] = any ? 1 : 0;
+    }
+    __syncthreads();
+    const int t0 = min(n, (int)threadIdx.x * per), t1 = min(n, t0 + per);
+    int mine = 0;
+    for (int t = t0; t < t1; ++t) mine += flag[t];
+    sc[0][threadIdx.x] = mine;
+    __syncthreads();
+    int cur = 0;
+    for (int d = 1; d < LIVE_NT; d <<= 1) {                 // inclusive scan, double-buffered
+        const int v = sc[cur][threadIdx.x] + ((int)threadIdx.x >= d ? sc[cur][threadIdx.x - d] : 0);
+        sc[cur ^ 1][threadIdx.x] = v;
+        cur ^= 1;
+        __syncthreads();
+    }
+    int at = sc[cur][threadIdx.x] - mine;
+    for (int t = t0; t < t1; ++t) {
+        if (flag[t]) { rowmap[t] = at; live[at] = t; ++at; }
+        else rowmap[t] = -1;
+    }
+    if (threadIdx.x == LIVE_NT - 1) count[0] = sc[cur][LIVE_NT - 1];
+}
+extern "C" int pa_live_rows_max(void) { return LIVE_MAX_ROWS; }
+extern "C" int pa_live_rows(const unsigned char* mask, int mask_batch_stride, int* rowmap, int* live, int* count, int batch, int Hp, int Wp,
+                            hipStream_t st) {
+    if (batch < 1 || Hp < 1 || Wp < 1 || (int64_t)batch * Hp * Wp > LIVE_MAX_ROWS) return (int)hipErrorInvalidValue;
+    const int n = batch * Hp * Wp;
+    PA_LAUNCH(live_rows_kernel, dim3(1), dim3(LIVE_NT), (size_t)((n + 15) & ~15), st, mask, mask_batch_stride, rowmap, live, count, batch, Hp, Wp);
+    LAUNCH_CHECK();
+}
+// Compact copy of the live rows: dst row r = src row live[r] for r < *count, zeros for r in [*count, roundup(*count, 128)); rows beyond that
+// are not touched.  src == NULL: only the zero rows (the padding of a buffer whose live rows somebody else writes).  16 bytes per thread.
+__global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restrict__ src, size_t lds16, uint4* __restrict__ dst, size_t ldd16, int row16,
+                                                          const int* __restrict__ live, const int* __restrict__ count) {
+    const int r = blockIdx.x, cnt = *count;
+    if (r >= ((cnt + 127) & ~127)) return;
+    if (r < cnt && src == nullptr) return;
+    const uint4* s = r < cnt ? src + (size_t)live[r] * lds16 : nullptr;
+    uint4* d = dst + (size_t)r * ldd16;
+    for (int c = threadIdx.x; c < row16; c += 256) d[c] = s ? s[c] : zero4();
+}
+extern "C" int pa_gather_rows(const void* src, int64_t src_row_bytes, void* dst, int64_t dst_row_bytes, int64_t row_bytes, const int* live,
+                              const int* count, int M, hipStream_t st) {
+    if (M < 1 || row_bytes % 16 || src_row_bytes % 16 || dst_row_bytes % 16 || row_bytes > dst_row_bytes || (src != nullptr && row_bytes > src_row_bytes))
+        return (int)hipErrorInvalidValue;
+    if (((uintptr_t)src | (uintptr_t)dst) & 15) return (int)hipErrorInvalidValue;
+    const int Mp = (M + 127) / 128 * 128;
+    PA_LAUNCH(gather_rows_kernel, dim3(Mp), dim3(256), 0, st, (const uint4*)src, (size_t)(src_row_bytes / 16), (uint4*)dst, (size_t)(dst_row_bytes / 16),
+              (int)(row_bytes / 16), live, count);
+    LAUNCH_CHECK();
+}
+// zero the rows of x whose rowmap entry is negative (the dead rows of a matrix whose live rows a scattering epilogue writes)
+__global__ __launch_bounds__(256) void fill_dead_rows_kernel(uint4* __restrict__ x, size_t pitch16, size_t row16, const int* __restrict__ rowmap) {
+    const int r = blockIdx.x;
+    if (rowmap[r] >= 0) return;
+    uint4* d = x + (size_t)r * pitch16;
+    for (size_t c = threadIdx.x; c < row16; c += 256) d[c] = zero4();
+}
+extern "C" int pa_fill_dead_rows(void* x, int64_t pitch_bytes, int64_t row_bytes, const int* rowmap, int M, hipStream_t st) {
+    if (M < 1 || row_bytes % 16 || pitch_bytes % 16 || row_bytes > pitch_bytes || ((uintptr_t)x & 15)) return (int)hipErrorInvalidValue;
+    PA_LAUNCH(fill_dead_rows_kernel, dim3(M), dim3(256), 0, st, (uint4*)x, (size_t)(pitch_bytes / 16), (size_t)(row_bytes / 16), rowmap);
+    LAUNCH_CHECK();
+}
+
 // ------------------------------------------------------------------------------- diagnostics: a stand-in for a collective's kernel
 // scratch[i] = 0.5 * (scratch[i] + src[i]), `passes` times, on exactly `nblocks` persistent workgroups of 256 threads: the HBM traffic
 // (12 B per element per pass) and CU footprint of a ring all-reduce step with `nblocks` channels, without touching the gradient it

@@ -143,6 +143,20 @@ template <typename OutT> struct Epi4Bias {
         else store8(out + (size_t)i * ldo + j, add4(a, c.a), add4(b, c.b));
     }
 };
+// data gradient over compact rows (decoder backward, live token rows): compact row i of the product goes to row live[i] of `out`; rows at and
+// beyond *count are dropped.  The values are Epi4Bias<bf16>'s without a bias (the same add of a zero: the same bits as the dense launch).
+struct Epi4Scatter {
+    bf16* out; size_t ldo; const int* live; const int* count; int M, N;
+    typedef EpiNone Col;
+    struct Row { int dst; };
+    DEVI Col col(int) const { return Col{}; }
+    DEVI Row row(int i, int) const { return Row{(i < M && i < *count) ? live[i] : -1}; }
+    DEVI void store(int, int j, float4 a, float4 b, const Col&, const Row& r, int) const {
+        if (r.dst < 0 || j >= N) return;
+        const float4 z = make_float4(0, 0, 0, 0);
+        store8(out + (size_t)r.dst * ldo + j, add4(a, z), add4(b, z));
+    }
+};
 struct Epi4BiasGelu {       // aux (optional): the 8-bit code of gelu'(pre) (see EpiBiasGelu), row pitch ld bytes
     unsigned char* aux; bf16* act; size_t ld; const float* bias; int M, N;
     typedef EpiCol8 Col;
@@ -344,7 +358,10 @@ extern "C" int pa_slab_reduce(const float* in, float* out, int64_t n, int nz, in
 
 // column sums of a [M, N] T matrix (bias gradients): stage 1 partial[chunk][N], stage 2 slab reduce (fixed order)
 // block = 32 column-lanes (8 consecutive columns each, one 16-byte load for bf16) x 8 row-lanes; 128 rows per block
-template <typename T> __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, size_t ld, int M, int N, int rows_per_chunk, float* __restrict__ part) {
+// mcount (optional): the number of rows to sum, on the device (<= M, which sizes the grid); chunks behind it write zero partial rows
+template <typename T> __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, size_t ld, int M, int N, int rows_per_chunk, float* __restrict__ part,
+                                                                           const int* __restrict__ mcount = nullptr) {
+    if (mcount != nullptr) M = min(M, *mcount);
     const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
     const int c0 = (blockIdx.x * 32 + cl) * 8;
     const int r0 = blockIdx.y * rows_per_chunk, r1 = min(M, r0 + rows_per_chunk);
@@ -380,18 +397,25 @@ extern "C" int64_t pa_colsum_workspace_bytes(int M, int N) {
     const int rpc = colsum_rows_per_chunk(M), chunks = (M + rpc - 1) / rpc;
     return (int64_t)chunks * N * sizeof(float);
 }
-extern "C" int pa_colsum(int dtype, const void* x, int64_t ld, int M, int N, float* out, void* workspace, hipStream_t st) {
+static int colsum_t(int dtype, const void* x, int64_t ld, int M, int N, float* out, void* workspace, const int* mcount, hipStream_t st) {
     if (N % 8 || ld % 8) return (int)hipErrorInvalidValue;
     const int rpc = colsum_rows_per_chunk(M), chunks = (M + rpc - 1) / rpc;
     float* part = reinterpret_cast<float*>(workspace);
     dim3 grid((N + 255) / 256, chunks);
     if (dtype == PA_BF16)
-        PA_LAUNCH(colsum_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)x, (size_t)ld, M, N, rpc, part);
+        PA_LAUNCH(colsum_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)x, (size_t)ld, M, N, rpc, part, mcount);
     else
-        PA_LAUNCH(colsum_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (size_t)ld, M, N, rpc, part);
+        PA_LAUNCH(colsum_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (size_t)ld, M, N, rpc, part, mcount);
     int e = (int)hipGetLastError();
     if (e) return e;
     return pa_slab_reduce(part, out, N, chunks, N, 0, st);
+}
+extern "C" int pa_colsum(int dtype, const void* x, int64_t ld, int M, int N, float* out, void* workspace, hipStream_t st) {
+    return colsum_t(dtype, x, ld, M, N, out, workspace, nullptr, st);
+}
+extern "C" int pa_colsum_live(int dtype, const void* x, int64_t ld, int M, int N, float* out, void* workspace, const int* count, hipStream_t st) {
+    if (count == nullptr || M < 1) return (int)hipErrorInvalidValue;
+    return colsum_t(dtype, x, ld, M, N, out, workspace, count, st);
 }
 
 // ------------------------------------------------------------------------------- linear forward
@@ -593,12 +617,33 @@ extern "C" int pa_linear_wgrad(int dtype, const void* dy, int64_t lddy, const vo
     return linear_wgrad_t<float>((const float*)dy, lddy, (const float*)x, ldx, dw, (float*)workspace, M, N, K, st);
 }
 
+// ------------------------------------------------------------------------------- decoder backward over the live token rows
+// (include/painter_hip.h, "live rows").  bf16 256 x 256 kernel only: a shape it does not take is an error, the caller
+// asks pa_decoder_live_ok() first and stays on the dense entry points otherwise.
+extern "C" int pa_fill_dead_rows(void* x, int64_t pitch_bytes, int64_t row_bytes, const int* rowmap, int M, hipStream_t st);
+extern "C" int pa_linear_dgrad_live(const void* dy, int64_t lddy, const void* w, void* dx, int64_t lddx, const int* live, const int* rowmap,
+                                    const int* count, int M, int N, int K, hipStream_t st) {
+    if (live == nullptr || rowmap == nullptr || count == nullptr || M < 8 || K % 8 || lddx % 8) return (int)hipErrorInvalidValue;
+    if (!g256::ok(M, K, N, false, true, lddy, K)) return (int)hipErrorInvalidValue;
+    int e = pa_fill_dead_rows(dx, lddx * 2, (int64_t)K * 2, rowmap, M, st);
+    if (e) return e;
+    return g256::launch_live<false, true>((const bf16*)dy, lddy, (const bf16*)w, K, Epi4Scatter{(bf16*)dx, (size_t)lddx, live, count, M, K}, M, K, N, count, st);
+}
+extern "C" int pa_linear_wgrad_live(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, const int* count, int M, int N, int K,
+                                    hipStream_t st) {
+    if (count == nullptr || M < 128 || M % 128) return (int)hipErrorInvalidValue;
+    if (!wgrad_fast(PA_BF16, M, N, K) || !g256::ok(N, K, M, true, true, lddy, ldx)) return (int)hipErrorInvalidValue;
+    return g256::launch_live<true, true>((const bf16*)dy, lddy, (const bf16*)x, ldx, Epi4Slab{dw, (size_t)K, 0, N, K}, N, K, M, count, st);
+}
+
 extern "C" int pa_abi_version(void) { return PA_ABI_VERSION; }
 // knobs: 0-4 gemm256 (g256::g_dbg), 5 the G256_ILV_AB schedule override (experiment builds), 6 rel-pos splits, 7 fused rel-pos gradient,
 // 8 light attention workgroups last, 9 conv3x3 weight-gradient groups, 10 LayerNorm-backward variant (round 5 shared index 5 with the ILV
-// override: tools that swept one silently switched the other), 16 DropPath skipping (common.h, g_drop_skip)
+// override: tools that swept one silently switched the other), 16 DropPath skipping (common.h, g_drop_skip), 17 decoder backward over the live rows
+// (common.h, g_decoder_rows)
 extern "C" int pa_debug_get(int which) {
     if (which == 16) return g_drop_skip;
+    if (which == 17) return g_decoder_rows;
     if (which < 0 || which > 15) return -1;
     if (which == 9) return g_conv_wgrad_groups;
     if (which == 10) return g_ln_bwd_variant;
@@ -610,6 +655,7 @@ extern "C" int pa_debug_get(int which) {
 }
 extern "C" int pa_debug_set(int which, int value) {
     if (which == 16) { g_drop_skip = value; return 0; }
+    if (which == 17) { g_decoder_rows = value; return 0; }
     if (which < 0 || which > 15) return (int)hipErrorInvalidValue;
     if (which < 8) g256::g_dbg[which] = value;
     if (which == 9) g_conv_wgrad_groups = value;

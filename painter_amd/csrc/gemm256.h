@@ -168,11 +168,20 @@ constexpr int BM_HALF = 128;
 // ever (measured: no gain at all).  So the KEPT row panels of a region (full tiles, half tiles) are numbered densely and the XCD runs and
 // patches are laid over them alone (the first kept * tiles_n workgroups); the workgroups behind them take the skipped tiles, whose
 // epilogue-only work is spread by the dispatcher.  The ranges of skipped panels come from one walk over the factor vector (scalar loads).
-template <bool AMM, bool BMM, int ILV, class Epi, bool SHORT = false, bool MIXED = false, bool SKIP = false>
+// LIVE (decoder backward over the token rows the loss mask leaves live): one dimension of the launch is known on the device only --
+// *live_count, read once in front of everything else; the grid is sized for the largest count.
+//   K-major A (data gradient over compact rows): M = *live_count.  The row tiles [0, ceil(M / 256)) are the launch: the XCD runs and patches are
+//     laid over them alone, the workgroups behind them return at once.  Uniform 256-row tiles (the tile plan is a host decision); A rows at
+//     and beyond M are never read (the row clamp of src_off) and the epilogue functor drops their results.
+//   M-major A (weight gradient over compact rows, no K split): the contraction runs over roundup(*live_count, 128) rows = an even number of K
+//     tiles; the rows between the count and that bound must be zero in BOTH operands.  A count of 0 runs no K loop and stores the zero accumulator.
+// Nothing changes inside the K loop, and LIVE = false compiles to the kernel it was before.
+template <bool AMM, bool BMM, int ILV, class Epi, bool SHORT = false, bool MIXED = false, bool SKIP = false, bool LIVE = false>
 __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag, uint32_t lda, const bf16* __restrict__ Bg,
                                                       uint32_t ldb, Epi epi, int M, int N, int ktiles, int ktiles_per_split,
                                                       int tiles_n, int stagger, int order, int nfull, int patch,
-                                                      const float* __restrict__ rowskip, int rps) {
+                                                      const float* __restrict__ rowskip, int rps, const int* __restrict__ live_count) {
+    static_assert(!(LIVE && (SHORT || MIXED || SKIP)), "a device-side count goes with uniform 256-row tiles");
     static_assert(!(SHORT && AMM), "the 224-row tile is built for a K-major A operand");
     static_assert(!(SKIP && AMM), "row tiles are skipped only for a K-major A operand");
     static_assert(!(MIXED && (AMM || SHORT)), "half tiles are built for a K-major A operand and 256-row full tiles");
@@ -194,6 +203,15 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
     // (MIXED: the full tiles and the half tiles are two regions of the grid, each ordered on its own)
     const bool htile = MIXED && (int)blockIdx.x >= nfull * tiles_n;
     int nwg = MIXED ? (htile ? (int)gridDim.x - nfull * tiles_n : nfull * tiles_n) : (int)gridDim.x;
+    if constexpr (LIVE) {
+        if constexpr (AMM) {
+            ktiles = ktiles_per_split = min(ktiles, ((*live_count + 127) >> 7) * 2);      // (never beyond the rows the operands hold)
+        } else {
+            M = min(M, *live_count);
+            nwg = ((M + BM - 1) / BM) * tiles_n;
+            if ((int)blockIdx.x >= nwg) return;
+        }
+    }
     const int bid = htile ? (int)blockIdx.x - nfull * tiles_n : (int)blockIdx.x;
     // SKIP: f(a, b) for every maximal range [a, b) of this region's row panels that lie wholly in dropped samples, ascending.  `dmask`: bit s =
     // sample s is dropped (one vector load + ballot per wave: a scalar walk over the factors cost ~5 us per workgroup); with nobody dropped --
@@ -287,6 +305,7 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
     const bool blk3 = !(SHORT && wr == 1);          // does this wave own the fourth 32-row block of its 128 rows?  (wave-uniform)
     const int kt0 = split * ktiles_per_split;
     const int nt = min(ktiles - kt0, ktiles_per_split);
+    const bool empty = LIVE && AMM && nt == 0;      // (workgroup-uniform; a constant without LIVE)
     // ---- DMA sources: 8 per lane (4 units x 2), as byte offsets from a wave-uniform, per-tile advancing base
     uint32_t oa[2][2], ob[2][2];
 #pragma unroll
@@ -493,7 +512,7 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
             }
         }
     }
-    if (!ran_half && !skipped) {
+    if (!ran_half && !skipped && !empty) {
         // ---- prologue: tile 0 entirely, plus a0/b0 of tile 1   (nt is even and >= 2: see launch())
         stage_a(0, 0, 0);
         stage_b(0, 0, 0);
@@ -510,7 +529,7 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
             tile_body(I1{}, T + 1);
         }
     }
-    if (wr == 0 && !ran_half && !skipped) bar();       // (the full loop's half-phase offset between the wave rows; the half-tile loop runs in step)
+    if (wr == 0 && !ran_half && !skipped && !empty) bar();       // (the full loop's half-phase offset between the wave rows; the half-tile loop runs in step)
     wait_vm<0>();          // the clamped tail DMAs must have landed before this workgroup's LDS is handed on
 
     // ---- epilogue.  A lane owns one output row of each 32x32 block; storing from there would touch 32 cache lines per
@@ -586,9 +605,9 @@ static inline int per_split(int ktiles, int nsplit) {
     int per = (ktiles + nsplit - 1) / nsplit;
     return per + (per & 1);
 }
-template <bool AMM, bool BMM, int ILV, bool SHORT, class Epi, bool MIXED = false, bool SKIP = false>
+template <bool AMM, bool BMM, int ILV, bool SHORT, class Epi, bool MIXED = false, bool SKIP = false, bool LIVE = false>
 static int launch_ilv(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi epi, int M, int N, int K, int nsplit, hipStream_t st, int nfull = 0,
-                      const float* rowskip = nullptr, int rps = 1);
+                      const float* rowskip = nullptr, int rps = 1, const int* live_count = nullptr);
 #ifndef G256_ILV_DEFAULT
 #define G256_ILV_DEFAULT 2     // round 3 (tools/gemm_ilv_ab.py, MI355X): 2 is 4-15 % faster than 0 on the forward GEMMs, 4-6 % on the data gradients,
 #endif                         // 2 % on the weight gradients, bit-identical results; 1 = 0.  In the training step the gain shrinks to ~1 % (DVFS)
@@ -660,10 +679,16 @@ static int launch_skip(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi
     if (tp.is_short) return launch_ilv<false, BMM, G256_ILV_DEFAULT, true, Epi, false, true>(A, lda, B, ldb, epi, M, N, K, 1, st, 0, rowskip, rps);
     return launch_ilv<false, BMM, G256_ILV_DEFAULT, false, Epi, false, true>(A, lda, B, ldb, epi, M, N, K, 1, st, 0, rowskip, rps);
 }
-template <bool AMM, bool BMM, int ILV, bool SHORT, class Epi, bool MIXED, bool SKIP>
+// Launch with a device-side count (gemm256_kernel, LIVE).  K-major A: M = the largest row count (the grid); M-major A: K = the largest
+// contraction length, a multiple of 128 (the operands hold that many rows), un-split.
+template <bool AMM, bool BMM, class Epi>
+static int launch_live(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi epi, int M, int N, int K, const int* live_count, hipStream_t st) {
+    return launch_ilv<AMM, BMM, G256_ILV_DEFAULT, false, Epi, false, false, true>(A, lda, B, ldb, epi, M, N, K, 1, st, 0, nullptr, 1, live_count);
+}
+template <bool AMM, bool BMM, int ILV, bool SHORT, class Epi, bool MIXED, bool SKIP, bool LIVE>
 static int launch_ilv(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi epi, int M, int N, int K, int nsplit, hipStream_t st, int nfull,
-                      const float* rowskip, int rps) {
-    auto kern = gemm256_kernel<AMM, BMM, ILV, Epi, SHORT, MIXED, SKIP>;
+                      const float* rowskip, int rps, const int* live_count) {
+    auto kern = gemm256_kernel<AMM, BMM, ILV, Epi, SHORT, MIXED, SKIP, LIVE>;
     static bool attr_done = false;
     if (!attr_done) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
@@ -679,7 +704,7 @@ static int launch_ilv(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi 
     const int splits = (ktiles + per - 1) / per;      // every split gets an even number (>= 2) of tiles
     if (g_dbg[1]) epi.M = 0;
     PA_LAUNCH(kern, dim3(tiles_m * tiles_n, splits), dim3(NT), LDS_BYTES, st, A, (uint32_t)lda, B, (uint32_t)ldb, epi, M, N,
-              ktiles, per, tiles_n, g_dbg[0], g_dbg[2], nfull, g_misc_knob[0] > 0 ? g_misc_knob[0] : env_patch, rowskip, rps);
+              ktiles, per, tiles_n, g_dbg[0], g_dbg[2], nfull, g_misc_knob[0] > 0 ? g_misc_knob[0] : env_patch, rowskip, rps, live_count);
     return (int)hipGetLastError();
 }
 // row tiles of the launch launch<AMM = false>(...) makes for this shape (partial rows of a column-sum epilogue = 2 x this)

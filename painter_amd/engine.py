@@ -386,35 +386,36 @@ class HotPath:
 
         filt = getattr(self, "side_filter", None)          # diagnostics: {"dec","fc2","fc1","proj","qkv"} subsets, "nocolsum", "nowgrad"
 
-        def param_grads(wname, bname, dy, x, bout=None):
+        def param_grads(wname, bname, dy, x, bout=None, wgrad=ops.linear_wgrad, colsum=ops.colsum):
             """G[wname] = dy^T.x, G[bname] = colsum(dy) (into `bout`, a slice of the block's flat small-gradient buffer, when given)
-            -- on the side stream when enabled.  Frozen parameters (outside `want`) cost nothing here."""
+            -- on the side stream when enabled.  Frozen parameters (outside `want`) cost nothing here.
+            wgrad(dy, x) / colsum(dy, out=): the two computations (the decoder's live-row route passes its own)."""
             if not need(wname) and (bname in G or not need(bname)):
                 return
             if not need(wname) or not need(bname):          # partly frozen layer: only what is asked for, in the caller's stream order
                 def one():
                     if need(wname):
-                        G[wname] = ops.linear_wgrad(dy, x)
+                        G[wname] = wgrad(dy, x)
                     if bname not in G and need(bname):
-                        G[bname] = ops.colsum(dy, out=bout)
+                        G[bname] = colsum(dy, out=bout)
                 on_side(one, *[t for t in (dy, x if need(wname) else None) if t is not None])
                 return
             tag = "dec" if wname.startswith("decoder") else wname.split(".")[-2]
             if side is None or (filt is not None and tag not in filt):
-                G[wname] = ops.linear_wgrad(dy, x)
+                G[wname] = wgrad(dy, x)
                 if bname not in G:                 # (fc2 / proj biases: already summed by the LayerNorm backward that produced dy)
-                    G[bname] = ops.colsum(dy, out=bout)
+                    G[bname] = colsum(dy, out=bout)
                 return
             if filt is not None and "nocolsum" in filt:
-                G[bname] = ops.colsum(dy, out=bout)
+                G[bname] = colsum(dy, out=bout)
             if filt is not None and "nowgrad" in filt:
-                G[wname] = ops.linear_wgrad(dy, x)
+                G[wname] = wgrad(dy, x)
             side.wait_stream(main)                 # dy (and x) are enqueued on main
             with torch.cuda.stream(side):
                 if wname not in G:
-                    G[wname] = ops.linear_wgrad(dy, x)
+                    G[wname] = wgrad(dy, x)
                 if bname not in G:
-                    G[bname] = ops.colsum(dy, out=bout)
+                    G[bname] = colsum(dy, out=bout)
             dy.record_stream(side)                 # the allocator must not hand these out again before the side stream is done
             x.record_stream(side)
             if _DBG_KEEP:
@@ -472,11 +473,30 @@ class HotPath:
                 lambda: (ops.conv3x3_wgrad(dy3, S.E) if need("decoder_pred.0.weight") else None,
                          ops.colsum(dy3.view(npix, c.dec)) if need("decoder_pred.0.bias") else None),
                 *[t for t in (dy3, S.E) if t is not None])
-        dE = ops.conv3x3_dgrad_unshuffle(dy3, S.wf, B, c.Hp, c.Wp, c.P)
-        del dy3
-        param_grads("decoder_embed.weight", "decoder_embed.bias", dE, S.concat)
-        dconcat = ops.linear_dgrad(dE, self.w("decoder_embed.weight", P))
-        tr("dE", dE); tr("dconcat", dconcat)
+        w_de = self.w("decoder_embed.weight", P)
+        if dpatch is None and ops.decoder_live_ok(T, B, c.Hp, c.Wp, c.P, w_de.shape[1]):
+            # The loss touches masked patches only: dE is exactly zero on every token without a masked patch in its 3 x 3 neighbourhood.  The
+            # conv's data gradient writes the live rows compacted, both decoder_embed GEMMs and the bias sum run over those rows alone (their
+            # number stays on the device), and the data gradient is scattered back into a dconcat whose dead rows are zero.
+            # A gradient on pred_patch (dpatch) makes every row live: that case, the fp32 build and ragged shapes stay dense.
+            rowmap, live, count = ops.live_rows(S.mask, B, c.Hp, c.Wp)
+            dE = ops.conv3x3_dgrad_unshuffle_live(dy3, S.wf, rowmap, count, B, c.Hp, c.Wp, c.P)
+            del dy3
+            param_grads("decoder_embed.weight", "decoder_embed.bias", dE, S.concat,
+                        wgrad=lambda dy, x: ops.linear_wgrad(dy, x, live=(live, count)),
+                        colsum=lambda dy, out=None: ops.colsum_live(dy, count, out=out))
+            if side is not None:
+                count.record_stream(side)          # (rowmap / live / count share one allocation; the side stream's GEMM and sums read it)
+            dconcat = ops.linear_dgrad(dE, w_de, live=(live, rowmap, count))
+            if _DBG_TRACE:
+                tr("dE", dE[:int(count.item())])
+        else:
+            dE = ops.conv3x3_dgrad_unshuffle(dy3, S.wf, B, c.Hp, c.Wp, c.P)
+            del dy3
+            param_grads("decoder_embed.weight", "decoder_embed.bias", dE, S.concat)
+            dconcat = ops.linear_dgrad(dE, w_de)
+            tr("dE", dE)
+        tr("dconcat", dconcat)
         del dE
         ready(["decoder_embed.weight", "decoder_embed.bias"])
         ready([n for n in G if n.startswith("decoder_pred.")])

@@ -122,12 +122,25 @@ def linear_pixshuf(x, w, bias, batch, Hp, Wp, P, C):
     return out
 
 
-def linear_dgrad(dy, w, gelu_aux=None, out=None, colsum_out=None, *, rowskip=None, rows_per_sample=1):
+def linear_dgrad(dy, w, gelu_aux=None, out=None, colsum_out=None, *, rowskip=None, rows_per_sample=1, live=None):
     """dX[M,K] = dY[M,N] . W[N,K]  (* gelu'(pre) when gelu_aux, the second result of linear_gelu() in the same dtype, is given).
     colsum_out (f32 [K], optional): receives the column sums of dX as stored -- the bias gradient of the layer whose dY dX is -- from the
     GEMM's epilogue (bf16 fast path) instead of a separate pass.
     rowskip (f32 [M / rows_per_sample]): the DropPath factors of the branch; dY rows of a sample whose factor is 0 are zero, row tiles
-    that lie wholly in such samples are not computed (dX rows zero)."""
+    that lie wholly in such samples are not computed (dX rows zero).
+    live = (live, rowmap, count) of live_rows(): dY is the COMPACT matrix of the live rows (>= rowmap.numel() rows) and dX [rowmap.numel(), K]
+    gets dX[live[r]] = dY[r] . W for r < count, zeros in the dead rows (include/painter_hip.h, pa_linear_dgrad_live)."""
+    if live is not None:
+        assert gelu_aux is None and colsum_out is None and rowskip is None
+        lv, rowmap, count = live
+        M, N, K = rowmap.numel(), dy.shape[1], w.shape[1]
+        _req(dy, torch.bfloat16); _req(w, torch.bfloat16)
+        assert w.is_contiguous() and w.shape[0] == N and dy.shape[0] >= M
+        if out is None:
+            out = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
+        check(lib.pa_linear_dgrad_live(p(dy), dy.stride(0), p(w), p(out), out.stride(0), p(lv), p(rowmap), p(count), M, N, K, stream()),
+              "pa_linear_dgrad_live")
+        return out
     M, N = dy.shape
     K = w.shape[1]
     T = dy.dtype
@@ -150,8 +163,21 @@ def linear_dgrad(dy, w, gelu_aux=None, out=None, colsum_out=None, *, rowskip=Non
     return out
 
 
-def linear_wgrad(dy, x, out=None):
-    """dW[N,K] = dY[M,N]^T . X[M,K] in fp32."""
+def linear_wgrad(dy, x, out=None, *, live=None):
+    """dW[N,K] = dY[M,N]^T . X[M,K] in fp32.
+    live = (live, count) of live_rows(): dY is the COMPACT matrix of the live rows ([roundup(M, 128), N], zero between count and
+    roundup(count, 128)); the live rows of X are gathered into the same form and the contraction runs over them alone."""
+    if live is not None:
+        lv, count = live
+        xc = gather_rows(x, lv, count)
+        Mp, N = dy.shape
+        K = x.shape[1]
+        _req(dy, torch.bfloat16); _req(xc, torch.bfloat16)
+        assert xc.shape[0] == Mp and Mp % 128 == 0
+        if out is None:
+            out = torch.empty((N, K), dtype=torch.float32, device=dy.device)
+        check(lib.pa_linear_wgrad_live(p(dy), dy.stride(0), p(xc), xc.stride(0), p(out), p(count), Mp, N, K, stream()), "pa_linear_wgrad_live")
+        return out
     M, N = dy.shape
     K = x.shape[1]
     T = dy.dtype
@@ -170,6 +196,83 @@ def colsum(x, out=None):
         out = torch.empty((N,), dtype=torch.float32, device=x.device)
     ws = workspace(lib.pa_colsum_workspace_bytes(M, N), x.device)
     check(lib.pa_colsum(code(x.dtype), p(x), x.stride(0), M, N, p(out), p(ws), stream()), "pa_colsum")
+    return out
+
+
+# ------------------------------------------------------------------------------------------- decoder backward over the live token rows
+def decoder_rows(mode=None):
+    """The run-time switch of the live-row decoder backward (pa_debug_set knob 17): 0 default (on unless PAINTER_AMD_DECODER_ROWS=0), 1 off,
+    2 on.  -> the value found; sets `mode` when given."""
+    old = int(lib.pa_debug_get(17))
+    if mode is not None:
+        check(lib.pa_debug_set(17, int(mode)), "pa_debug_set")
+    return old
+
+
+def decoder_live_ok(T, batch, Hp, Wp, P, Kin):
+    """Do the live-row kernels take this decoder (bf16 build, shapes of the 256 x 256 GEMM and the conv tile kernel), and is the switch on?"""
+    return T == torch.bfloat16 and bool(lib.pa_decoder_live_ok(code(T), batch, Hp, Wp, P, Kin))
+
+
+def live_rows(mask_u8, batch, Hp, Wp):
+    """mask_u8 [B, L] or [1, L] -> (rowmap int32 [B*L]: compact index or -1, live int32 [B*L]: token by compact index, count int32 [1]):
+    the tokens with a masked patch in their 3 x 3 grid neighbourhood (include/painter_hip.h, pa_live_rows).  Nothing comes back to the host."""
+    n = batch * Hp * Wp
+    assert mask_u8.dtype in (torch.uint8, torch.bool) and mask_u8.is_cuda and mask_u8.stride(-1) == 1 and mask_u8.shape[-1] == Hp * Wp
+    assert mask_u8.shape[0] in (1, batch)
+    mbs = 0 if mask_u8.shape[0] == 1 else mask_u8.stride(0)
+    buf = torch.empty((2 * n + 1,), dtype=torch.int32, device=mask_u8.device)
+    rowmap, live, count = buf[:n], buf[n:2 * n], buf[2 * n:]
+    check(lib.pa_live_rows(p(mask_u8), mbs, p(rowmap), p(live), p(count), batch, Hp, Wp, stream()), "pa_live_rows")
+    return rowmap, live, count
+
+
+def padded_rows(n):
+    return (n + 127) // 128 * 128
+
+
+def conv3x3_dgrad_unshuffle_live(dy3, wf, rowmap, count, batch, Hp, Wp, P, out=None):
+    """-> the compact dE, bf16 [roundup(B*L, 128), P*P*64]: rows [0, count) = the live token rows in order, [count, roundup(count, 128)) zero,
+    the rest unwritten."""
+    assert dy3.dtype == torch.bfloat16
+    if out is None:
+        out = torch.empty((padded_rows(batch * Hp * Wp), P * P * 64), dtype=dy3.dtype, device=dy3.device)
+    assert out.shape == (padded_rows(batch * Hp * Wp), P * P * 64) and out.is_contiguous()
+    check(lib.pa_conv3x3_dgrad_unshuffle_live(p(dy3), p(wf), p(out), p(rowmap), p(count), batch, Hp, Wp, P, stream()),
+          "pa_conv3x3_dgrad_unshuffle_live")
+    return out
+
+
+def gather_rows(x, live, count, out=None):
+    """x [M, N] -> compact [roundup(M, 128), N]: row r = x[live[r]] for r < count, zeros up to roundup(count, 128), the rest unwritten."""
+    M, N = x.shape
+    _req(x)
+    if out is None:
+        out = torch.empty((padded_rows(M), N), dtype=x.dtype, device=x.device)
+    es = x.element_size()
+    check(lib.pa_gather_rows(p(x), x.stride(0) * es, p(out), out.stride(0) * es, N * es, p(live), p(count), M, stream()), "pa_gather_rows")
+    return out
+
+
+def linear_wgrad_live(dy, x, count, out=None):
+    """dW[N, K] = dY^T . X over the first roundup(count, 128) rows of the compact operands (both zero between count and that bound)."""
+    M, N = dy.shape
+    K = x.shape[1]
+    _req(dy, torch.bfloat16); _req(x, torch.bfloat16)
+    assert x.shape[0] == M and M % 128 == 0
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float32, device=dy.device)
+    check(lib.pa_linear_wgrad_live(p(dy), dy.stride(0), p(x), x.stride(0), p(out), p(count), M, N, K, stream()), "pa_linear_wgrad_live")
+    return out
+
+
+def colsum_live(x, count, out=None):
+    """Column sums of the first count rows of x."""
+    M, N = x.shape
+    if out is None:
+        out = torch.empty((N,), dtype=torch.float32, device=x.device)
+    ws = workspace(lib.pa_colsum_workspace_bytes(M, N), x.device)
+    check(lib.pa_colsum_live(code(x.dtype), p(x), x.stride(0), M, N, p(out), p(ws), p(count), stream()), "pa_colsum_live")
     return out
 
 
