@@ -11,6 +11,10 @@ LIB_PATH = os.environ.get("PAINTER_AMD_LIB") or os.path.join(HERE, "lib", "libpa
 
 PA_F32, PA_BF16 = 0, 1
 EPI_BIAS, EPI_BIAS_F32, EPI_BIAS_GELU, EPI_BIAS_RESID = 0, 1, 2, 3
+# indices of pa_debug_set / pa_debug_get (csrc/common.h: enum Knob; 13 and 15 are free)
+(KNOB_G256_STAGGER, KNOB_G256_NOSTORE, KNOB_G256_ORDER, KNOB_WGRAD_TARGET, KNOB_G256_SHORT_TILES, KNOB_G256_ILV, KNOB_RELPOS_SPLITS,
+ KNOB_ATTN3_FUSE, KNOB_ATTN_LIGHT_LAST, KNOB_CONV_WGRAD_GROUPS, KNOB_LN_BWD_VARIANT, KNOB_G256_PATCH, KNOB_G256_MIXED) = range(13)
+KNOB_G256_MIXED_NFULL, KNOB_DROP_SKIP, KNOB_DECODER_ROWS, KNOB_COUNT = 14, 16, 17, 18
 
 _CT = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "hipStream_t": ctypes.c_void_p}
 

@@ -883,8 +883,8 @@ static int a3_xcd_map_on() {
         const char* l = getenv("PA_ATTN_LIGHT_LAST");
         return ((e ? atoi(e) : 1) ? 1 : 0) | ((l ? atoi(l) : 0) ? 2 : 0);
     }();
-    if (g_attn_light_last == 1) return v & 1;
-    if (g_attn_light_last == 2) return v | 2;
+    if (g_knob[KNOB_ATTN_LIGHT_LAST] == 1) return v & 1;
+    if (g_knob[KNOB_ATTN_LIGHT_LAST] == 2) return v | 2;
     return v;
 }
 
@@ -935,7 +935,7 @@ __global__ __launch_bounds__(256) void relpos_part_reduce_kernel(const float4* _
 extern "C" int pa_slab_reduce(const float* in, float* out, int64_t n, int nz, int64_t stride, int accumulate, hipStream_t st);
 static int a3_fuse_on() {
     static const int v = [] { const char* e = getenv("PA_ATTN3_FUSE_RELPOS"); return e ? atoi(e) : 1; }();
-    return g_attn3_fuse == 1 ? 0 : (g_attn3_fuse == 2 ? 1 : v);
+    return g_knob[KNOB_ATTN3_FUSE] == 1 ? 0 : (g_knob[KNOB_ATTN3_FUSE] == 2 ? 1 : v);
 }
 // workgroups of the dQ launch = partial slots
 static int a3_blocks(int L) { return (L / 32 + a3::NW - 1) / a3::NW; }

@@ -114,40 +114,43 @@ DEVI float wave_max(float v) {
     return v;
 }
 
-// tuning knob shared across translation units: K splits of the rel-pos table-gradient GEMM (0 = built-in default; pa_debug_set(6, n)).
-// The engine asks for 4 when that GEMM runs on the side stream beside the data-gradient chain (fewer, longer workgroups: 54.54 -> 54.35
-// ms/step), the stand-alone optimum is 16.
-inline int g_relpos_splits = 0;
-// pa_debug_set(7, v): 0 = default (fused rel-pos table gradient in the generation-3 dQ kernel unless PA_ATTN3_FUSE_RELPOS=0), 1 = off, 2 = on
-inline int g_attn3_fuse = 0;
-// pa_debug_set(8, v): 0 = default (light attention workgroups NOT dispatched last unless PA_ATTN_LIGHT_LAST=1; round 5), 1 = off, 2 = on
-inline int g_attn_light_last = 0;
-
-// pa_debug_set(10, v) (round 5 shared index 5 with gemm256's ILV schedule override): LayerNorm backward variant: 0 = default (rows split over the 4 waves of a workgroup wherever D >= 1024), 1 = one wave per
-// row everywhere (the kernel of rounds 1 - 4; still what narrow D runs)
-inline int g_ln_bwd_variant = 0;
-
-// pa_debug_set(9, n): tests only -- cap on the number of workgroups of the conv3x3 weight-gradient kernel (0 = the product's 512): with a small
-// cap every workgroup walks many tiles, through both ring phases and across column-strip boundaries, at test sizes
-inline int g_conv_wgrad_groups = 0;
-// pa_debug_set(11 .. 15, v): round-6 experiment knobs, read where they are named: [0] = 11 gemm256 tile patch per XCD (0 = default,
-// TR * 16 + TC otherwise), [1] = 12 mixed 224-row + 128-row tiles for the multi-round GEMMs (0 = default on, 1 = off), [2] = 13, [3] = 14, [4] = 15 free
-inline int g_misc_knob[5] = {0, 0, 0, 0, 0};
-
-// pa_debug_set(16, v) / PAINTER_AMD_DROP_SKIP: DropPath skipping (the *_skip entry points: attention workgroups and GEMM row tiles of samples
-// whose factor is 0 do no work).  0 = default (on unless PAINTER_AMD_DROP_SKIP=0), 1 = off (the factor vector is ignored: what ran before), 2 = on
-inline int g_drop_skip = 0;
+// Run-time knobs of the library, host side only: ONE table, indexed by the numbers pa_debug_set / pa_debug_get take (they are part of what
+// bench.py, the tests and tools/ pass: never renumbered).  0 = the built-in default everywhere.
+enum Knob {
+    KNOB_G256_STAGGER = 0,         // gemm256: first-round de-phasing in shader cycles
+    KNOB_G256_NOSTORE = 1,         // gemm256: drop the epilogue stores (diagnostics)
+    KNOB_G256_ORDER = 2,           // gemm256: 1 = plain row-major tile order, 2 = blocked order with split = blockIdx.y (the pre-round-5 split-K assignment)
+    KNOB_WGRAD_TARGET = 3,         // workgroup target of the weight-gradient GEMM (gemm.hip: wgrad_fast_splits)
+    KNOB_G256_SHORT_TILES = 4,     // gemm256: 0 = the cost rule, 1 = always 256 rows, 2 = 224 rows wherever the kernel can
+    KNOB_G256_ILV = 5,             // (G256_ILV_AB builds) 1 + ILV schedule override
+    KNOB_RELPOS_SPLITS = 6,        // K splits of the rel-pos table-gradient GEMM.  The engine asks for 8 when that GEMM runs on the side stream beside the
+                                   // data-gradient chain (fewer, longer workgroups), the stand-alone optimum is 16
+    KNOB_ATTN3_FUSE = 7,           // fused rel-pos table gradient in the generation-3 dQ kernel: 0 = on unless PA_ATTN3_FUSE_RELPOS=0, 1 = off, 2 = on
+    KNOB_ATTN_LIGHT_LAST = 8,      // light attention workgroups dispatched last: 0 = off unless PA_ATTN_LIGHT_LAST=1 (round 5), 1 = off, 2 = on
+    KNOB_CONV_WGRAD_GROUPS = 9,    // tests only -- cap on the number of workgroups of the conv3x3 weight-gradient kernel (0 = the product's 512): with a small
+                                   // cap every workgroup walks many tiles, through both ring phases and across column-strip boundaries, at test sizes
+    KNOB_LN_BWD_VARIANT = 10,      // LayerNorm backward: 0 = rows split over the 4 waves of a workgroup wherever D >= 1024, 1 = one wave per row everywhere
+                                   // (the kernel of rounds 1 - 4; still what narrow D runs).  Round 5 let this knob share index 5 with the ILV override:
+                                   // tools that swept one silently switched the other
+    KNOB_G256_PATCH = 11,          // gemm256 tile patch per XCD (0 = default, TR * 16 + TC otherwise)
+    KNOB_G256_MIXED = 12,          // mixed 224-row + 128-row tiles for the multi-round GEMMs: 0 = on, 1 = off, 2 = KNOB_G256_MIXED_NFULL full tiles (tools/gemm_mixed_probe.py)
+    KNOB_FREE_13 = 13,             // free
+    KNOB_G256_MIXED_NFULL = 14,
+    KNOB_FREE_15 = 15,             // free
+    KNOB_DROP_SKIP = 16,           // DropPath skipping (the *_skip entry points: attention workgroups and GEMM row tiles of samples whose factor is 0 do no
+                                   // work): 0 = on unless PAINTER_AMD_DROP_SKIP=0, 1 = off (the factor vector is ignored: what ran before), 2 = on
+    KNOB_DECODER_ROWS = 17,        // the decoder backward over the token rows the loss mask leaves live (pa_decoder_live_ok; the engine asks it once per
+                                   // backward): 0 = on unless PAINTER_AMD_DECODER_ROWS=0, 1 = off (the dense decoder backward: what ran before), 2 = on
+    KNOB_COUNT = 18
+};
+inline int g_knob[KNOB_COUNT] = {};
 static inline bool drop_skip_on() {
     static const int env = [] { const char* v = getenv("PAINTER_AMD_DROP_SKIP"); return v ? atoi(v) : 1; }();
-    return g_drop_skip == 1 ? false : (g_drop_skip == 2 ? true : env != 0);
+    return g_knob[KNOB_DROP_SKIP] == 1 ? false : (g_knob[KNOB_DROP_SKIP] == 2 ? true : env != 0);
 }
-
-// pa_debug_set(17, v) / PAINTER_AMD_DECODER_ROWS: the decoder backward over the token rows the loss mask leaves live (pa_decoder_live_ok; the engine
-// asks it once per backward).  0 = default (on unless PAINTER_AMD_DECODER_ROWS=0), 1 = off (the dense decoder backward: what ran before), 2 = on
-inline int g_decoder_rows = 0;
 static inline bool decoder_rows_on() {
     static const int env = [] { const char* v = getenv("PAINTER_AMD_DECODER_ROWS"); return v ? atoi(v) : 1; }();
-    return g_decoder_rows == 1 ? false : (g_decoder_rows == 2 ? true : env != 0);
+    return g_knob[KNOB_DECODER_ROWS] == 1 ? false : (g_knob[KNOB_DECODER_ROWS] == 2 ? true : env != 0);
 }
 
 // host-side launch counters of the attention entry points, by kernel family: [0..2] pa_attn_fwd on the generic (attn_fwd.hip) /

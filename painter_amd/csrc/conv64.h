@@ -197,7 +197,7 @@ static inline bool ok(int Bn, int Hi, int Wi) {
 // Halo row r (0..3) of the tile in ring phase p (0 / 1, flips every step, 0 after a fresh load) lives in slot (2 p + r) & 3; the step code
 // reaches the slots through four wave-uniform offsets (ONE copy of the MFMA body: see below).
 static inline int wgrad_groups(int ntiles) {
-    const int cap = g_conv_wgrad_groups > 0 ? g_conv_wgrad_groups : 512;      // 512 = two resident workgroups per CU; pa_debug_set(9, n): tests
+    const int cap = g_knob[KNOB_CONV_WGRAD_GROUPS] > 0 ? g_knob[KNOB_CONV_WGRAD_GROUPS] : 512;      // 512 = two resident workgroups per CU; pa_debug_set(9, n): tests
     return ntiles < cap ? ntiles : cap;
 }
 

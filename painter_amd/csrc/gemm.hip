@@ -563,7 +563,7 @@ static int wgrad_fast_splits(int M, int N, int K) {
     // interleaved A/B on one box: 256 -> 132.9 / 133.1 images/s, 128 -> 135.0 / 134.9, 64 -> 136.1 (with 64 the fc1/fc2/qkv weight
     // gradients need no K split at all).  pa_debug_set(3, n) / PA_WGRAD_WGS select it.
     static const int env_target = [] { const char* v = getenv("PA_WGRAD_WGS"); return v ? atoi(v) : 0; }();
-    int target = env_target > 0 ? env_target : (g256::g_dbg[3] > 0 ? g256::g_dbg[3] : 256);
+    int target = env_target > 0 ? env_target : (g_knob[KNOB_WGRAD_TARGET] > 0 ? g_knob[KNOB_WGRAD_TARGET] : 256);
     if (target < 16) target = 16;
     int s = (target + 3 * tiles / 4) / tiles;          // (rounds up from x.25: ViT-H/14's 75-tile qkv gradient gets 2 splits = 150 workgroups at target 96, not 75 long ones.
     if (s < 1) s = 1;                                   //  At the side-stream target 96 every ViT-L shape -- 16 / 48 / 64 tiles -- keeps the count round-half-up gave it; at the
@@ -637,32 +637,12 @@ extern "C" int pa_linear_wgrad_live(const void* dy, int64_t lddy, const void* x,
 }
 
 extern "C" int pa_abi_version(void) { return PA_ABI_VERSION; }
-// knobs: 0-4 gemm256 (g256::g_dbg), 5 the G256_ILV_AB schedule override (experiment builds), 6 rel-pos splits, 7 fused rel-pos gradient,
-// 8 light attention workgroups last, 9 conv3x3 weight-gradient groups, 10 LayerNorm-backward variant (round 5 shared index 5 with the ILV
-// override: tools that swept one silently switched the other), 16 DropPath skipping (common.h, g_drop_skip), 17 decoder backward over the live rows
-// (common.h, g_decoder_rows)
+// the knob table (common.h: enum Knob, g_knob)
 extern "C" int pa_debug_get(int which) {
-    if (which == 16) return g_drop_skip;
-    if (which == 17) return g_decoder_rows;
-    if (which < 0 || which > 15) return -1;
-    if (which == 9) return g_conv_wgrad_groups;
-    if (which == 10) return g_ln_bwd_variant;
-    if (which > 10) return g_misc_knob[which - 11];
-    if (which == 6) return g_relpos_splits;
-    if (which == 7) return g_attn3_fuse;
-    if (which == 8) return g_attn_light_last;
-    return g256::g_dbg[which];
+    return which < 0 || which >= KNOB_COUNT ? -1 : g_knob[which];
 }
 extern "C" int pa_debug_set(int which, int value) {
-    if (which == 16) { g_drop_skip = value; return 0; }
-    if (which == 17) { g_decoder_rows = value; return 0; }
-    if (which < 0 || which > 15) return (int)hipErrorInvalidValue;
-    if (which < 8) g256::g_dbg[which] = value;
-    if (which == 9) g_conv_wgrad_groups = value;
-    if (which == 10) g_ln_bwd_variant = value;
-    if (which > 10) g_misc_knob[which - 11] = value;
-    if (which == 6) g_relpos_splits = value;
-    if (which == 7) g_attn3_fuse = value;
-    if (which == 8) g_attn_light_last = value;
+    if (which < 0 || which >= KNOB_COUNT) return (int)hipErrorInvalidValue;
+    g_knob[which] = value;
     return 0;
 }

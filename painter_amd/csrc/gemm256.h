@@ -26,8 +26,6 @@ namespace g256 {
 
 constexpr int BM = 256, BN = 256, BK = 64, NT = 512;
 constexpr int LDS_BYTES = 131072;
-// diagnostics (pa_debug_set): [0] first-round de-phasing in shader cycles, [1] drop epilogue stores, [2] 1 = plain row-major tile order, 2 = blocked order with split = blockIdx.y (the pre-round-5 split-K assignment), [3] wgrad workgroup target
-inline int g_dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // [5] (G256_ILV_AB builds) 1 + ILV schedule override
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_cvoid;
 
@@ -254,7 +252,7 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
     // all K slabs of its operand panels: the fc1 weight gradient read 431 MB where 129 are algorithmic (PMC, profiles/roofline_traffic.json).
     // Now the (split, tile) list -- split-major -- is cut into 8 contiguous runs, one per XCD: an XCD holds one split (or a few whole ones,
     // or a part of one) and inside it a compact patch of tiles, so a K slab of the operands goes through as few L2s as the sizes allow.
-    // Needs the workgroup count to be a multiple of 8; order 2 (g_dbg[2]) keeps the old assignment for A/B.
+    // Needs the workgroup count to be a multiple of 8; order 2 (KNOB_G256_ORDER) keeps the old assignment for A/B.
     if (gridDim.y > 1 && order == 0 && ((nwg * gridDim.y) & 7) == 0) {
         const int lin = blockIdx.y * nwg + bid;
         const int w = (lin & 7) * ((nwg * (int)gridDim.y) >> 3) + (lin >> 3);
@@ -264,7 +262,7 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
     // Inside the run the tiles are ordered in blocks of TR row panels x TC column panels (row groups of TR panels, column blocks of TC,
     // then row-major inside a block), so that the ~32 tiles an XCD has in flight form a TR x TC patch: per contraction step they pull
     // TR + TC operand panels through that XCD's L2 instead of 2 + tiles_n (fc1 forward, 16 column panels: FETCH_SIZE 251 -> ~165 MB
-    // per launch; the weight matrix alone is twice the L2).  g_dbg[2] = 1 restores the plain row-major order (A/B).
+    // per launch; the weight matrix alone is twice the L2).  KNOB_G256_ORDER = 1 restores the plain row-major order (A/B).
     int tm = 0, tn = 0;
     if (skipped) {
     } else if (order != 1) {
@@ -612,12 +610,12 @@ static int launch_ilv(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi 
 #define G256_ILV_DEFAULT 2     // round 3 (tools/gemm_ilv_ab.py, MI355X): 2 is 4-15 % faster than 0 on the forward GEMMs, 4-6 % on the data gradients,
 #endif                         // 2 % on the weight gradients, bit-identical results; 1 = 0.  In the training step the gain shrinks to ~1 % (DVFS)
 // Which row-tile height for an un-split launch with a K-major A operand: rounds of 256 workgroups x the tile's relative cost.
-// g_dbg[4] (pa_debug_set(4, v)): 0 = this rule, 1 = always 256 rows, 2 = 224 rows wherever the kernel can.  PA_G256_SHORT_COST: the
+// KNOB_G256_SHORT_TILES (pa_debug_set(4, v)): 0 = this rule, 1 = always 256 rows, 2 = 224 rows wherever the kernel can.  PA_G256_SHORT_COST: the
 // 224-row tile's cost relative to the 256-row tile in percent (default 92: 14 of 16 MFMAs, the full load segment and barriers).
 static inline bool use_short(int M, int N, int nsplit, bool amm) {
     if (amm || nsplit != 1 || M < BM) return false;
-    if (g_dbg[4] == 1) return false;
-    if (g_dbg[4] == 2) return true;
+    if (g_knob[KNOB_G256_SHORT_TILES] == 1) return false;
+    if (g_knob[KNOB_G256_SHORT_TILES] == 2) return true;
     static const int cost = [] { const char* v = getenv("PA_G256_SHORT_COST"); return v ? atoi(v) : 92; }();
     const int tiles_n = (N + BN - 1) / BN;
     const long t256 = (long)((M + BM - 1) / BM) * tiles_n, t224 = (long)((M + BM_SHORT - 1) / BM_SHORT) * tiles_n;
@@ -633,8 +631,8 @@ static inline bool use_short(int M, int N, int nsplit, bool amm) {
 struct TilePlan { bool is_short, mixed; int nfull; };
 static inline TilePlan tile_plan(int M, int N, int nsplit, bool amm) {
     TilePlan p{use_short(M, N, nsplit, amm), false, 0};
-    if (amm || nsplit != 1 || M < 2 * BM || g_misc_knob[1] == 1 || g_dbg[4] != 0) return p;
-    if (g_misc_knob[1] == 2 && g_misc_knob[3] > 0 && (long)g_misc_knob[3] * BM < M) return TilePlan{false, true, g_misc_knob[3]};      // diagnostics (tools/gemm_mixed_probe.py): pa_debug_set(12, 2) + pa_debug_set(14, nfull)
+    if (amm || nsplit != 1 || M < 2 * BM || g_knob[KNOB_G256_MIXED] == 1 || g_knob[KNOB_G256_SHORT_TILES] != 0) return p;
+    if (g_knob[KNOB_G256_MIXED] == 2 && g_knob[KNOB_G256_MIXED_NFULL] > 0 && (long)g_knob[KNOB_G256_MIXED_NFULL] * BM < M) return TilePlan{false, true, g_knob[KNOB_G256_MIXED_NFULL]};      // diagnostics (tools/gemm_mixed_probe.py): pa_debug_set(12, 2) + pa_debug_set(14, nfull)
     static const int cs = [] { const char* v = getenv("PA_G256_SHORT_COST"); return v ? atoi(v) : 97; }();
     static const int ch = [] { const char* v = getenv("PA_G256_HALF_COST"); return v ? atoi(v) : 75; }();
     const int tn = (N + BN - 1) / BN;
@@ -661,7 +659,7 @@ static int launch(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi epi,
     }
 #ifdef G256_ILV_AB       // experiment build: all three schedules in one library, pa_debug_set(5, 1 + ILV) picks one at run time
     static const int env_ilv = [] { const char* v = getenv("PA_G256_ILV"); return v ? atoi(v) : G256_ILV_DEFAULT; }();
-    const int ilv = g_dbg[5] > 0 ? g_dbg[5] - 1 : env_ilv;
+    const int ilv = g_knob[KNOB_G256_ILV] > 0 ? g_knob[KNOB_G256_ILV] - 1 : env_ilv;
     if (ilv == 2) return launch_ilv<AMM, BMM, 2, false>(A, lda, B, ldb, epi, M, N, K, nsplit, st);
     if (ilv == 1) return launch_ilv<AMM, BMM, 1, false>(A, lda, B, ldb, epi, M, N, K, nsplit, st);
     return launch_ilv<AMM, BMM, 0, false>(A, lda, B, ldb, epi, M, N, K, nsplit, st);
@@ -702,9 +700,9 @@ static int launch_ilv(const bf16* A, size_t lda, const bf16* B, size_t ldb, Epi 
     const int ktiles = K / BK;
     const int per = per_split(ktiles, nsplit);
     const int splits = (ktiles + per - 1) / per;      // every split gets an even number (>= 2) of tiles
-    if (g_dbg[1]) epi.M = 0;
+    if (g_knob[KNOB_G256_NOSTORE]) epi.M = 0;
     PA_LAUNCH(kern, dim3(tiles_m * tiles_n, splits), dim3(NT), LDS_BYTES, st, A, (uint32_t)lda, B, (uint32_t)ldb, epi, M, N,
-              ktiles, per, tiles_n, g_dbg[0], g_dbg[2], nfull, g_misc_knob[0] > 0 ? g_misc_knob[0] : env_patch, rowskip, rps, live_count);
+              ktiles, per, tiles_n, g_knob[KNOB_G256_STAGGER], g_knob[KNOB_G256_ORDER], nfull, g_knob[KNOB_G256_PATCH] > 0 ? g_knob[KNOB_G256_PATCH] : env_patch, rowskip, rps, live_count);
     return (int)hipGetLastError();
 }
 // row tiles of the launch launch<AMM = false>(...) makes for this shape (partial rows of a column-sum epilogue = 2 x this)

@@ -330,7 +330,7 @@ static int ln_bwd_blocks_wave(int R) {
 // 4 per CU -0.68 ms, 2-row batches / 5 per CU +0.15 ms (6 spilled registers and 1255 short workgroups).
 constexpr int LNB_RB = 2;
 static int lnb_occ(int D) { return D <= 1024 ? 4 : 3; }
-static bool ln_bwd_rows_ok(int D) { return g_ln_bwd_variant != 1 && D >= 1024 && D <= 2048; }
+static bool ln_bwd_rows_ok(int D) { return g_knob[KNOB_LN_BWD_VARIANT] != 1 && D >= 1024 && D <= 2048; }
 static int ln_bwd_blocks_rows(int R, int D) {
     const int nbatch = (R + LNB_RB - 1) / LNB_RB, cap = 256 * lnb_occ(D);
     if (nbatch <= 0) return 0;                                  // an empty batch: no workgroups, no workspace (and no division by k = 0)

@@ -13,29 +13,17 @@ Data layout in HBM (per rank):
   pred / loss              fp32 NCHW [B,3,H,W], [2]
 """
 import os
+from typing import NamedTuple
 
 import torch
 
 from . import hostmath, ops
-from ._lib import EPI_BIAS, EPI_BIAS_F32, EPI_BIAS_RESID
+from ._lib import EPI_BIAS, EPI_BIAS_F32, EPI_BIAS_RESID, KNOB_RELPOS_SPLITS, KNOB_WGRAD_TARGET
 
 
-# diagnostics for the two-stream backward: keep every tensor the side stream reads alive until the end of the backward (no
-# allocator reuse), or serialise the two streams (no concurrency)
-_DBG_KEEP = os.environ.get("PAINTER_AMD_DEBUG_KEEPALIVE", "0") == "1"
-_DBG_SERIAL = os.environ.get("PAINTER_AMD_DEBUG_SERIAL", "0") == "1"
-_SIDE_EXTRA = os.environ.get("PAINTER_AMD_SIDE_EXTRA", "1") != "0"     # rel-pos and conv weight gradients on the side stream too
-_DBG_TRACE = os.environ.get("PAINTER_AMD_DEBUG_TRACE", "0") == "1"     # checksums of the backward's intermediates -> HotPath.trace
-
-
-# A/B switches of two round-5 / round-4 arrangements (tools/step_engine_ab.py toggles the module globals in one process):
-#   _ATTN_PREP   "fused": the dQ kernel computes Delta itself (no launch);  "launch": one pa_attn_bwd_prep launch per block (round 4)
-#   _FC1_COLSUM  "epilogue": fc1's bias gradient from the fc2 data-gradient GEMM's epilogue (round 4);  "separate": a column-sum pass on the side stream
-_ATTN_PREP = os.environ.get("PAINTER_AMD_ATTN_PREP", "fused")
-_FC1_COLSUM = os.environ.get("PAINTER_AMD_FC1_COLSUM", "epilogue")
 _SIDE_STREAM = os.environ.get("PAINTER_AMD_SIDE_STREAM", "1") != "0"
-_SIDE_PRIORITY = int(os.environ.get("PAINTER_AMD_SIDE_PRIORITY", "0"))
-_RELPOS_PACK = os.environ.get("PAINTER_AMD_RELPOS_PACK", "batch")      # "per_block": the per-block pack launches of rounds 4 - 5 (A/B only)
+_DBG_SERIAL = os.environ.get("PAINTER_AMD_DEBUG_SERIAL", "0") == "1"   # diagnostics: serialise the two streams of the backward (no concurrency)
+_DBG_TRACE = os.environ.get("PAINTER_AMD_DEBUG_TRACE", "0") == "1"     # checksums of the backward's intermediates -> HotPath.trace
 _configured = False
 # sizing of the parameter-gradient kernels when they run on the side stream, beside the data-gradient chain (0 = stand-alone sizing)
 WGRAD_SIDE_TARGET = 96       # round 5 re-sweep on the lighter side stream (tools/step_knob_ab.py, profiles/r05_wgrad_side_target_sweep.log): 96 -> 53.08, 128 -> 53.42, 160 -> 54.09, 192 -> 54.47 ms/step
@@ -49,8 +37,8 @@ def _configure_library():
     if _configured:
         return
     from ._lib import lib
-    lib.pa_debug_set(6, RELPOS_SIDE_SPLITS if _SIDE_STREAM else 0)       # K splits of the rel-pos table-gradient GEMM beside the main chain: round 2: 16 -> 54.54, 4 -> 54.35, 2 -> 55.0 ms/step; round 3 (tools/knob_sweep.py): 2 -> 56.18, 4 -> 55.10, 8 -> 54.89
-    lib.pa_debug_set(3, WGRAD_SIDE_TARGET if _SIDE_STREAM else 0)     # wgrad GEMM workgroup target (gemm.hip: wgrad_fast_splits); round-2 sweep: 64 -> 59.7, 96 -> 57.7, 128 -> 57.7, 192 -> 58.9, 256 -> 59.2 ms/step
+    lib.pa_debug_set(KNOB_RELPOS_SPLITS, RELPOS_SIDE_SPLITS if _SIDE_STREAM else 0)       # K splits of the rel-pos table-gradient GEMM beside the main chain: round 2: 16 -> 54.54, 4 -> 54.35, 2 -> 55.0 ms/step; round 3 (tools/knob_sweep.py): 2 -> 56.18, 4 -> 55.10, 8 -> 54.89
+    lib.pa_debug_set(KNOB_WGRAD_TARGET, WGRAD_SIDE_TARGET if _SIDE_STREAM else 0)     # wgrad GEMM workgroup target (gemm.hip: wgrad_fast_splits); round-2 sweep: 64 -> 59.7, 96 -> 57.7, 128 -> 57.7, 192 -> 58.9, 256 -> 59.2 ms/step
     _configured = True
 
 
@@ -105,6 +93,120 @@ class _Saved:
     pass
 
 
+class _Block(NamedTuple):
+    """What one block's forward keeps for its backward (S.blocks[i]; the backward drops the entry as it consumes it)."""
+    x: torch.Tensor            # the block's input (fp32 residual stream)
+    mean1: torch.Tensor
+    rstd1: torch.Tensor
+    ln1: torch.Tensor
+    qkv: torch.Tensor
+    rcat: torch.Tensor
+    ao: torch.Tensor           # attention output, the operand of proj
+    lse: torch.Tensor
+    x1: torch.Tensor           # residual stream after the attention branch
+    mean2: torch.Tensor
+    rstd2: torch.Tensor
+    ln2: torch.Tensor
+    gaux: torch.Tensor         # ops.linear_gelu's second result
+    act: torch.Tensor
+    Bc: int                    # samples in the stream at this block (2B up to the merge, B afterwards)
+    atab: torch.Tensor         # ops.attn_fwd's tables (None where the kernels in use export none)
+    group: int                 # SegGPT ensemble group size, 0 = no ensemble in this block
+
+
+class _Tap(NamedTuple):
+    """A feature tap's saved LayerNorm input and statistics (S.taps[k])."""
+    x: torch.Tensor
+    mean: torch.Tensor
+    rstd: torch.Tensor
+
+
+class _Streams:
+    """The two HIP streams of one backward.  The data-gradient chain runs on `main`, the caller's stream; parameter gradients, which nothing
+    downstream in the backward consumes, go to `side` (None: everything runs inline).  The rule between them, carried here once: the side
+    stream waits for main before each piece of work; every main-stream tensor that work reads is recorded against the side stream, so that
+    the allocator does not hand its memory out again before the side stream is done with it; PAINTER_AMD_DEBUG_SERIAL joins main behind
+    every piece (no concurrency: diagnostics)."""
+    __slots__ = ("main", "side")
+
+    def __init__(self, main, side):
+        self.main, self.side = main, side
+
+    def run(self, fn, *reads):
+        """-> fn(), a parameter-gradient computation that reads the main-stream tensors `reads` (None entries are ignored)."""
+        if self.side is None:
+            return fn()
+        self.side.wait_stream(self.main)
+        with torch.cuda.stream(self.side):
+            r = fn()
+        for t in reads:
+            if t is not None:
+                t.record_stream(self.side)
+        if _DBG_SERIAL:
+            self.main.wait_stream(self.side)
+        return r
+
+    def shared(self, t):
+        """-> t, a main-stream allocation that work on the side stream reads or writes as well."""
+        if self.side is not None:
+            t.record_stream(self.side)
+        return t
+
+    def private(self, t):
+        """-> a buffer the main stream may overwrite while the side stream may still read t: a new one, or t itself without a side stream."""
+        return t if self.side is None else torch.empty_like(t)
+
+    def ready(self, sync, G, names, flat=None):
+        """Hand the bucket `names` of G to the GradSync (if any) behind both streams: its gradients come from both, and the exchange reads
+        main-stream allocations (LayerNorm / rel-pos / tail gradients).  flat: one contiguous fp32 buffer that already holds every small
+        gradient of `names` (they are views of it): it is exchanged as ONE message in place -- no flattening copy on the side stream."""
+        if sync is not None:
+            self.run(lambda: sync.ready(G, names, flat=flat), *[G[n] for n in names])
+
+    def join(self, probe=None):
+        """Order every gradient before whatever the caller enqueues next.  probe (tools/step_tail.py): two events, when each stream ran dry."""
+        if self.side is not None:
+            if probe is not None:
+                probe[0].record(self.main)
+                probe[1].record(self.side)
+            self.main.wait_stream(self.side)
+
+
+class _Backward:
+    """The per-call context the parts of HotPath.backward share."""
+    __slots__ = ("P", "S", "sync", "want", "st", "G", "flats", "rc_shape", "dnorm")
+
+    def __init__(self, P, S, sync, want, st):
+        self.P, self.S, self.sync, self.want, self.st = P, S, sync, want, st
+        self.G = {}
+        self.flats = {}                                    # block -> its flat small-gradient buffer (HotPath.block_flat)
+        self.rc_shape = tuple(S.blocks[-1].rcat.shape)     # Rcat [NRP, head_dim]: the same for every block
+        self.dnorm = None                                  # the four taps' accumulated d(norm.weight, norm.bias)
+
+    def need(self, n):
+        return self.want is None or n in self.want
+
+    def param_grads(self, wname, bname, dy, x, bout=None, wgrad=None, colsum=None):
+        """G[wname] = dy^T.x and G[bname] = colsum(dy) (into `bout`, a slice of the block's flat small-gradient buffer, when given), as far as
+        they are wanted: a frozen parameter (outside `want`) costs nothing, and a bias that is already in G was summed by the kernel that
+        produced dy (fc2 / proj: the LayerNorm backward; fc1: the fc2 data-gradient GEMM's epilogue).
+        wgrad(dy, x) / colsum(dy, out=): the two computations, ops.linear_wgrad / ops.colsum unless given (the decoder's live-row route)."""
+        G = self.G
+        do_w, do_b = self.need(wname), bname not in G and self.need(bname)
+        if not (do_w or do_b):
+            return
+
+        def fn():
+            if do_w:
+                G[wname] = (wgrad or ops.linear_wgrad)(dy, x)
+            if do_b:
+                G[bname] = (colsum or ops.colsum)(dy, out=bout)
+        self.st.run(fn, dy, x if do_w else None)
+
+    def ready(self, names, flat=None):
+        self.st.ready(self.sync, self.G, names, flat=flat)
+
+
 class HotPath:
     """Owns the per-module device constants and runs forward / backward."""
 
@@ -127,10 +229,7 @@ class HotPath:
     def side_stream(self, device):
         s = self._side.get(device)
         if s is None:
-            # PAINTER_AMD_SIDE_PRIORITY: HIP stream priority of the parameter-gradient stream (0 = default; what the runtime accepts
-            # is clamped by torch / HIP; tools/prio_ab.py measures it against a high-priority main stream)
-            s = torch.cuda.Stream(device=device, priority=getattr(self, "side_priority", _SIDE_PRIORITY))
-            self._side[device] = s
+            s = self._side[device] = torch.cuda.Stream(device=device)
         return s
 
     LN_RING = 6
@@ -211,11 +310,6 @@ class HotPath:
         i = int(pre.split(".")[1])
         rh, rw = P[pre + "attn.rel_pos_h"], P[pre + "attn.rel_pos_w"]
         st = self._rcache
-        if _RELPOS_PACK == "per_block":            # rounds 4 - 5 (A/B: tools/step_engine_ab.py): one launch per block and orientation
-            key, ver = (pre, transposed), (rh.data_ptr(), rw.data_ptr(), rh._version, rw._version)
-            if key not in st or st[key][0] != ver:
-                st[key] = (ver, (ops.relpos_pack_t if transposed else ops.relpos_pack)(rh, rw, c.Hp, c.Wp, self.T))
-            return st[key][1]
         if st and st["dev"] == rh.device and st["ptr"][i] == (rh.data_ptr(), rw.data_ptr()) and st["ver"][i] == (rh._version, rw._version):
             return (st["rcatT"] if transposed else st["rcat"])[i]
         hs = [P["blocks.%d.attn.rel_pos_h" % k] for k in range(c.depth)]
@@ -235,9 +329,7 @@ class HotPath:
         """Mark the packed rel-pos tables stale, as an optimizer update of the tables does through their version counters (buffers and the
         address table stay): bench.py calls it before every timed step so that forward + backward is timed as training runs it."""
         st = self._rcache
-        if _RELPOS_PACK == "per_block":
-            st.clear()
-        elif st:
+        if st:
             st["ver"] = [None] * len(st["ver"])
 
     def invalidate(self):
@@ -329,7 +421,7 @@ class HotPath:
             x2 = ops.linear_fwd(act, self.w(pre + "mlp.fc2.weight", P), P[pre + "mlp.fc2.bias"], EPI_BIAS_RESID,
                                 resid=x1, rowscale=ds_m, rows_per_sample=L, rowskip=ds_m)
             if need_grad:
-                S.blocks.append((x, mean1, rstd1, ln1, qkv, rcat, ao, lse, x1, mean2, rstd2, ln2, gaux, act, Bc, atab, group))
+                S.blocks.append(_Block(x, mean1, rstd1, ln1, qkv, rcat, ao, lse, x1, mean2, rstd2, ln2, gaux, act, Bc, atab, group))
             x = x2
             if i == c.merge_idx:
                 Bc = B
@@ -338,7 +430,7 @@ class HotPath:
                 k = c.taps.index(i)
                 _, mt, rt = ops.layernorm_fwd(x, P["norm.weight"], P["norm.bias"], c.ln_eps, T, out=concat[:, k * D:(k + 1) * D])
                 if need_grad:
-                    S.taps.append((x, mt, rt))
+                    S.taps.append(_Tap(x, mt, rt))
         E = ops.linear_pixshuf(concat, self.w("decoder_embed.weight", P), P["decoder_embed.bias"], B, c.Hp, c.Wp, c.P, c.dec)
         w3r, wf = ops.conv3x3_pack(P["decoder_pred.0.weight"], T)
         w1 = P["decoder_pred.3.weight"].reshape(3, c.dec)
@@ -365,91 +457,39 @@ class HotPath:
         gradient is computed and exchanged (want is ignored).
         dpatch: f32 [B, L, P*P*3] gradient of the returned pred_patch, or None (then dpred is today's pa_loss_bwd).
 
-        Two HIP streams: the data-gradient chain (dgrad GEMMs, attention backward, LayerNorm backward) runs on the caller's
-        stream; every weight/bias gradient of an nn.Linear (wgrad GEMM + slab reduction + column sum) is enqueued on a side
-        stream behind an event, because nothing downstream in the backward consumes it."""
-        c, T = self.cfg, self.T
-        B, L, D = S.B, c.L, c.D
+        Two HIP streams (_Streams): the data-gradient chain (dgrad GEMMs, attention backward, LayerNorm backward) runs on the caller's
+        stream; every parameter gradient (wgrad GEMM + slab reduction + column sum, the conv and rel-pos table gradients, the deferred
+        LayerNorm reductions) is enqueued on a side stream behind it, because nothing downstream in the backward consumes it."""
         dev = S.imgs.device
-        G = {}
         if sync is not None:
             want = None
-        need = (lambda n: True) if want is None else (lambda n: n in want)
-        main = torch.cuda.current_stream(dev)
         side = self.side_stream(dev) if self.use_side_stream and (want is None or len(want) > 0) else None
-        keep = []
+        X = _Backward(P, S, sync, want, _Streams(torch.cuda.current_stream(dev), side))
         self.trace = []
+        dconcat, dpred_loss = self._backward_decoder(X, dloss, dpatch, want_tgts)
+        dx = dyT_next = None
+        for i in reversed(range(self.cfg.depth)):
+            dx, dyT_next = self._backward_block(X, i, dconcat, dx, dyT_next)
+        dimgs, dtgts = self._backward_tokens(X, dx, dpred_loss, want_imgs, want_tgts)
+        del dpred_loss
+        G = X.G
+        if want is not None:
+            G = {n: g for n, g in G.items() if g is not None and n in want}
+        X.st.join(getattr(self, "tail_probe", None))       # every gradient is ordered before whatever the caller enqueues next
+        if sync is not None:
+            sync.finish()
+        if want_imgs or want_tgts:
+            return G, dimgs, dtgts
+        return G
 
-        def tr(name, t):
-            if _DBG_TRACE:
-                self.trace.append((name, t.detach().double().abs().sum()))
+    def _tr(self, name, t):
+        if _DBG_TRACE:
+            self.trace.append((name, t.detach().double().abs().sum()))
 
-        filt = getattr(self, "side_filter", None)          # diagnostics: {"dec","fc2","fc1","proj","qkv"} subsets, "nocolsum", "nowgrad"
-
-        def param_grads(wname, bname, dy, x, bout=None, wgrad=ops.linear_wgrad, colsum=ops.colsum):
-            """G[wname] = dy^T.x, G[bname] = colsum(dy) (into `bout`, a slice of the block's flat small-gradient buffer, when given)
-            -- on the side stream when enabled.  Frozen parameters (outside `want`) cost nothing here.
-            wgrad(dy, x) / colsum(dy, out=): the two computations (the decoder's live-row route passes its own)."""
-            if not need(wname) and (bname in G or not need(bname)):
-                return
-            if not need(wname) or not need(bname):          # partly frozen layer: only what is asked for, in the caller's stream order
-                def one():
-                    if need(wname):
-                        G[wname] = wgrad(dy, x)
-                    if bname not in G and need(bname):
-                        G[bname] = colsum(dy, out=bout)
-                on_side(one, *[t for t in (dy, x if need(wname) else None) if t is not None])
-                return
-            tag = "dec" if wname.startswith("decoder") else wname.split(".")[-2]
-            if side is None or (filt is not None and tag not in filt):
-                G[wname] = wgrad(dy, x)
-                if bname not in G:                 # (fc2 / proj biases: already summed by the LayerNorm backward that produced dy)
-                    G[bname] = colsum(dy, out=bout)
-                return
-            if filt is not None and "nocolsum" in filt:
-                G[bname] = colsum(dy, out=bout)
-            if filt is not None and "nowgrad" in filt:
-                G[wname] = wgrad(dy, x)
-            side.wait_stream(main)                 # dy (and x) are enqueued on main
-            with torch.cuda.stream(side):
-                if wname not in G:
-                    G[wname] = wgrad(dy, x)
-                if bname not in G:
-                    G[bname] = colsum(dy, out=bout)
-            dy.record_stream(side)                 # the allocator must not hand these out again before the side stream is done
-            x.record_stream(side)
-            if _DBG_KEEP:
-                keep.extend([dy, x])
-            if _DBG_SERIAL:
-                main.wait_stream(side)
-
-        def on_side(fn, *inputs):
-            """Run a parameter-gradient computation that nothing downstream consumes on the side stream (inputs: main-stream tensors)."""
-            if side is None or not _SIDE_EXTRA:
-                return fn()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                r = fn()
-            for t in inputs:
-                t.record_stream(side)
-            if _DBG_SERIAL:
-                main.wait_stream(side)
-            return r
-
-        def ready(names, flat=None):
-            """flat: one contiguous fp32 buffer that already holds every small gradient of `names` (they are views of it): it is
-            exchanged as ONE message in place -- no flattening copy on the side stream."""
-            if sync is None:
-                return
-            if side is None:
-                sync.ready(G, names, flat=flat)
-                return
-            side.wait_stream(main)                 # the bucket's gradients come from both streams
-            for n in names:                        # main-stream allocations (LayerNorm / rel-pos / tail gradients) are read by the
-                G[n].record_stream(side)           # side stream's exchange: keep the allocator from recycling them early
-            with torch.cuda.stream(side):
-                sync.ready(G, names, flat=flat)
-
+    def _backward_decoder(self, X, dloss, dpatch, want_tgts):
+        """Loss, decoder tail and decoder_embed -> (dconcat T [B*L, 4D], the loss's own term of dpred or None)."""
+        c, T, P, S, G, st, need = self.cfg, self.T, X.P, X.S, X.G, X.st, X.need
+        B = S.B
         dpred_loss = None          # the loss's own term of dpred: its direct gradient w.r.t. tgts is -dpred_loss
         if dpatch is None:
             dpred = ops.loss_bwd(S.pred, S.tgts, S.valid, S.mask, dloss, S.loss_out, c.P, c.loss_func)
@@ -465,14 +505,10 @@ class HotPath:
         G["decoder_pred.3.weight"] = tg[128:320].reshape(3, c.dec, 1, 1)
         G["decoder_pred.3.bias"] = tg[320:323]
         npix = B * c.H * c.W
-        if want is None:
-            G["decoder_pred.0.weight"], G["decoder_pred.0.bias"] = on_side(
-                lambda: (ops.conv3x3_wgrad(dy3, S.E), ops.colsum(dy3.view(npix, c.dec))), dy3, S.E)
-        elif need("decoder_pred.0.weight") or need("decoder_pred.0.bias"):
-            G["decoder_pred.0.weight"], G["decoder_pred.0.bias"] = on_side(
+        if need("decoder_pred.0.weight") or need("decoder_pred.0.bias"):
+            G["decoder_pred.0.weight"], G["decoder_pred.0.bias"] = st.run(
                 lambda: (ops.conv3x3_wgrad(dy3, S.E) if need("decoder_pred.0.weight") else None,
-                         ops.colsum(dy3.view(npix, c.dec)) if need("decoder_pred.0.bias") else None),
-                *[t for t in (dy3, S.E) if t is not None])
+                         ops.colsum(dy3.view(npix, c.dec)) if need("decoder_pred.0.bias") else None), dy3, S.E)
         w_de = self.w("decoder_embed.weight", P)
         if dpatch is None and ops.decoder_live_ok(T, B, c.Hp, c.Wp, c.P, w_de.shape[1]):
             # The loss touches masked patches only: dE is exactly zero on every token without a masked patch in its 3 x 3 neighbourhood.  The
@@ -480,153 +516,154 @@ class HotPath:
             # number stays on the device), and the data gradient is scattered back into a dconcat whose dead rows are zero.
             # A gradient on pred_patch (dpatch) makes every row live: that case, the fp32 build and ragged shapes stay dense.
             rowmap, live, count = ops.live_rows(S.mask, B, c.Hp, c.Wp)
+            st.shared(count)                       # (rowmap / live / count share one allocation; the side stream's GEMM and sums read it)
             dE = ops.conv3x3_dgrad_unshuffle_live(dy3, S.wf, rowmap, count, B, c.Hp, c.Wp, c.P)
             del dy3
-            param_grads("decoder_embed.weight", "decoder_embed.bias", dE, S.concat,
-                        wgrad=lambda dy, x: ops.linear_wgrad(dy, x, live=(live, count)),
-                        colsum=lambda dy, out=None: ops.colsum_live(dy, count, out=out))
-            if side is not None:
-                count.record_stream(side)          # (rowmap / live / count share one allocation; the side stream's GEMM and sums read it)
+            X.param_grads("decoder_embed.weight", "decoder_embed.bias", dE, S.concat,
+                          wgrad=lambda dy, x: ops.linear_wgrad(dy, x, live=(live, count)),
+                          colsum=lambda dy, out=None: ops.colsum_live(dy, count, out=out))
             dconcat = ops.linear_dgrad(dE, w_de, live=(live, rowmap, count))
             if _DBG_TRACE:
-                tr("dE", dE[:int(count.item())])
+                self._tr("dE", dE[:int(count.item())])
         else:
             dE = ops.conv3x3_dgrad_unshuffle(dy3, S.wf, B, c.Hp, c.Wp, c.P)
             del dy3
-            param_grads("decoder_embed.weight", "decoder_embed.bias", dE, S.concat)
+            X.param_grads("decoder_embed.weight", "decoder_embed.bias", dE, S.concat)
             dconcat = ops.linear_dgrad(dE, w_de)
-            tr("dE", dE)
-        tr("dconcat", dconcat)
+            self._tr("dE", dE)
+        self._tr("dconcat", dconcat)
         del dE
-        ready(["decoder_embed.weight", "decoder_embed.bias"])
-        ready([n for n in G if n.startswith("decoder_pred.")])
-        dnorm = None
-        dx = None
-        dyT_next = None
-        flats = {}
+        X.ready(["decoder_embed.weight", "decoder_embed.bias"])
+        X.ready([n for n in G if n.startswith("decoder_pred.")])
+        return dconcat, dpred_loss
 
-        def block_flat(i_):
-            """The flat small-gradient buffer of block i_ (allocated on first use: block i_ + 1's norm1 backward already writes block
-            i_'s fc2 bias gradient into it)."""
-            if i_ not in flats:
-                nrp_, hd_ = rc_shape
-                sizes = [2 * D, 2 * D, 3 * D, D, c.hidden, D, nrp_ * hd_]
-                fb = torch.empty((sum(sizes),), dtype=torch.float32, device=dev)
-                if side is not None:
-                    fb.record_stream(side)
-                flats[i_] = (fb, dict(zip(("n1", "n2", "qkv", "proj", "fc1", "fc2", "rel"), torch.split(fb, sizes))))
-            return flats[i_]
+    def block_flat(self, X, i):
+        """(buffer, named views) of block i's small gradients (LayerNorm affine, the four biases, the rel-pos tables), which live in ONE flat
+        buffer so that the gradient exchange sends them as one message without a flattening copy:
+        [norm1 g,b | norm2 g,b | qkv.b | proj.b | fc1.b | fc2.b | d rcat].  Allocated on first use: block i + 1's norm1 backward already
+        writes block i's fc2 bias gradient into it."""
+        if i not in X.flats:
+            D = self.cfg.D
+            sizes = [2 * D, 2 * D, 3 * D, D, self.cfg.hidden, D, X.rc_shape[0] * X.rc_shape[1]]
+            fb = X.st.shared(torch.empty((sum(sizes),), dtype=torch.float32, device=X.S.imgs.device))
+            X.flats[i] = (fb, dict(zip(("n1", "n2", "qkv", "proj", "fc1", "fc2", "rel"), torch.split(fb, sizes))))
+        return X.flats[i]
 
-        rc_shape = tuple(S.blocks[-1][5].shape)            # Rcat [NRP, head_dim]: the same for every block
-        for i in reversed(range(c.depth)):
-            pre = "blocks.%d." % i
-            x0, mean1, rstd1, ln1, qkv, rcat, ao, lse, x1, mean2, rstd2, ln2, gaux, act, Bc, atab, ens_group = S.blocks[i]
-            S.blocks[i] = None
-            R = Bc * L
-            ds_a, ds_m = (None, None) if S.drop is None else S.drop[i]
-            # DropPath skipping (see forward): the dY rows of a dropped sample are exact zeros (the LayerNorm backward / merge_bwd multiplied
-            # them by the factor), so the branch's data-gradient kernels leave them out.  The ensemble mixes samples: no skipping there.
-            sk_a = None if ens_group > 0 else ds_a
-            # the block's small gradients (LayerNorm affine, the four biases, the rel-pos tables) live in ONE flat buffer so that the
-            # gradient exchange sends them as one message without a flattening copy: [norm1 g,b | norm2 g,b | qkv.b | proj.b | fc1.b | fc2.b | d rcat]
-            nrp, hd = rcat.shape
-            flat, fl = block_flat(i)
-            del flats[i]
-            # dyT = bf16(ds_m * dx) is emitted by the kernel that produces the final dx of this block's output: the tap
-            # LayerNorm backward, block i+1's norm1 backward (dyT_next), or the stream-merge backward
-            if i in c.taps:
-                k = c.taps.index(i)
-                xt, mt, rt = S.taps[k]
-                dyT = torch.empty((R, D), dtype=T, device=dev)
-                # (the LayerNorm backward kernels also sum the columns of the dxT they emit: dxT is the dY of fc2 / proj, so that
-                # sum is the layer's bias gradient -- no separate pass over dxT)
-                dx, gb = ops.layernorm_bwd(dconcat[:, k * D:(k + 1) * D], xt, mt, rt, P["norm.weight"], dres=dx, dx=dx, dxT=dyT,
-                                           rowscale=ds_m, rows_per_sample=L, dxT_colsum=fl["fc2"])
-                G[pre + "mlp.fc2.bias"] = fl["fc2"]
-                if need("norm.weight") or need("norm.bias"):
-                    dnorm = gb if dnorm is None else _add_(dnorm, gb)
-            elif i == c.merge_idx:
-                dx, dyT = ops.merge_bwd(T, dx, ds_m, L, B * L, D)
-            else:
-                dyT = dyT_next
-            # ---- MLP branch: x2 = x1 + s_m * fc2(gelu(fc1(LN2(x1))))
-            param_grads(pre + "mlp.fc2.weight", pre + "mlp.fc2.bias", dyT, act, fl["fc2"])
-            tr("%d.dyT" % i, dyT)
-            # (the GEMM's epilogue also sums the columns of the dpre it stores: fc1's bias gradient, no separate pass over [R, 4D])
-            if _FC1_COLSUM == "epilogue":
-                dpre = ops.linear_dgrad(dyT, self.w(pre + "mlp.fc2.weight", P), gelu_aux=gaux, colsum_out=fl["fc1"], rowskip=ds_m, rows_per_sample=L)
-                G[pre + "mlp.fc1.bias"] = fl["fc1"]
-            else:                                  # A/B: param_grads below sums the columns of dpre on the side stream
-                dpre = ops.linear_dgrad(dyT, self.w(pre + "mlp.fc2.weight", P), gelu_aux=gaux)
-            tr("%d.dpre" % i, dpre)
-            param_grads(pre + "mlp.fc1.weight", pre + "mlp.fc1.bias", dpre, ln2, fl["fc1"])
-            dln2 = ops.linear_dgrad(dpre, self.w(pre + "mlp.fc1.weight", P), rowskip=ds_m, rows_per_sample=L)
-            tr("%d.dln2" % i, dln2)
-            del dpre
-            # dyT may still be read by the side stream: the attention branch's dY gets its own buffer
-            dyA = torch.empty_like(dyT) if side is not None else dyT
-            # (the reduction of the LayerNorm parameter-gradient partials is a parameter gradient too: side stream)
-            lnws, lndone = self.ln_workspace(dev, ops.layernorm_bwd_workspace_bytes(R, D), main, side if _SIDE_EXTRA else None)
-            dx, fin = ops.layernorm_bwd(dln2, x1, mean2, rstd2, P[pre + "norm2.weight"], dres=dx, dx=dx, dxT=dyA,
-                                        rowscale=ds_a, rows_per_sample=L, gb=fl["n2"].view(2, D), dxT_colsum=fl["proj"], defer=True, ws=lnws)
-            gb = None
-            if need(pre + "norm2.weight") or need(pre + "norm2.bias") or need(pre + "attn.proj.bias"):
-                gb = on_side(fin)
-                lndone()
-                G[pre + "norm2.weight"], G[pre + "norm2.bias"] = gb[0], gb[1]
-            G[pre + "attn.proj.bias"] = fl["proj"]
-            del dyT
-            tr("%d.dx_ln2" % i, dx); tr("%d.dyA" % i, dyA)
-            if gb is not None:
-                tr("%d.gb2" % i, gb)
-            # ---- attention branch: x1 = x0 + s_a * proj(attn(LN1(x0)))
-            if ens_group > 0:
-                # SegGPT feature ensemble (forward: x1 = x0 + s_a * ens(proj(...))): the branch gradient is ens applied to s_a * dx (fp32: the
-                # kernel's own type), re-rounded to the operand type.  Column sums are unchanged by a mean + broadcast over samples, so
-                # the proj bias gradient the LayerNorm backward already summed (of s_a * dx) stands.
-                da = ops.ensemble_resid(torch.zeros_like(dx), dx if ds_a is None else ops.scale_cast(torch.float32, dx, ds_a, L), Bc, ens_group, L, D)
-                dyA = da if T == torch.float32 else ops.cast_bf16(da, out=dyA)
-                del da
-            param_grads(pre + "attn.proj.weight", pre + "attn.proj.bias", dyA, ao, fl["proj"])
-            dao = ops.linear_dgrad(dyA, self.w(pre + "attn.proj.weight", P), out=dln2, rowskip=sk_a, rows_per_sample=L)
-            tr("%d.dao" % i, dao)
-            del dyA
-            rcatT = self.relpos(pre, P, True)
-            dqkv, dG = ops.attn_bwd_core(qkv, rcat, rcatT, ao, dao, lse, Bc, L, c.heads, c.Hp, c.Wp, c.scale, tables=atab, prep=_ATTN_PREP, rowskip=sk_a)
-            if need(pre + "attn.rel_pos_h") or need(pre + "attn.rel_pos_w"):
-                # (the dQ kernel still writes its rel-pos partials / dG when the tables are frozen: only this reduction is skipped)
-                drcat = on_side(lambda: ops.attn_bwd_relpos(dG, qkv, nrp, Bc, L, c.heads, c.Hp, c.Wp, out=fl["rel"].view(nrp, hd)), dG, qkv)
-                nh, nw = 2 * c.Hp - 1, 2 * c.Wp - 1
-                G[pre + "attn.rel_pos_h"] = drcat[:nh]
-                G[pre + "attn.rel_pos_w"] = drcat[nh:nh + nw]
-            del dG
-            tr("%d.dqkv" % i, dqkv)
-            param_grads(pre + "attn.qkv.weight", pre + "attn.qkv.bias", dqkv, ln1, fl["qkv"])
-            dln1 = ops.linear_dgrad(dqkv, self.w(pre + "attn.qkv.weight", P), out=dao, rowskip=sk_a, rows_per_sample=L)
-            del dqkv
-            nxt = i - 1
+    def _backward_block(self, X, i, dconcat, dx, dyT_next):
+        """Block i: (dx of its output -- None at the last block --, the dY of its fc2 when block i + 1's norm1 backward emitted it)
+        -> (dx of its input, the dY of block i - 1's fc2 or None)."""
+        c, T, P, S, G, st, need = self.cfg, self.T, X.P, X.S, X.G, X.st, X.need
+        B, L, D = S.B, c.L, c.D
+        dev = S.imgs.device
+        tr = self._tr
+        pre = "blocks.%d." % i
+        b = S.blocks[i]
+        S.blocks[i] = None
+        R = b.Bc * L
+        ds_a, ds_m = (None, None) if S.drop is None else S.drop[i]
+        # DropPath skipping (see forward): the dY rows of a dropped sample are exact zeros (the LayerNorm backward / merge_bwd multiplied
+        # them by the factor), so the branch's data-gradient kernels leave them out.  The ensemble mixes samples: no skipping there.
+        sk_a = None if b.group > 0 else ds_a
+        nrp, hd = X.rc_shape
+        flat, fl = self.block_flat(X, i)
+        del X.flats[i]
+        # dyT = bf16(ds_m * dx) is emitted by the kernel that produces the final dx of this block's output: the tap
+        # LayerNorm backward, block i+1's norm1 backward (dyT_next), or the stream-merge backward
+        if i in c.taps:
+            k = c.taps.index(i)
+            tap = S.taps[k]
+            dyT = torch.empty((R, D), dtype=T, device=dev)
+            # (the LayerNorm backward kernels also sum the columns of the dxT they emit: dxT is the dY of fc2 / proj, so that
+            # sum is the layer's bias gradient -- no separate pass over dxT)
+            dx, gb = ops.layernorm_bwd(dconcat[:, k * D:(k + 1) * D], tap.x, tap.mean, tap.rstd, P["norm.weight"], dres=dx, dx=dx, dxT=dyT,
+                                       rowscale=ds_m, rows_per_sample=L, dxT_colsum=fl["fc2"])
+            G[pre + "mlp.fc2.bias"] = fl["fc2"]
+            if need("norm.weight") or need("norm.bias"):
+                X.dnorm = gb if X.dnorm is None else _add_(X.dnorm, gb)
+        elif i == c.merge_idx:
+            dx, dyT = ops.merge_bwd(T, dx, ds_m, L, B * L, D)
+        else:
+            dyT = dyT_next
+        # ---- MLP branch: x2 = x1 + s_m * fc2(gelu(fc1(LN2(x1))))
+        X.param_grads(pre + "mlp.fc2.weight", pre + "mlp.fc2.bias", dyT, b.act, fl["fc2"])
+        tr("%d.dyT" % i, dyT)
+        # (the GEMM's epilogue also sums the columns of the dpre it stores: fc1's bias gradient, no separate pass over [R, 4D])
+        dpre = ops.linear_dgrad(dyT, self.w(pre + "mlp.fc2.weight", P), gelu_aux=b.gaux, colsum_out=fl["fc1"], rowskip=ds_m, rows_per_sample=L)
+        G[pre + "mlp.fc1.bias"] = fl["fc1"]
+        tr("%d.dpre" % i, dpre)
+        X.param_grads(pre + "mlp.fc1.weight", pre + "mlp.fc1.bias", dpre, b.ln2, fl["fc1"])
+        dln2 = ops.linear_dgrad(dpre, self.w(pre + "mlp.fc1.weight", P), rowskip=ds_m, rows_per_sample=L)
+        tr("%d.dln2" % i, dln2)
+        del dpre
+        dyA = st.private(dyT)                      # dyT may still be read by the side stream: the attention branch's dY gets its own buffer
+        # (the reduction of the LayerNorm parameter-gradient partials is a parameter gradient too: side stream)
+        lnws, lndone = self.ln_workspace(dev, ops.layernorm_bwd_workspace_bytes(R, D), st.main, st.side)
+        dx, fin = ops.layernorm_bwd(dln2, b.x1, b.mean2, b.rstd2, P[pre + "norm2.weight"], dres=dx, dx=dx, dxT=dyA,
+                                    rowscale=ds_a, rows_per_sample=L, gb=fl["n2"].view(2, D), dxT_colsum=fl["proj"], defer=True, ws=lnws)
+        gb = None
+        if need(pre + "norm2.weight") or need(pre + "norm2.bias") or need(pre + "attn.proj.bias"):
+            gb = st.run(fin)
+            lndone()
+            G[pre + "norm2.weight"], G[pre + "norm2.bias"] = gb[0], gb[1]
+        G[pre + "attn.proj.bias"] = fl["proj"]
+        del dyT
+        tr("%d.dx_ln2" % i, dx); tr("%d.dyA" % i, dyA)
+        if gb is not None:
+            tr("%d.gb2" % i, gb)
+        # ---- attention branch: x1 = x0 + s_a * proj(attn(LN1(x0)))
+        if b.group > 0:
+            # SegGPT feature ensemble (forward: x1 = x0 + s_a * ens(proj(...))): the branch gradient is ens applied to s_a * dx (fp32: the
+            # kernel's own type), re-rounded to the operand type.  Column sums are unchanged by a mean + broadcast over samples, so
+            # the proj bias gradient the LayerNorm backward already summed (of s_a * dx) stands.
+            da = ops.ensemble_resid(torch.zeros_like(dx), dx if ds_a is None else ops.scale_cast(torch.float32, dx, ds_a, L), b.Bc, b.group, L, D)
+            dyA = da if T == torch.float32 else ops.cast_bf16(da, out=dyA)
+            del da
+        X.param_grads(pre + "attn.proj.weight", pre + "attn.proj.bias", dyA, b.ao, fl["proj"])
+        dao = ops.linear_dgrad(dyA, self.w(pre + "attn.proj.weight", P), out=dln2, rowskip=sk_a, rows_per_sample=L)
+        tr("%d.dao" % i, dao)
+        del dyA
+        rcatT = self.relpos(pre, P, True)
+        dqkv, dG = ops.attn_bwd_core(b.qkv, b.rcat, rcatT, b.ao, dao, b.lse, b.Bc, L, c.heads, c.Hp, c.Wp, c.scale, tables=b.atab, rowskip=sk_a)
+        if need(pre + "attn.rel_pos_h") or need(pre + "attn.rel_pos_w"):
+            # (the dQ kernel still writes its rel-pos partials / dG when the tables are frozen: only this reduction is skipped)
+            drcat = st.run(lambda: ops.attn_bwd_relpos(dG, b.qkv, nrp, b.Bc, L, c.heads, c.Hp, c.Wp, out=fl["rel"].view(nrp, hd)), dG, b.qkv)
+            nh, nw = 2 * c.Hp - 1, 2 * c.Wp - 1
+            G[pre + "attn.rel_pos_h"] = drcat[:nh]
+            G[pre + "attn.rel_pos_w"] = drcat[nh:nh + nw]
+        del dG
+        tr("%d.dqkv" % i, dqkv)
+        X.param_grads(pre + "attn.qkv.weight", pre + "attn.qkv.bias", dqkv, b.ln1, fl["qkv"])
+        dln1 = ops.linear_dgrad(dqkv, self.w(pre + "attn.qkv.weight", P), out=dao, rowskip=sk_a, rows_per_sample=L)
+        del dqkv
+        nxt = i - 1
+        if nxt >= 0 and nxt not in c.taps and nxt != c.merge_idx:
+            dyT_next = torch.empty((R, D), dtype=T, device=dev)
+        else:
             dyT_next = None
-            if nxt >= 0 and nxt not in c.taps and nxt != c.merge_idx:
-                dyT_next = torch.empty((R, D), dtype=T, device=dev)
-            ds_next = None if (S.drop is None or nxt < 0) else S.drop[nxt][1]
-            cs_next = None
-            if dyT_next is not None:               # dyT_next is block nxt's fc2 dY: its column sum goes into block nxt's flat buffer
-                cs_next = block_flat(nxt)[1]["fc2"]
-                G["blocks.%d.mlp.fc2.bias" % nxt] = cs_next
-            lnws, lndone = self.ln_workspace(dev, ops.layernorm_bwd_workspace_bytes(R, D), main, side if _SIDE_EXTRA else None)
-            dx, fin = ops.layernorm_bwd(dln1, x0, mean1, rstd1, P[pre + "norm1.weight"], dres=dx, dx=dx, dxT=dyT_next,
-                                        rowscale=ds_next if dyT_next is not None else None, rows_per_sample=L, gb=fl["n1"].view(2, D),
-                                        dxT_colsum=cs_next, defer=True, ws=lnws)
-            if need(pre + "norm1.weight") or need(pre + "norm1.bias") or (cs_next is not None and need("blocks.%d.mlp.fc2.bias" % nxt)):
-                gb = on_side(fin)
-                lndone()
-                G[pre + "norm1.weight"], G[pre + "norm1.bias"] = gb[0], gb[1]
-            tr("%d.dx_ln1" % i, dx)
-            del x0, ln1, qkv, ao, x1, ln2, gaux, act, atab
-            ready([n for n in G if n.startswith(pre)], flat=flat)
-        if dnorm is not None:
-            G["norm.weight"], G["norm.bias"] = dnorm[0], dnorm[1]
-        # ---- token assembly + patch embed
+        ds_next = None if (S.drop is None or nxt < 0) else S.drop[nxt][1]
+        cs_next = None
+        if dyT_next is not None:               # dyT_next is block nxt's fc2 dY: its column sum goes into block nxt's flat buffer
+            cs_next = self.block_flat(X, nxt)[1]["fc2"]
+            G["blocks.%d.mlp.fc2.bias" % nxt] = cs_next
+        lnws, lndone = self.ln_workspace(dev, ops.layernorm_bwd_workspace_bytes(R, D), st.main, st.side)
+        dx, fin = ops.layernorm_bwd(dln1, b.x, b.mean1, b.rstd1, P[pre + "norm1.weight"], dres=dx, dx=dx, dxT=dyT_next,
+                                    rowscale=ds_next if dyT_next is not None else None, rows_per_sample=L, gb=fl["n1"].view(2, D),
+                                    dxT_colsum=cs_next, defer=True, ws=lnws)
+        if need(pre + "norm1.weight") or need(pre + "norm1.bias") or (cs_next is not None and need("blocks.%d.mlp.fc2.bias" % nxt)):
+            gb = st.run(fin)
+            lndone()
+            G[pre + "norm1.weight"], G[pre + "norm1.bias"] = gb[0], gb[1]
+        tr("%d.dx_ln1" % i, dx)
+        del b
+        X.ready([n for n in G if n.startswith(pre)], flat=flat)
+        return dx, dyT_next
+
+    def _backward_tokens(self, X, dx, dpred_loss, want_imgs, want_tgts):
+        """Token assembly + patch embedding (and the last gradient bucket) -> (d imgs, d tgts), None where not asked for."""
+        c, T, P, S, G, need = self.cfg, self.T, X.P, X.S, X.G, X.need
+        B, L, D = S.B, c.L, c.D
+        if X.dnorm is not None:
+            G["norm.weight"], G["norm.bias"] = X.dnorm[0], X.dnorm[1]
         dpe, sums = ops.tokens_bwd(T, dx, S.mask, B, L, D)
         if need("patch_embed.proj.weight"):
             if S.cols is not None:
@@ -637,7 +674,7 @@ class HotPath:
             G["patch_embed.proj.bias"] = ops.colsum(dpe)
         if need("pos_embed"):
             dposemb = torch.zeros_like(P["pos_embed"])
-            ops.pos_bwd(self.pos_operator(dev)[1], sums[0], sums[1], dposemb[0, c.cls:], c.src * c.src, D)
+            ops.pos_bwd(self.pos_operator(S.imgs.device)[1], sums[0], sums[1], dposemb[0, c.cls:], c.src * c.src, D)
             G["pos_embed"] = dposemb
         for k_, nm in enumerate(("segment_token_x", "segment_token_y", "mask_token")):
             if need(nm):
@@ -653,36 +690,19 @@ class HotPath:
             # there: the reference's DDP wrapper would refuse the unused parameter outright.)
             types_present = set(S.seg_type.reshape(-1).tolist())
             for t_, nm in ((0.0, "type_token_cls"), (1.0, "type_token_ins")):
-                if (t_ not in types_present and sync is None) or not need(nm):
+                if (t_ not in types_present and X.sync is None) or not need(nm):
                     continue
                 w = (S.seg_type.reshape(-1) == t_).to(torch.float32)
                 sel = ops.scale_cast(torch.float32, dx, torch.cat((w, w)).contiguous(), L)
                 G[nm] = ops.colsum(sel).view(1, 1, 1, D)
                 small_tail.append(nm)
-        ready(["norm.weight", "norm.bias", "patch_embed.proj.weight", "patch_embed.proj.bias", "pos_embed",
-               "segment_token_x", "segment_token_y", "mask_token"] + small_tail)
-        dimgs = dtgts = None
-        if want_imgs or want_tgts:
-            # input gradients (pa_patch_embed_dgrad): d tgts also carries the loss's direct term, -dpred_loss
-            dimgs, dtgts = ops.patch_embed_dgrad(dpe, self.w_patch(P), B, c.Hp, c.Wp, c.P, D, want_imgs, want_tgts,
-                                                 addend=dpred_loss if want_tgts else None, alpha=-1.0)
-        del dpred_loss
-        if want is not None:
-            G = {n: g for n, g in G.items() if g is not None and n in want}
-        if side is not None:
-            if getattr(self, "tail_probe", None) is not None:      # diagnostics (tools/step_tail.py): when each stream ran dry
-                self.tail_probe[0].record(main)
-                self.tail_probe[1].record(side)
-            main.wait_stream(side)                 # every gradient is ordered before whatever the caller enqueues next
-        if keep:
-            torch.cuda.synchronize()
-            keep.clear()
-        if sync is not None:
-            sync.finish()
-        if want_imgs or want_tgts:
-            return G, dimgs, dtgts
-        return G
-
+        X.ready(["norm.weight", "norm.bias", "patch_embed.proj.weight", "patch_embed.proj.bias", "pos_embed",
+                 "segment_token_x", "segment_token_y", "mask_token"] + small_tail)
+        if not (want_imgs or want_tgts):
+            return None, None
+        # input gradients (pa_patch_embed_dgrad): d tgts also carries the loss's direct term, -dpred_loss
+        return ops.patch_embed_dgrad(dpe, self.w_patch(P), B, c.Hp, c.Wp, c.P, D, want_imgs, want_tgts,
+                                     addend=dpred_loss if want_tgts else None, alpha=-1.0)
 
 def _add_(a, b):
     """a += b for two small fp32 device tensors through the slab reducer (keeps arithmetic inside the library)."""

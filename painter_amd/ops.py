@@ -2,7 +2,7 @@
 memory (torch.empty), the current HIP stream and dtype tags; all arithmetic happens in libpainter_hip.so."""
 import torch
 
-from ._lib import (EPI_BIAS, EPI_BIAS_F32, EPI_BIAS_GELU, EPI_BIAS_RESID, PA_BF16, PA_F32, check, lib)
+from ._lib import (EPI_BIAS, EPI_BIAS_F32, EPI_BIAS_GELU, EPI_BIAS_RESID, KNOB_DECODER_ROWS, KNOB_DROP_SKIP, PA_BF16, PA_F32, check, lib)
 
 _WS = {}
 
@@ -33,6 +33,19 @@ def workspace(nbytes, device, slot=0):
     return buf
 
 
+def _mbs(mask_u8):
+    """Batch stride of a [B, L] mask; 0 for a [1, L] mask that every sample shares."""
+    return 0 if mask_u8.shape[0] == 1 else mask_u8.stride(0)
+
+
+def _knob(which, mode):
+    """-> the value found in a pa_debug_set knob; sets `mode` when given."""
+    old = int(lib.pa_debug_get(which))
+    if mode is not None:
+        check(lib.pa_debug_set(which, int(mode)), "pa_debug_set")
+    return old
+
+
 def _req(t, dtype=None):
     assert t.is_cuda and t.stride(-1) == 1, "device tensor with unit inner stride required"
     if dtype is not None:
@@ -42,7 +55,8 @@ def _req(t, dtype=None):
 
 # ------------------------------------------------------------------------------------------- linear
 def _skip_args(rowskip, skip_rows_per_sample, M):
-    """DropPath skipping (include/painter_hip.h, ABI 7): rowskip = the branch's factor vector, f32 [M / skip_rows_per_sample]."""
+    """DropPath skipping (include/painter_hip.h, ABI 7): rowskip = the branch's factor vector, f32 [M / skip_rows_per_sample].
+    None -> a null pointer: the *_skip entry points then are the plain ones."""
     if rowskip is None:
         return 0, 1
     assert rowskip.dtype == torch.float32 and rowskip.is_cuda and rowskip.is_contiguous() and skip_rows_per_sample >= 1
@@ -53,10 +67,7 @@ def _skip_args(rowskip, skip_rows_per_sample, M):
 def drop_skip(mode=None):
     """The run-time switch of DropPath skipping (pa_debug_set knob 16): 0 default (on unless PAINTER_AMD_DROP_SKIP=0), 1 off, 2 on.
     -> the value found; sets `mode` when given."""
-    old = int(lib.pa_debug_get(16))
-    if mode is not None:
-        check(lib.pa_debug_set(16, int(mode)), "pa_debug_set")
-    return old
+    return _knob(KNOB_DROP_SKIP, mode)
 
 
 def linear_fwd(x, w, bias, epilogue=EPI_BIAS, out=None, out2=None, resid=None, rowscale=None, rows_per_sample=1, *, rowskip=None,
@@ -74,13 +85,9 @@ def linear_fwd(x, w, bias, epilogue=EPI_BIAS, out=None, out2=None, resid=None, r
         out = torch.empty((M, N), dtype=odt, device=x.device)
     if epilogue == EPI_BIAS_RESID:
         assert resid is not None and resid.dtype == torch.float32 and resid.stride(0) == out.stride(0)
-    if rowskip is None:
-        check(lib.pa_linear_fwd(code(T), epilogue, p(x), x.stride(0), p(w), p(bias), p(out), p(out2), out.stride(0),
-                                p(resid), p(rowscale), rows_per_sample, M, N, K, stream()), "pa_linear_fwd")
-    else:
-        sk, srps = _skip_args(rowskip, rows_per_sample if skip_rows_per_sample is None else skip_rows_per_sample, M)
-        check(lib.pa_linear_fwd_skip(code(T), epilogue, p(x), x.stride(0), p(w), p(bias), p(out), p(out2), out.stride(0),
-                                     p(resid), p(rowscale), rows_per_sample, M, N, K, sk, srps, stream()), "pa_linear_fwd_skip")
+    sk, srps = _skip_args(rowskip, rows_per_sample if skip_rows_per_sample is None else skip_rows_per_sample, M)
+    check(lib.pa_linear_fwd_skip(code(T), epilogue, p(x), x.stride(0), p(w), p(bias), p(out), p(out2), out.stride(0),
+                                 p(resid), p(rowscale), rows_per_sample, M, N, K, sk, srps, stream()), "pa_linear_fwd_skip")
     return out
 
 
@@ -153,13 +160,9 @@ def linear_dgrad(dy, w, gelu_aux=None, out=None, colsum_out=None, *, rowskip=Non
     if colsum_out is not None:
         assert colsum_out.shape == (K,) and colsum_out.dtype == torch.float32 and colsum_out.is_contiguous()
         ws = workspace(lib.pa_linear_dgrad_workspace_bytes(M, K), dy.device, slot=2)
-    if rowskip is None:
-        check(lib.pa_linear_dgrad(code(T), p(dy), dy.stride(0), p(w), p(gelu_aux), p(out), out.stride(0), p(colsum_out), p(ws), M, N, K, stream()),
-              "pa_linear_dgrad")
-    else:
-        sk, srps = _skip_args(rowskip, rows_per_sample, M)
-        check(lib.pa_linear_dgrad_skip(code(T), p(dy), dy.stride(0), p(w), p(gelu_aux), p(out), out.stride(0), p(colsum_out), p(ws), M, N, K,
-                                       sk, srps, stream()), "pa_linear_dgrad_skip")
+    sk, srps = _skip_args(rowskip, rows_per_sample, M)
+    check(lib.pa_linear_dgrad_skip(code(T), p(dy), dy.stride(0), p(w), p(gelu_aux), p(out), out.stride(0), p(colsum_out), p(ws), M, N, K,
+                                   sk, srps, stream()), "pa_linear_dgrad_skip")
     return out
 
 
@@ -169,15 +172,7 @@ def linear_wgrad(dy, x, out=None, *, live=None):
     roundup(count, 128)); the live rows of X are gathered into the same form and the contraction runs over them alone."""
     if live is not None:
         lv, count = live
-        xc = gather_rows(x, lv, count)
-        Mp, N = dy.shape
-        K = x.shape[1]
-        _req(dy, torch.bfloat16); _req(xc, torch.bfloat16)
-        assert xc.shape[0] == Mp and Mp % 128 == 0
-        if out is None:
-            out = torch.empty((N, K), dtype=torch.float32, device=dy.device)
-        check(lib.pa_linear_wgrad_live(p(dy), dy.stride(0), p(xc), xc.stride(0), p(out), p(count), Mp, N, K, stream()), "pa_linear_wgrad_live")
-        return out
+        return linear_wgrad_live(dy, gather_rows(x, lv, count), count, out=out)
     M, N = dy.shape
     K = x.shape[1]
     T = dy.dtype
@@ -203,10 +198,7 @@ def colsum(x, out=None):
 def decoder_rows(mode=None):
     """The run-time switch of the live-row decoder backward (pa_debug_set knob 17): 0 default (on unless PAINTER_AMD_DECODER_ROWS=0), 1 off,
     2 on.  -> the value found; sets `mode` when given."""
-    old = int(lib.pa_debug_get(17))
-    if mode is not None:
-        check(lib.pa_debug_set(17, int(mode)), "pa_debug_set")
-    return old
+    return _knob(KNOB_DECODER_ROWS, mode)
 
 
 def decoder_live_ok(T, batch, Hp, Wp, P, Kin):
@@ -220,10 +212,9 @@ def live_rows(mask_u8, batch, Hp, Wp):
     n = batch * Hp * Wp
     assert mask_u8.dtype in (torch.uint8, torch.bool) and mask_u8.is_cuda and mask_u8.stride(-1) == 1 and mask_u8.shape[-1] == Hp * Wp
     assert mask_u8.shape[0] in (1, batch)
-    mbs = 0 if mask_u8.shape[0] == 1 else mask_u8.stride(0)
     buf = torch.empty((2 * n + 1,), dtype=torch.int32, device=mask_u8.device)
     rowmap, live, count = buf[:n], buf[n:2 * n], buf[2 * n:]
-    check(lib.pa_live_rows(p(mask_u8), mbs, p(rowmap), p(live), p(count), batch, Hp, Wp, stream()), "pa_live_rows")
+    check(lib.pa_live_rows(p(mask_u8), _mbs(mask_u8), p(rowmap), p(live), p(count), batch, Hp, Wp, stream()), "pa_live_rows")
     return rowmap, live, count
 
 
@@ -369,12 +360,8 @@ def attn_fwd(qkv, rcat, batch, L, heads, Hp, Wp, scale, need_tables=False, *, ro
         nb = lib.pa_attn_tables_bytes(code(T), batch, L, heads, Hp, Wp, hd)
         if nb > 0:
             tables = torch.empty((nb,), dtype=torch.uint8, device=qkv.device)
-    if rowskip is None:
-        check(lib.pa_attn_fwd(code(T), p(qkv), qkv.stride(0), p(rcat), p(out), out.stride(0), p(lse), p(tables), batch, L, heads,
-                              Hp, Wp, hd, float(scale), stream()), "pa_attn_fwd")
-    else:
-        check(lib.pa_attn_fwd_skip(code(T), p(qkv), qkv.stride(0), p(rcat), p(out), out.stride(0), p(lse), p(tables), batch, L, heads,
-                                   Hp, Wp, hd, float(scale), _skip_args(rowskip, 1, batch)[0], stream()), "pa_attn_fwd_skip")
+    check(lib.pa_attn_fwd_skip(code(T), p(qkv), qkv.stride(0), p(rcat), p(out), out.stride(0), p(lse), p(tables), batch, L, heads,
+                               Hp, Wp, hd, float(scale), _skip_args(rowskip, 1, batch)[0], stream()), "pa_attn_fwd_skip")
     return (out, lse, tables) if need_tables else (out, lse)
 
 
@@ -428,14 +415,9 @@ def attn_bwd_core(qkv, rcat, rcatT, out, dout, lse, batch, L, heads, Hp, Wp, sca
     else:
         dG = torch.empty((batch * L, heads * nrp), dtype=T, device=dev)
     aux = workspace(lib.pa_attn_bwd_aux_bytes(batch, L, heads, Hp, Wp), dev, slot=1)
-    if rowskip is None:
-        check(lib.pa_attn_bwd(code(T), p(qkv), qkv.stride(0), p(rcat), p(rcatT), p(dout), dout.stride(0), p(lse), p(delta),
-                              p(dqkv), p(dG), p(part), p(aux), p(tables), p(o_arg), 0 if o_arg is None else o_arg.stride(0), batch, L, heads, Hp, Wp, hd,
-                              float(scale), stream()), "pa_attn_bwd")
-    else:
-        check(lib.pa_attn_bwd_skip(code(T), p(qkv), qkv.stride(0), p(rcat), p(rcatT), p(dout), dout.stride(0), p(lse), p(delta),
-                                   p(dqkv), p(dG), p(part), p(aux), p(tables), p(o_arg), 0 if o_arg is None else o_arg.stride(0), batch, L, heads, Hp, Wp,
-                                   hd, float(scale), _skip_args(rowskip, 1, batch)[0], stream()), "pa_attn_bwd_skip")
+    check(lib.pa_attn_bwd_skip(code(T), p(qkv), qkv.stride(0), p(rcat), p(rcatT), p(dout), dout.stride(0), p(lse), p(delta),
+                               p(dqkv), p(dG), p(part), p(aux), p(tables), p(o_arg), 0 if o_arg is None else o_arg.stride(0), batch, L, heads, Hp, Wp,
+                               hd, float(scale), _skip_args(rowskip, 1, batch)[0], stream()), "pa_attn_bwd_skip")
     return dqkv, (dG if part is None else part)
 
 
@@ -499,10 +481,9 @@ def patch_embed_fwd(T, imgs, tgts, w, bias, mask_token, seg_x, seg_y, pos, mask_
                     batch, Hp, Wp, P, D):
     """w: T [D, ldw] as patch_weight_pack returns it (a plain [D, 3*P*P] T copy is the same thing when P % 8 == 0)."""
     tokens = torch.empty((2 * batch * Hp * Wp, D), dtype=torch.float32, device=imgs.device)
-    mbs = 0 if mask_u8.shape[0] == 1 else mask_u8.stride(0)
     assert w.dtype == T and w.shape[0] == D and w.stride(1) == 1
     check(lib.pa_patch_embed_fwd(code(T), p(imgs), p(tgts), p(w), w.stride(0), p(bias), p(mask_token), p(seg_x), p(seg_y), p(pos),
-                                 p(mask_u8), mbs, p(type_cls), p(type_ins), p(seg_type), p(tokens), batch, Hp, Wp, P, D,
+                                 p(mask_u8), _mbs(mask_u8), p(type_cls), p(type_ins), p(seg_type), p(tokens), batch, Hp, Wp, P, D,
                                  stream()), "pa_patch_embed_fwd")
     return tokens
 
@@ -521,9 +502,8 @@ def patch_im2col(imgs, tgts, batch, Hp, Wp, P):
 
 def patch_embed_fwd_cols(cols, w, bias, mask_token, seg_x, seg_y, pos, mask_u8, type_cls, type_ins, seg_type, batch, L, D):
     tokens = torch.empty((2 * batch * L, D), dtype=torch.float32, device=cols.device)
-    mbs = 0 if mask_u8.shape[0] == 1 else mask_u8.stride(0)
     assert w.dtype == torch.bfloat16 and w.shape[0] == D and w.stride(1) == 1 and cols.is_contiguous()
-    check(lib.pa_patch_embed_fwd_cols(p(cols), p(w), w.stride(0), p(bias), p(mask_token), p(seg_x), p(seg_y), p(pos), p(mask_u8), mbs,
+    check(lib.pa_patch_embed_fwd_cols(p(cols), p(w), w.stride(0), p(bias), p(mask_token), p(seg_x), p(seg_y), p(pos), p(mask_u8), _mbs(mask_u8),
                                       p(type_cls), p(type_ins), p(seg_type), p(tokens), batch, L, cols.shape[1], D, stream()), "pa_patch_embed_fwd_cols")
     return tokens
 
@@ -554,8 +534,7 @@ def patch_embed_dgrad(dpe, w, batch, Hp, Wp, P, D, want_imgs=True, want_tgts=Tru
 def tokens_bwd(T, dx0, mask_u8, batch, L, D):
     dpe = torch.empty((2 * batch * L, D), dtype=T, device=dx0.device)
     sums = torch.empty((3, L, D), dtype=torch.float32, device=dx0.device)
-    mbs = 0 if mask_u8.shape[0] == 1 else mask_u8.stride(0)
-    check(lib.pa_tokens_bwd(code(T), p(dx0), p(mask_u8), mbs, p(dpe), p(sums), batch, L, D, stream()), "pa_tokens_bwd")
+    check(lib.pa_tokens_bwd(code(T), p(dx0), p(mask_u8), _mbs(mask_u8), p(dpe), p(sums), batch, L, D, stream()), "pa_tokens_bwd")
     return dpe, sums
 
 
@@ -637,8 +616,7 @@ def loss_fwd(pred, tgts, valid, mask_u8, P, ignore_rule, eps_den, kind, beta=0.0
     B, _, Hi, Wi = pred.shape
     out = torch.empty((2,), dtype=torch.float32, device=pred.device)
     ws = workspace(lib.pa_loss_workspace_bytes(B, Hi, Wi), pred.device)
-    mbs = 0 if mask_u8.shape[0] == 1 else mask_u8.stride(0)
-    check(lib.pa_loss_fwd(p(pred), p(tgts), p(valid), p(mask_u8), mbs, p(out), p(ws), B, Hi, Wi, P, int(ignore_rule),
+    check(lib.pa_loss_fwd(p(pred), p(tgts), p(valid), p(mask_u8), _mbs(mask_u8), p(out), p(ws), B, Hi, Wi, P, int(ignore_rule),
                           float(eps_den), LOSS_KINDS[kind], float(beta), stream()), "pa_loss_fwd")
     return out
 
@@ -646,8 +624,7 @@ def loss_fwd(pred, tgts, valid, mask_u8, P, ignore_rule, eps_den, kind, beta=0.0
 def loss_bwd(pred, tgts, valid, mask_u8, dloss, loss_out, P, kind, beta=0.01):
     B, _, Hi, Wi = pred.shape
     dpred = torch.empty_like(pred)
-    mbs = 0 if mask_u8.shape[0] == 1 else mask_u8.stride(0)
-    check(lib.pa_loss_bwd(p(pred), p(tgts), p(valid), p(mask_u8), mbs, p(dloss), p(loss_out), p(dpred), B, Hi, Wi, P,
+    check(lib.pa_loss_bwd(p(pred), p(tgts), p(valid), p(mask_u8), _mbs(mask_u8), p(dloss), p(loss_out), p(dpred), B, Hi, Wi, P,
                           LOSS_KINDS[kind], float(beta), stream()), "pa_loss_bwd")
     return dpred
 
@@ -660,8 +637,7 @@ def pred_bwd(pred, tgts, valid, mask_u8, dloss, loss_out, dpatch, P, kind, want_
     dpred_loss = torch.empty_like(pred) if want_loss_term else None
     if dpatch is not None:
         assert dpatch.shape == (B, (Hi // P) * (Wi // P), 3 * P * P) and dpatch.dtype == torch.float32 and dpatch.is_contiguous()
-    mbs = 0 if mask_u8.shape[0] == 1 else mask_u8.stride(0)
-    check(lib.pa_pred_bwd(p(pred), p(tgts), p(valid), p(mask_u8), mbs, p(dloss), p(loss_out), p(dpatch), p(dpred), p(dpred_loss), B, Hi, Wi,
+    check(lib.pa_pred_bwd(p(pred), p(tgts), p(valid), p(mask_u8), _mbs(mask_u8), p(dloss), p(loss_out), p(dpatch), p(dpred), p(dpred_loss), B, Hi, Wi,
                           P, LOSS_KINDS[kind], float(beta), stream()), "pa_pred_bwd")
     return dpred, dpred_loss
 

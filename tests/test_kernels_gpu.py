@@ -958,6 +958,33 @@ def test_c_abi_of_the_hot_path_rejects_bad_shapes_instead_of_reading_out_of_boun
     torch.cuda.synchronize()
 
 
+def test_debug_knobs_are_one_table_without_aliasing():
+    """pa_debug_get returns what pa_debug_set stored, for every index 0 .. 17, and no other index moves with it (round 5 let two knobs
+    share an index: tools that swept one silently switched the other); an index outside the table is an error for set and -1 for get."""
+    from painter_amd import _lib
+    from painter_amd._lib import lib
+    n = _lib.KNOB_COUNT
+    assert n == 18
+    saved = [lib.pa_debug_get(k) for k in range(n)]
+    try:
+        assert all(v != -1 for v in saved)
+        for k in range(n):
+            before = [lib.pa_debug_get(j) for j in range(n)]
+            assert lib.pa_debug_set(k, 1000 + k) == 0
+            after = [lib.pa_debug_get(j) for j in range(n)]
+            assert after[k] == 1000 + k
+            assert after[:k] + after[k + 1:] == before[:k] + before[k + 1:], k
+        for bad in (n, -1, 99):
+            assert lib.pa_debug_set(bad, 1) != 0 and lib.pa_debug_get(bad) == -1
+        assert [lib.pa_debug_get(j) for j in range(n)] == [1000 + j for j in range(n)]
+    finally:
+        for k, v in enumerate(saved):
+            lib.pa_debug_set(k, v)
+    names = {k: v for k, v in vars(_lib).items() if k.startswith("KNOB_") and k != "KNOB_COUNT"}
+    assert len(set(names.values())) == len(names) and all(0 <= v < n for v in names.values())
+    assert (_lib.KNOB_WGRAD_TARGET, _lib.KNOB_RELPOS_SPLITS, _lib.KNOB_DROP_SKIP, _lib.KNOB_DECODER_ROWS) == (3, 6, 16, 17)
+
+
 # ------------------------------------------------------------------------------------------------ glue and loss kernels at full width
 def _glue_widths():
     """(batch, L, D) of the two timed configurations: ViT-L (bench.py's per-GPU batch 8) and ViT-H/14 (per-GPU batch 4)."""

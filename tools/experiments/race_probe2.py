@@ -1,3 +1,4 @@
+# Kept as the record, not maintained: last ran against commit 5793597 (it drives HotPath.side_filter, which the engine no longer has).
 """Run-to-run determinism of the two-stream backward with / without an initialised (but unused) RCCL process group."""
 import os
 import sys

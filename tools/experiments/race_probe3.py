@@ -1,3 +1,4 @@
+# Kept as the record, not maintained: last ran against commit 5793597 (it drives HotPath.side_filter, which the engine no longer has).
 """With an initialised process group (host jitter), trace the backward's intermediate checksums in two-stream mode against the
 single-stream reference and report the first diverging intermediate of every failing run."""
 import os

@@ -73,7 +73,6 @@ for s in "$@"; do
                python tools/pmc_traffic.py gpurun_out/pmc_FETCH_SIZE gpurun_out/pmc_WRITE_SIZE gpurun_out/roofline_traffic.json > gpurun_out/pmc_traffic.log 2>&1; echo "traffic rc=$?"
                rm -rf gpurun_out/pmc_FETCH_SIZE gpurun_out/pmc_WRITE_SIZE ;;
     adopt)     cp gpurun_out/roofline_traffic.json profiles/roofline_traffic.json && echo "adopted the PMC traffic of this library for the bench line of this visit" ;;
-    engab)     timeout 600 python tools/step_engine_ab.py 5 6 "delta in dQ + colsum in epilogue (default):_ATTN_PREP=fused,_FC1_COLSUM=epilogue" "prep launch:_ATTN_PREP=launch,_FC1_COLSUM=epilogue" "separate fc1 column sums:_ATTN_PREP=fused,_FC1_COLSUM=separate" > gpurun_out/engab.log 2>&1; echo "engab rc=$?"; tail -4 gpurun_out/engab.log ;;
     libab)     timeout 900 python tools/step_lib_ab.py 3 6 "round-5 build=painter_amd/lib/libpainter_hip.so" "baseline build=painter_amd/lib/libpainter_hip_base.so" > gpurun_out/libab.log 2>&1; echo "libab rc=$?"; tail -4 gpurun_out/libab.log ;;
     r5quick)   timeout 600 python -m pytest tests/test_kernels_gpu.py tests/test_model_gpu.py -m gpu -q -s -x -k "conv64 or decoder_tail or small or vitl_b8 or vit_large_b8 or gemm256" > gpurun_out/r5quick.log 2>&1; echo "r5quick rc=$?"; grep -a "passed\|failed\|rror" gpurun_out/r5quick.log | tail -5 ;;
     r6attn)    timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_model_gpu.py -m gpu -q -s -x -k "attn or vit_large or small_painter or small_seggpt" > gpurun_out/r6attn.log 2>&1; echo "r6attn rc=$?"; grep -a "passed\|failed\|rror\|worst" gpurun_out/r6attn.log | tail -12 ;;
@@ -101,7 +100,6 @@ for s in "$@"; do
     lnfwdab)   timeout 600 python tools/step_knob_ab.py 4 6 "LN forward, persistent waves (round 6):13=1" "one row per wave (round 5):13=0" > gpurun_out/lnfwdab.log 2>&1; echo "lnfwdab rc=$?"; tail -3 gpurun_out/lnfwdab.log ;;
     livey)     timeout 1200 python -m pytest tests/test_live_yardstick_gpu.py tests/test_model_gpu.py -m gpu -q -s -k "live_yardstick or h14" > gpurun_out/livey.log 2>&1; echo "livey rc=$?"; grep -v amdgpu.ids gpurun_out/livey.log | grep "head_dim 80\|h14.*bf16\|train_one_epoch at\|passed\|failed\|Error\|assert" | cut -c1-1500 ;;
     packtests) timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_model_gpu.py tests/test_optim_gpu.py tests/test_parallel_gpu.py -m gpu -q -x -k "relpos or attn_fwd or small or weight_cache or seggpt or vit_large_b8 or GradSync or broadcast" > gpurun_out/packtests.log 2>&1; echo "packtests rc=$?"; tail -3 gpurun_out/packtests.log ;;
-    packab)    timeout 900 python tools/step_engine_ab.py 4 6 "one launch for all blocks, every step (round 6):_RELPOS_PACK=batch,REPACK=1" "48 launches, every step (training, rounds 1-5):_RELPOS_PACK=per_block,REPACK=1" "tables kept across steps (bench, rounds 4-5):_RELPOS_PACK=per_block,REPACK=0" > gpurun_out/packab.log 2>&1; echo "packab rc=$?"; tail -4 gpurun_out/packab.log ;;
     energy)    timeout 600 python tools/energy_by_family.py 2.0 > gpurun_out/energy.log 2>&1; echo "energy rc=$?"; grep -v amdgpu.ids gpurun_out/energy.log ;;
     deltaprobe) timeout 300 python tools/attn_delta_probe.py > gpurun_out/deltaprobe.log 2>&1; echo "deltaprobe rc=$?"; cat gpurun_out/deltaprobe.log ;;
     *)         echo "unknown section $s" ;;
