@@ -481,6 +481,41 @@ int pa_painter_decode_f64(const float* pred, const pa_decode_job* jobs, int n_jo
  * palette: float32 [n_colours][3]. */
 int pa_palette_argmin(const void* image, const float* palette, void* out_i32, int h, int w, int n_colours, int dist_type,
                       hipStream_t stream);
+/* Class-agnostic instance decode: coco_panoptic/COCOCAInstSegEvaluatorCustom.py:252-354 (post_process_segm_output_by_threshold, the
+ * evaluator's default `--post_type threshold`) followed by util/matrix_nms.py:5-121 (mask_matrix_nms), csrc/painter_inst.hip.
+ * image: uint8 [h][w][3]; palette: DEVICE float32 [n_colours][3] of integer values 0..255 (define_colors_per_location_r_gb, :42-67, without
+ * the background row); thresholds: DEVICE float32 [n_thr].  Candidate t * n_colours + c is the mask  float(L1) / 3.0f < thresholds[t]
+ * (:288-290), L1 = sum over channels of |pixel - colour|, with n pixels and S = sum of L1 over them; maskness = S / (3 n) (:296).
+ * Where the reference leaves ties to float32 rounding and an unspecified sort, this path defines them: n, S, areas and intersections are
+ * exact integers; the first sort (:319) compares S1 * n2 with S2 * n1 in int64, ties to the lower candidate index; the sorts of
+ * matrix_nms.py:53 and :112 are descending, ties to the earlier position; the NMS arithmetic (:67-99) is float64; scores leave as float32.
+ * Capacities: h, w <= 16384, h * w <= 2^24, n_thr <= 8, n_thr * n_colours <= 65536, nms_pre <= 4096, max_num <= nms_pre.  Null pointers,
+ * sizes < 1 or sizes beyond a capacity return hipErrorInvalidValue before anything is launched. */
+/* host only: bytes of the workspace of pa_inst_decode, -1 for bad arguments.  ~ nms_pre * h * w / 8 (bit masks) + 4 * nms_pre^2
+ * (intersections) + 16 * n_thr * n_colours. */
+int64_t pa_inst_workspace_bytes(int h, int w, int n_colours, int n_thr, int nms_pre);
+/* host only, for tests and tools: byte offset of a section of that workspace after a decode.  0: n, uint32 [n_thr * n_colours];
+ * 1: S, uint64 [n_thr * n_colours]; 2: int32 {live candidates, survivors}; 3: survivors' candidate indices in NMS order, int32 [nms_pre];
+ * 4: their areas, int32; 5: their scores before the NMS, float64; 6: their bit masks, uint32 [nms_pre][stride]; 7: intersections,
+ * int32 [nms_pre][nms_pre], defined for i < j < survivors; 8: scores after the NMS, float64; 9: not an offset, the stride of section 6 in
+ * words (words rounded up to a multiple of 4). */
+int64_t pa_inst_workspace_offset(int h, int w, int n_colours, int n_thr, int nms_pre, int section);
+/* :288-296, the first stage alone: n_u32 = uint32 [n_thr][n_colours], s_u64 = uint64 [n_thr][n_colours] (both cleared first). */
+int pa_inst_stats(const void* image, const float* palette, const float* thresholds, void* n_u32, void* s_u64, int h, int w, int n_colours,
+                  int n_thr, hipStream_t stream);
+/* matrix_nms.py:65-67 on bit masks: masks_u32 = uint32 [n_rows][words], bit b of word k = pixel 32 k + b, words a multiple of 4, 16-byte
+ * aligned; inter_i32 = int32 [n_rows][ld] (cleared first), inter[i][j] = shared pixels for i < j, and for every i, j inside a diagonal
+ * 64 x 64 tile; the rest of the lower triangle stays 0. */
+int pa_inst_intersections(const void* masks_u32, int n_rows, int words, void* inter_i32, int ld, hipStream_t stream);
+/* The whole decode, nothing but launches on `stream`.  nms_pre: the literal 2000 of :318; max_num: 100 of :332; kernel: 0 gaussian
+ * (exp(-sigma iou^2), :333), 1 linear; workspace: pa_inst_workspace_bytes, 256-byte aligned.  DEVICE outputs: out_count int32 [1] =
+ * number of instances n <= max_num (0: no candidate -- the reference then reports ONE all-zero mask with score 0 and label 0, :302-310,
+ * which callers restate); out_scores float32 [max_num]; out_scores_f64 float64 [max_num] before the cast, or NULL; out_candidates int32
+ * [max_num] = t * n_colours + c; out_masks uint32 [max_num][ceil(h * w / 32)]; out_masks_u8 uint8 [max_num][h * w], the same masks with one
+ * byte (0 / 1) per pixel, or NULL.  Entries past n are 0. */
+int pa_inst_decode(const void* image, const float* palette, const float* thresholds, int h, int w, int n_colours, int n_thr, int nms_pre,
+                   int max_num, float sigma, int kernel, void* workspace, void* out_count, float* out_scores, void* out_scores_f64,
+                   void* out_candidates, void* out_masks, void* out_masks_u8, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -22,8 +22,10 @@ if os.environ.get("PA_SLP") != "1":
     FLAGS = FLAGS + ["-fno-slp-vectorize"]
 FLAGS = FLAGS + os.environ.get("PA_EXTRA_FLAGS", "").split()
 # seggpt_io.hip / pair_io.hip / painter_io.hip reproduce host float arithmetic (numpy, Pillow, CPU torch) bit for bit: no fused
-# multiply-add there except the explicit fma() calls of painter_io.hip's bilinear resize.
-EXTRA = {"seggpt_io.hip": ["-ffp-contract=off"], "pair_io.hip": ["-ffp-contract=off"], "painter_io.hip": ["-ffp-contract=off"]}
+# multiply-add there except the explicit fma() calls of painter_io.hip's bilinear resize.  painter_inst.hip: its float64 NMS arithmetic
+# is stated operation by operation (tests/painter_inst_host.py).
+EXTRA = {"seggpt_io.hip": ["-ffp-contract=off"], "pair_io.hip": ["-ffp-contract=off"], "painter_io.hip": ["-ffp-contract=off"],
+         "painter_inst.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

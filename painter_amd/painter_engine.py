@@ -14,15 +14,20 @@ The uint8 / int32 outputs are the bytes the scripts write (tests/test_painter_ev
 the digests the unmodified scripts produced); the float64 output of the three restoration tasks agrees with CPU torch's bicubic to
 ~1e-13 (torch's own operation order is not reproduced there).
 
+`instances` / `PainterEngine.run_instances` decode a painted `coco_pano_inst` picture into class-agnostic instances on the device
+(csrc/painter_inst.hip): the evaluator's threshold route and its Matrix NMS (COCOCAInstSegEvaluatorCustom.py:252-354,
+util/matrix_nms.py) on exact integers and bit masks, ties defined (tests/painter_inst_host.py is the definition).
+
 Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
 (`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
 `cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
 canvases the script built, or pass an already resized 448 x 448 uint8 query to `run`); PSNR / SSIM; the detectron2 / mmpose
-evaluators apart from the colour -> class decode (`class_map`).
+evaluators apart from the colour -> class decode (`class_map`) and the instance decode (`instances`).
 
 There is no CPU fallback: a CPU device or a missing libpainter_hip.so raises.
 """
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -159,6 +164,91 @@ def class_map(picture, palette, dist_type="abs", device="cuda"):
     return out.cpu().numpy()
 
 
+NMS_KERNELS = {"gaussian": 0, "linear": 1}
+
+
+@functools.lru_cache(maxsize=4)
+def location_palette(num_location_r=16, num_location_gb=20):
+    """The colours the `coco_pano_inst` targets are painted with, one per location, as float32 [16 * num_location_gb^2][3] without the
+    background row (define_colors_per_location_r_gb, COCOCAInstSegEvaluatorCustom.py:42-67): red steps down by 255 // num_location_r
+    per cell of the 4 x 4 global grid (row-major), green by 256 // num_location_gb + 1 per local row, blue by the same per local column."""
+    sep_r, sep_gb = 255 // num_location_r, 256 // num_location_gb + 1
+    cell, y, x = np.meshgrid(np.arange(16), np.arange(num_location_gb), np.arange(num_location_gb), indexing="ij")
+    pal = np.stack([255 - cell * sep_r, 255 - y * sep_gb, 255 - x * sep_gb], -1).reshape(-1, 3)
+    assert pal.min() >= 0 and len({tuple(c) for c in pal.tolist()}) == len(pal)
+    pal = pal.astype(np.float32)
+    pal.setflags(write=False)                  # cached: every caller sees the same array
+    return pal
+
+
+class InstanceDecode:
+    """One launched pa_inst_decode: every output sits in ONE device buffer, so `result()` is one copy back and one synchronisation."""
+
+    def __init__(self, picture, palette, thresholds, nms_pre, max_num, kernel, sigma):
+        if kernel not in NMS_KERNELS:
+            raise NotImplementedError("%s kernel is not supported in matrix nms!" % kernel)
+        self.img = img = picture
+        dev = img.device
+        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.is_contiguous(), (img.dtype, tuple(img.shape))
+        pal = np.ascontiguousarray(np.asarray(location_palette() if palette is None else palette, dtype=np.float32))
+        assert pal.ndim == 2 and pal.shape[1] == 3 and (pal == np.floor(pal)).all() and pal.min() >= 0 and pal.max() <= 255, \
+            "painter_engine: the palette holds integer colours 0..255"
+        thr = np.atleast_1d(np.asarray(thresholds, dtype=np.float32))
+        self.h, self.w, self.k, self.n_thr = int(img.shape[0]), int(img.shape[1]), int(pal.shape[0]), int(thr.size)
+        self.nms_pre, self.max_num = int(nms_pre), int(max_num)
+        self.words = (self.h * self.w + 31) // 32
+        shape = (self.h, self.w, self.k, self.n_thr, self.nms_pre)
+        nbytes = lib.pa_inst_workspace_bytes(*shape)
+        if nbytes < 0 or self.max_num < 1 or self.max_num > self.nms_pre:
+            check(1, "pa_inst_decode (sizes %s, max_num %d)" % (shape, self.max_num))
+        self.shape = shape
+        self.params = torch.from_numpy(np.concatenate([pal.ravel(), thr])).to(dev, non_blocking=True)
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        m, hw = self.max_num, self.h * self.w
+        # ONE byte buffer: int32 count | float64 scores [m] | float32 scores [m] | int32 candidates [m] | bit masks [m][words] | byte masks [m][h * w]
+        self.o64, self.o32, self.oidx, self.obits = 8, 8 + 8 * m, 8 + 12 * m, 8 + 16 * m
+        self.obytes = self.obits + 4 * m * self.words
+        self.out = torch.zeros(self.obytes + m * hw, dtype=torch.uint8, device=dev)
+        at = lambda off: self.out.data_ptr() + off
+        check(lib.pa_inst_decode(img.data_ptr(), self.params.data_ptr(), self.params.data_ptr() + 4 * pal.size, self.h, self.w, self.k,
+                                 self.n_thr, self.nms_pre, m, float(sigma), NMS_KERNELS[kernel], self.workspace.data_ptr(), at(0),
+                                 at(self.o32), at(self.o64), at(self.oidx), at(self.obits), at(self.obytes), _stream()), "pa_inst_decode")
+
+    def section(self, which, dtype, count):
+        """A section of the workspace (pa_inst_workspace_offset) as a numpy array: for tests and tools."""
+        off = lib.pa_inst_workspace_offset(*self.shape, which)
+        return self.workspace[off:off + count * np.dtype(dtype).itemsize].cpu().numpy().view(dtype)
+
+    def result(self, with_f64=False, with_bits=False):
+        """The copy back (and the one synchronisation).  The bool masks are a view of the bytes the device wrote."""
+        a = self.out.cpu().numpy()
+        n, m, hw = int(a[:4].view(np.int32)[0]), self.max_num, self.h * self.w
+        if n == 0:              # no candidate: the reference's single all-zero mask with score 0 and label 0 (:302-310)
+            res = dict(scores=np.zeros(1, np.float32), labels=np.zeros(1, np.float32), masks=np.zeros((1, self.h, self.w), bool),
+                       candidates=np.full(1, -1, np.int32))
+            if with_f64:
+                res["scores_f64"] = np.zeros(1)
+            return res
+        res = dict(scores=a[self.o32:self.o32 + 4 * n].view(np.float32), labels=np.ones(n, np.float32),
+                   masks=a[self.obytes:self.obytes + n * hw].view(bool).reshape(n, self.h, self.w),
+                   candidates=a[self.oidx:self.oidx + 4 * n].view(np.int32))
+        if with_f64:
+            res["scores_f64"] = a[self.o64:self.o64 + 8 * n].view(np.float64)
+        if with_bits:
+            res["bits"] = a[self.obits:self.obits + 4 * m * self.words].view(np.uint32).reshape(m, self.words)[:n]
+        return res
+
+
+def instances(picture, palette=None, dist_thr=19.0, nms_pre=2000, max_num=100, kernel="gaussian", sigma=2.0, device="cuda"):
+    """COCOCAInstSegEvaluatorCustom.post_process_segm_output_by_threshold (:252-354) with mask_matrix_nms (util/matrix_nms.py:5-121):
+    uint8 [H][W][3] picture (numpy or CUDA tensor), palette [K][3] (default `location_palette()`), dist_thr a threshold or a list of them
+    -> dict(scores float32 [n], labels float32 [n], masks bool [n][H][W], candidates int32 [n] = t * K + c of each instance).
+    Ties are defined (include/painter_hip.h): exact integer statistics, rational maskness order, stable sorts, float64 NMS."""
+    device = _require_cuda(picture.device if torch.is_tensor(picture) else device)
+    img = picture if torch.is_tensor(picture) else torch.from_numpy(np.ascontiguousarray(picture)).to(device)
+    return InstanceDecode(img, palette, dist_thr, nms_pre, max_num, kernel, sigma).result()
+
+
 class PainterEngine:
     """One prompt pair, one task, any number of query pictures.  prompt_img / prompt_tgt: RGB uint8 arrays of any size, resized once
     (`Image.resize((input_size, input_size))`, Pillow-exact) and kept on the device."""
@@ -186,44 +276,68 @@ class PainterEngine:
         return imgs, tgts
 
     @torch.no_grad()
-    def _run_batch(self, pictures, sizes, saved):
+    def _launch_batch(self, pictures, sizes, saved):
         """Host copies (the uint8 pictures, the job table) are all enqueued BEFORE the forward, while the stream holds nothing but
-        this batch's own resizes; from the forward's first launch to the copy back the host only enqueues kernels."""
+        this batch's own resizes; from the forward's first launch to the copy back the host only enqueues kernels.  -> the launched
+        DecodePlan, its pictures still on the device."""
         io = self.io
         queries = torch.stack([io.resize(io.upload(p), (self.res, self.res)) for p in pictures])
         plan = DecodePlan(self.task, sizes, self.device, saved=saved)
         imgs, tgts = self.stitch(queries)
         y = _forward(self.model, imgs, tgts)
-        plan.launch(y, self.res, self.res, io.patch)
+        return plan.launch(y, self.res, self.res, io.patch)
+
+    def _run_batch(self, pictures, sizes, saved):
+        plan = self._launch_batch(pictures, sizes, saved)
         return plan.pictures(), (plan.saved_pictures() if saved else None)
 
-    def _run(self, pictures, sizes, saved):
+    def _run(self, pictures, sizes, batch):
+        """batch(pictures, sizes) -> one result per picture, called once per `batch_size` pictures with the model in eval mode."""
         if sizes is None:
             sizes = [(p.shape[1], p.shape[0]) for p in pictures]
         assert len(sizes) == len(pictures)
         was_training = self.model.training
         self.model.eval()
         try:
-            outs, outs8 = [], []
+            outs = []
             for i in range(0, len(pictures), self.batch_size):
-                o, o8 = self._run_batch(pictures[i:i + self.batch_size], sizes[i:i + self.batch_size], saved)
-                outs.extend(o)
-                outs8.extend(o8 or [])
+                outs.append(batch(pictures[i:i + self.batch_size], sizes[i:i + self.batch_size]))
         finally:
             self.model.train(was_training)
-        return outs, outs8
+        return outs
 
     def run(self, pictures, sizes=None):
         """pictures: list of RGB uint8 arrays [H][W][3] of any sizes -> one array per picture at its own size, or at sizes[i] =
         (width, height): uint8 [H][W][3], int32 [H][W] or float64 [H][W][3] by task."""
-        return self._run(pictures, sizes, False)[0]
+        return [o for b in self._run(pictures, sizes, lambda p, s: self._run_batch(p, s, False)[0]) for o in b]
 
     def run_restoration(self, pictures, sizes=None):
         """derain / lol / sidd: -> (float64 arrays as `run` returns them, the uint8 pictures those scripts save), both written by the
         one decode launch (a second copy back carries the uint8 pictures)."""
         if self.spec["kind"] != "f64":
             raise ValueError("painter_engine: task %r saves its output as it is; run_restoration is for derain / lol / sidd" % self.task)
-        return self._run(pictures, sizes, True)
+        pairs = self._run(pictures, sizes, lambda p, s: self._run_batch(p, s, True))
+        return [o for b in pairs for o in b[0]], [o for b in pairs for o in b[1]]
+
+    def run_instances(self, pictures, sizes=None, **kw):
+        """coco_pano_inst: forward and decode as `run`, then `instances(picture, **kw)` of every decoded picture straight from the
+        decode plan's device-resident uint8 output -- no PNG, no host copy of the picture; the decodes of a batch are all enqueued behind
+        its forward before the first copy back.  -> one dict per picture, as `instances` returns it."""
+        if self.task != "coco_pano_inst":
+            raise ValueError("painter_engine: run_instances decodes the pictures of coco_pano_inst, not of %r" % self.task)
+        kw.pop("device", None)
+        args = dict(palette=None, dist_thr=19.0, nms_pre=2000, max_num=100, kernel="gaussian", sigma=2.0)
+        unknown = set(kw) - set(args)
+        if unknown:
+            raise TypeError("run_instances: unexpected arguments %s" % sorted(unknown))
+        args.update(kw)
+
+        def batch(pics, sizes):
+            plan = self._launch_batch(pics, sizes, False)
+            jobs = [InstanceDecode(plan.out[off:off + int(np.prod(shape))].view(shape), args["palette"], args["dist_thr"], args["nms_pre"],
+                                   args["max_num"], args["kernel"], args["sigma"]) for off, shape in plan.views]
+            return [j.result() for j in jobs]
+        return [o for b in self._run(pictures, sizes, batch) for o in b]
 
 
 @torch.no_grad()
