@@ -517,6 +517,53 @@ int pa_inst_decode(const void* image, const float* palette, const float* thresho
                    int max_num, float sigma, int kernel, void* workspace, void* out_count, float* out_scores, void* out_scores_f64,
                    void* out_candidates, void* out_masks, void* out_masks_u8, hipStream_t stream);
 
+/* Panoptic merge of a painted `coco_pano_semseg` picture with instances, csrc/painter_pano.hip: class vote
+ * (coco_panoptic/COCOPanoEvaluatorCustom.py:259-276, COCOInstSegEvaluatorCustom.py:169-186), paste (COCOPanoEvaluatorCustom.py:69-109) and
+ * stuff fill (:111-132) on integers and bit masks; tests/painter_pano_host.py is the definition.
+ * image: uint8 [h][w][3]; palette: DEVICE float32 [n_colours][3] of integer values 0..255 (define_colors_by_mean_sep,
+ * data/coco_semseg/gen_color_coco_panoptic_segm.py:31-54); labels < n_things are things; dist_type: the codes of pa_palette_argmin.
+ * Instances: masks_u32 = uint32 [max_inst][ceil(h * w / 32)], bit b of word k = pixel 32 k + b (pa_inst_decode's out_masks; padding bits of
+ * the last word are ignored); scores float32 [max_inst]; n_dev = DEVICE int32 [1], the number of instances (clamped to 0..max_inst).
+ * Capacities: h * w <= 2^24, n_colours <= 1024, 2 <= n_things <= n_colours, 1 <= max_inst <= 1024.  Null required pointers, sizes beyond a
+ * capacity, NaN thresholds or a workspace that is not 256-byte aligned return hipErrorInvalidValue before anything is launched. */
+typedef struct pa_pano_segment {
+    int id;              /* 1, 2, ...: the value of its pixels in the panoptic map */
+    int isthing;
+    int category_id;     /* voted (or given) class of a thing, semantic label of stuff */
+    int instance_id;     /* index of the instance; -1 for stuff */
+    int area;            /* pixels that finally carry the id (the reference reports it for stuff only, :130) */
+    float score;         /* 0 for stuff */
+} pa_pano_segment;
+/* host only: bytes of the workspace of pa_pano_merge / pa_pano_decode, -1 for bad arguments.
+ * ~ 8 * max_inst * n_things (vote sums) + h * w * (4 + 1/8) (semantic map, union bits) + 8 * n_colours + 4 * max_inst. */
+int64_t pa_pano_workspace_bytes(int h, int w, int n_colours, int n_things, int max_inst);
+/* masks_u8: uint8 / bool [n_rows][h * w], non-zero = set -> out_u32 = uint32 [n_rows][ceil(h * w / 32)] in the layout above, padding bits 0:
+ * for masks that do not come from pa_inst_decode (the pre-computed route, COCOPanoEvaluatorCustom.py:229-248).  n_rows <= 1024. */
+int pa_pack_mask_bits(const void* masks_u8, int n_rows, int h, int w, void* out_u32, hipStream_t stream);
+/* :259-276 / COCOInstSegEvaluatorCustom.py:169-186 alone: out_s_u64 = uint64 [max_inst][n_things] (cleared first), S[i][k] = sum over the
+ * pixels of mask i of d2(pixel, colour k), d2 = sum_c |d| (abs), sum_c d^2 (square), sum_c (|d| + d^2) (mean: twice the reference's);
+ * out_classes = int32 [max_inst], first minimum of row i (= the reference's argmax of sum (1 - d / max d), and of its softmax); an empty mask
+ * and the slots past the count get 0. */
+int pa_pano_vote(const void* image, const float* palette, const void* masks_u32, const void* n_dev, int h, int w, int n_colours, int n_things,
+                 int dist_type, int max_inst, void* out_s_u64, void* out_classes, hipStream_t stream);
+/* :69-132 from a given semantic map (int32 [h][w], pa_palette_argmin's output) and classes (int32 [max_inst]).  Instances are visited in
+ * descending score order, ties to the lower index (a NaN score last); stop at the first (double)score < instances_score_thresh; skip area 0
+ * and (double)intersection / (double)area > overlap_threshold, intersection with the union of the masks accepted so far; an accepted
+ * instance gets the next id from 1 and owns its pixels outside that union.  Then every label l >= n_things in ascending order whose count c
+ * of pixels outside the union has not (double)c < stuff_area_thresh gets the next id (a threshold <= 0 therefore also keeps labels without
+ * a pixel, which the reference's torch.unique never visits).  DEVICE outputs: out_panoptic int32 [h][w], 0 = unassigned; out_rgb uint8
+ * [h][w][3] = panopticapi id2rgb (r = id % 256, g = id / 256 % 256, b = id / 65536), or NULL; out_count int32 [1] = segments;
+ * out_segments pa_pano_segment [max_inst + n_colours - n_things], entries past the count 0. */
+int pa_pano_merge(const void* semmap_i32, const void* masks_u32, const float* scores, const void* classes_i32, const void* n_dev, int h, int w,
+                  int n_colours, int n_things, int max_inst, double overlap_threshold, double stuff_area_thresh, double instances_score_thresh,
+                  void* workspace, void* out_panoptic, void* out_rgb, void* out_count, void* out_segments, hipStream_t stream);
+/* The whole definition, nothing but launches on `stream`: pa_palette_argmin into the workspace, the vote (skipped when classes_i32, int32
+ * [max_inst], is given: it is copied to out_classes), then the merge.  out_classes int32 [max_inst] is required. */
+int pa_pano_decode(const void* image, const float* palette, const void* masks_u32, const float* scores, const void* n_dev,
+                   const void* classes_i32, int h, int w, int n_colours, int n_things, int dist_type, int max_inst, double overlap_threshold,
+                   double stuff_area_thresh, double instances_score_thresh, void* workspace, void* out_panoptic, void* out_rgb, void* out_count,
+                   void* out_segments, void* out_classes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ EPI_BIAS, EPI_BIAS_F32, EPI_BIAS_GELU, EPI_BIAS_RESID = 0, 1, 2, 3
  KNOB_ATTN3_FUSE, KNOB_ATTN_LIGHT_LAST, KNOB_CONV_WGRAD_GROUPS, KNOB_LN_BWD_VARIANT, KNOB_G256_PATCH, KNOB_G256_MIXED) = range(13)
 KNOB_G256_MIXED_NFULL, KNOB_DROP_SKIP, KNOB_DECODER_ROWS, KNOB_COUNT = 14, 16, 17, 18
 
-_CT = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "hipStream_t": ctypes.c_void_p}
+_CT = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double, "hipStream_t": ctypes.c_void_p}
 
 
 def parse_header(path=HEADER):

@@ -18,11 +18,17 @@ the digests the unmodified scripts produced); the float64 output of the three re
 (csrc/painter_inst.hip): the evaluator's threshold route and its Matrix NMS (COCOCAInstSegEvaluatorCustom.py:252-354,
 util/matrix_nms.py) on exact integers and bit masks, ties defined (tests/painter_inst_host.py is the definition).
 
+`classify_instances`, `panoptic` and `run_panoptic` finish what COCO panoptic evaluation needs (csrc/painter_pano.hip): every instance
+gets the thing class its pixels vote for in the painted `coco_pano_semseg` picture, and instances and semantic picture are combined into
+a panoptic map with its segment list (COCOPanoEvaluatorCustom.py:47-134, 203-276; COCOInstSegEvaluatorCustom.py:169-194) -- chained
+behind the instance decode on the device, one copy back (tests/painter_pano_host.py is the definition).
+
 Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
 (`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
 `cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
 canvases the script built, or pass an already resized 448 x 448 uint8 query to `run`); PSNR / SSIM; the detectron2 / mmpose
-evaluators apart from the colour -> class decode (`class_map`) and the instance decode (`instances`).
+evaluators apart from the colour -> class decode (`class_map`), the instance decode (`instances`) and the panoptic merge (`panoptic`);
+PQ computation and PNG encoding.
 
 There is no CPU fallback: a CPU device or a missing libpainter_hip.so raises.
 """
@@ -184,7 +190,8 @@ def location_palette(num_location_r=16, num_location_gb=20):
 class InstanceDecode:
     """One launched pa_inst_decode: every output sits in ONE device buffer, so `result()` is one copy back and one synchronisation."""
 
-    def __init__(self, picture, palette, thresholds, nms_pre, max_num, kernel, sigma):
+    def __init__(self, picture, palette, thresholds, nms_pre, max_num, kernel, sigma, tail=0):
+        """tail: further bytes at the end of the output buffer, from offset `self.tail`, for what a caller chains behind the decode."""
         if kernel not in NMS_KERNELS:
             raise NotImplementedError("%s kernel is not supported in matrix nms!" % kernel)
         self.img = img = picture
@@ -208,7 +215,8 @@ class InstanceDecode:
         # ONE byte buffer: int32 count | float64 scores [m] | float32 scores [m] | int32 candidates [m] | bit masks [m][words] | byte masks [m][h * w]
         self.o64, self.o32, self.oidx, self.obits = 8, 8 + 8 * m, 8 + 12 * m, 8 + 16 * m
         self.obytes = self.obits + 4 * m * self.words
-        self.out = torch.zeros(self.obytes + m * hw, dtype=torch.uint8, device=dev)
+        self.tail = (self.obytes + m * hw + 15) // 16 * 16
+        self.out = torch.zeros(self.tail + int(tail) if tail else self.obytes + m * hw, dtype=torch.uint8, device=dev)
         at = lambda off: self.out.data_ptr() + off
         check(lib.pa_inst_decode(img.data_ptr(), self.params.data_ptr(), self.params.data_ptr() + 4 * pal.size, self.h, self.w, self.k,
                                  self.n_thr, self.nms_pre, m, float(sigma), NMS_KERNELS[kernel], self.workspace.data_ptr(), at(0),
@@ -219,9 +227,10 @@ class InstanceDecode:
         off = lib.pa_inst_workspace_offset(*self.shape, which)
         return self.workspace[off:off + count * np.dtype(dtype).itemsize].cpu().numpy().view(dtype)
 
-    def result(self, with_f64=False, with_bits=False):
-        """The copy back (and the one synchronisation).  The bool masks are a view of the bytes the device wrote."""
-        a = self.out.cpu().numpy()
+    def result(self, with_f64=False, with_bits=False, host=None):
+        """The copy back (and the one synchronisation).  The bool masks are a view of the bytes the device wrote.  host: the output
+        buffer as numpy, if the caller has copied it back already."""
+        a = self.out.cpu().numpy() if host is None else host
         n, m, hw = int(a[:4].view(np.int32)[0]), self.max_num, self.h * self.w
         if n == 0:              # no candidate: the reference's single all-zero mask with score 0 and label 0 (:302-310)
             res = dict(scores=np.zeros(1, np.float32), labels=np.zeros(1, np.float32), masks=np.zeros((1, self.h, self.w), bool),
@@ -247,6 +256,266 @@ def instances(picture, palette=None, dist_thr=19.0, nms_pre=2000, max_num=100, k
     device = _require_cuda(picture.device if torch.is_tensor(picture) else device)
     img = picture if torch.is_tensor(picture) else torch.from_numpy(np.ascontiguousarray(picture)).to(device)
     return InstanceDecode(img, palette, dist_thr, nms_pre, max_num, kernel, sigma).result()
+
+
+# ---- panoptic merge (csrc/painter_pano.hip)
+SEGMENT = np.dtype([("id", np.int32), ("isthing", np.int32), ("category_id", np.int32), ("instance_id", np.int32), ("area", np.int32),
+                    ("score", np.float32)])                                             # pa_pano_segment of include/painter_hip.h
+_INSTANCE_ARGS = dict(palette=None, dist_thr=19.0, nms_pre=2000, max_num=100, kernel="gaussian", sigma=2.0)
+
+
+@functools.lru_cache(maxsize=4)
+def semantic_palette(num_colors=133, channelsep=7):
+    """The colours the `coco_pano_semseg` targets are painted with, float32 [num_colors][3] (define_colors_by_mean_sep,
+    data/coco_semseg/gen_color_coco_panoptic_segm.py:31-54): each channel steps down by 256 // channelsep, blue fastest."""
+    sep, i = 256 // channelsep, np.arange(num_colors)
+    pal = np.stack([255 - sep * (i // channelsep ** 2), 255 - sep * (i % channelsep ** 2 // channelsep), 255 - sep * (i % channelsep)], -1)
+    assert pal.min() >= 0 and len({tuple(c) for c in pal.tolist()}) == len(pal)
+    pal = pal.astype(np.float32)
+    pal.setflags(write=False)                  # cached: every caller sees the same array
+    return pal
+
+
+def id2rgb(id_map):
+    """panopticapi.utils.id2rgb for an integer map: [H][W] -> uint8 [H][W][3], r = id % 256, g = id // 256 % 256, b = id // 65536."""
+    m = np.asarray(id_map).astype(np.int64)
+    return np.stack([m % 256, m // 256 % 256, m // 65536], -1).astype(np.uint8)
+
+
+def _picture(picture, device):
+    img = picture if torch.is_tensor(picture) else torch.from_numpy(np.ascontiguousarray(picture)).to(device)
+    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.is_contiguous(), (img.dtype, tuple(img.shape))
+    return img
+
+
+def _semantic_palette_array(palette):
+    pal = np.array(semantic_palette() if palette is None else palette, dtype=np.float32, order="C")          # a copy: the cached palette is read-only
+    assert pal.ndim == 2 and pal.shape[1] == 3 and (pal == np.floor(pal)).all() and pal.min() >= 0 and pal.max() <= 255, \
+        "painter_engine: the palette holds integer colours 0..255"
+    return pal
+
+
+def _host_array(values, dtype):
+    """Scores / classes of supplied instances (list, numpy or a tensor on any device) -> flat numpy array."""
+    return np.asarray(values.detach().cpu() if torch.is_tensor(values) else values).astype(dtype).ravel()
+
+
+def _bit_masks(masks, h, w, device):
+    """bool / uint8 [n][H][W] (numpy or CUDA tensor), or bit masks uint32 [n][ceil(H W / 32)] (the `bits` of an InstanceDecode) -> int32
+    CUDA tensor [max(n, 1)][words] in pa_inst_decode's bit layout, n.  device: the picture tensor's own device (with its index); a mask
+    tensor anywhere else is refused."""
+    words = (h * w + 31) // 32
+    if not torch.is_tensor(masks):
+        masks = np.asarray(masks)
+        if masks.dtype == np.uint32:
+            assert masks.ndim == 2 and masks.shape[1] == words, masks.shape
+            masks = np.ascontiguousarray(masks).view(np.int32)
+        else:
+            masks = np.ascontiguousarray(masks).view(np.uint8) if masks.dtype == bool else np.ascontiguousarray(masks, dtype=np.uint8)
+        masks = torch.from_numpy(masks).to(device)
+    if _require_cuda(masks.device) != device:                        # a host or foreign address must never reach a kernel
+        raise RuntimeError("painter_engine: the masks are on %s, the picture on %s" % (masks.device, device))
+    n = int(masks.shape[0])
+    if masks.dtype == torch.int32:
+        assert masks.dim() == 2 and masks.shape[1] == words, tuple(masks.shape)
+        return (masks.contiguous() if n else torch.zeros((1, words), dtype=torch.int32, device=device)), n
+    assert masks.dtype in (torch.uint8, torch.bool) and tuple(masks.shape[1:]) == (h, w), (masks.dtype, tuple(masks.shape))
+    bits = torch.zeros((max(n, 1), words), dtype=torch.int32, device=device)
+    if n:
+        check(lib.pa_pack_mask_bits(masks.contiguous().data_ptr(), n, h, w, bits.data_ptr(), _stream()), "pa_pack_mask_bits (%d masks)" % n)
+    return bits, n
+
+
+def classify_instances(semseg_picture, masks, palette=None, n_things=80, dist_type="abs", device="cuda"):
+    """COCOPanopticEvaluatorCustom.merge_inst_semseg_result_to_instseg (COCOPanoEvaluatorCustom.py:259-276; the softmax of
+    COCOInstSegEvaluatorCustom.py:169-186 does not change the argmax): the thing class whose colour the pixels of each mask are nearest
+    to in sum, as exact integers, ties to the lower class, class 0 for an empty mask.  semseg_picture: the painted `coco_pano_semseg`
+    picture, uint8 [H][W][3] (numpy or CUDA tensor); masks: bool / uint8 [n][H][W] (numpy or CUDA tensor) or the uint32 `bits` of an
+    InstanceDecode -> int32 [n] numpy."""
+    device = _require_cuda(semseg_picture.device if torch.is_tensor(semseg_picture) else device)
+    if torch.is_tensor(masks):
+        _require_cuda(masks.device)
+    if dist_type not in DIST_TYPES:
+        raise NotImplementedError(dist_type)
+    img = _picture(semseg_picture, device)
+    device = img.device
+    pal = _semantic_palette_array(palette)
+    h, w, k = int(img.shape[0]), int(img.shape[1]), int(pal.shape[0])
+    bits, n = _bit_masks(masks, h, w, device)
+    m = int(bits.shape[0])
+    dpal = torch.from_numpy(pal).to(device)
+    count = torch.tensor([n], dtype=torch.int32, device=device)
+    sums = torch.empty((m, int(n_things)), dtype=torch.int64, device=device)
+    classes = torch.empty(m, dtype=torch.int32, device=device)
+    check(lib.pa_pano_vote(img.data_ptr(), dpal.data_ptr(), bits.data_ptr(), count.data_ptr(), h, w, k, int(n_things), DIST_TYPES[dist_type], m,
+                           sums.data_ptr(), classes.data_ptr(), _stream()), "pa_pano_vote (sizes %s)" % ((h, w, k, n_things, m),))
+    return classes.cpu().numpy()[:n]
+
+
+class PanopticDecode:
+    """One launched pa_pano_decode.  Behind an InstanceDecode (built with `tail=PanopticDecode.out_bytes(...)`) it reads the decode's
+    count, scores and bit masks where the decode left them and writes into the tail of the decode's output buffer: `result()` is one copy
+    back and one synchronisation for both.  With supplied instances (dict(masks=, scores=, classes=None)) it owns its output buffer."""
+
+    @staticmethod
+    def out_bytes(h, w, k, n_things, max_inst):
+        return 16 + SEGMENT.itemsize * (max_inst + k - n_things) + 4 * max_inst + 7 * h * w
+
+    def __init__(self, semseg_picture, decode=None, supplied=None, palette=None, n_things=80, dist_type="abs", overlap_threshold=0.5,
+                 stuff_area_thresh=8192, instances_score_thresh=0.55):
+        if dist_type not in DIST_TYPES:
+            raise NotImplementedError(dist_type)
+        assert (decode is None) != (supplied is None)
+        self.img = img = semseg_picture
+        dev = img.device
+        pal = _semantic_palette_array(palette)
+        self.h, self.w, self.k, self.n_things = int(img.shape[0]), int(img.shape[1]), int(pal.shape[0]), int(n_things)
+        self.decode, self.supplied = decode, supplied
+        given = None
+        if decode is not None:
+            assert (decode.h, decode.w) == (self.h, self.w), "painter_engine: the two painted pictures differ in size"
+            self.max_inst, self.out, self.base = decode.max_num, decode.out, decode.tail
+            masks, scores, count = (decode.out.data_ptr() + o for o in (decode.obits, decode.o32, 0))
+        else:
+            self.bits, n = _bit_masks(supplied["masks"], self.h, self.w, dev)
+            self.max_inst, self.base = int(self.bits.shape[0]), 0
+            sc = np.zeros(self.max_inst, np.float32)
+            sc[:n] = _host_array(supplied["scores"], np.float32)
+            self.n, self.scores = n, torch.from_numpy(sc).to(dev)
+            self.count = torch.tensor([n], dtype=torch.int32, device=dev)
+            if supplied.get("classes") is not None:
+                cl = np.zeros(self.max_inst, np.int32)
+                cl[:n] = _host_array(supplied["classes"], np.int32)
+                self.given = given = torch.from_numpy(cl).to(dev)
+            masks, scores, count = self.bits.data_ptr(), self.scores.data_ptr(), self.count.data_ptr()
+        shape = (self.h, self.w, self.k, self.n_things, self.max_inst)
+        nbytes = lib.pa_pano_workspace_bytes(*shape)
+        if nbytes < 0:
+            check(1, "pa_pano_decode (sizes %s)" % (shape,))
+        if decode is None:
+            self.out = torch.zeros(self.out_bytes(*shape), dtype=torch.uint8, device=dev)
+        assert self.out.numel() >= self.base + self.out_bytes(*shape)
+        self.cap = self.max_inst + self.k - self.n_things
+        self.oseg, hw = self.base + 16, self.h * self.w
+        self.ocls = self.oseg + SEGMENT.itemsize * self.cap
+        self.opan = self.ocls + 4 * self.max_inst
+        self.orgb = self.opan + 4 * hw
+        self.palette = torch.from_numpy(pal).to(dev, non_blocking=True)
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        at = lambda off: self.out.data_ptr() + off
+        check(lib.pa_pano_decode(img.data_ptr(), self.palette.data_ptr(), masks, scores, count, None if given is None else given.data_ptr(),
+                                 *shape[:4], DIST_TYPES[dist_type], self.max_inst, float(overlap_threshold), float(stuff_area_thresh),
+                                 float(instances_score_thresh), self.workspace.data_ptr(), at(self.opan), at(self.orgb), at(self.base),
+                                 at(self.oseg), at(self.ocls), _stream()), "pa_pano_decode")
+
+    def result(self):
+        """The copy back (and the one synchronisation) -> the dict `panoptic` documents."""
+        a = self.out.cpu().numpy()
+        hw = self.h * self.w
+        if self.decode is not None:
+            inst = self.decode.result(host=a)
+            scores, masks, n = inst["scores"], inst["masks"], int(a[:4].view(np.int32)[0])
+        else:
+            masks = self.supplied["masks"]                          # handed back as they came: no copy of what the caller has
+            scores, n = _host_array(self.supplied["scores"], np.float32), self.n
+        count = int(a[self.base:self.base + 4].view(np.int32)[0])
+        table = a[self.oseg:self.oseg + SEGMENT.itemsize * count].view(SEGMENT)
+        segments = [dict(id=int(s["id"]), isthing=True, score=float(s["score"]), category_id=int(s["category_id"]),
+                         instance_id=int(s["instance_id"])) if s["isthing"] else
+                    dict(id=int(s["id"]), isthing=False, category_id=int(s["category_id"]), area=int(s["area"])) for s in table]
+        classes = a[self.ocls:self.ocls + 4 * n].view(np.int32) if n else np.zeros(len(scores), np.int32)
+        return dict(panoptic=a[self.opan:self.opan + 4 * hw].view(np.int32).reshape(self.h, self.w), segments=segments, classes=classes,
+                    scores=scores, masks=masks, rgb=a[self.orgb:self.orgb + 3 * hw].reshape(self.h, self.w, 3), areas=table["area"].copy())
+
+
+def _check_panoptic_args(dist_type, instances_kw):
+    """What can be refused before anything is enqueued."""
+    unknown = set(instances_kw) - set(_INSTANCE_ARGS)
+    if unknown:
+        raise TypeError("panoptic: unexpected arguments %s" % sorted(unknown))
+    if dist_type not in DIST_TYPES:
+        raise NotImplementedError(dist_type)
+    if instances_kw.get("kernel", "gaussian") not in NMS_KERNELS:
+        raise NotImplementedError("%s kernel is not supported in matrix nms!" % instances_kw["kernel"])
+
+
+def _launch_panoptic(sem, inst, instances, semseg_palette, n_things, merge, instances_kw):
+    """sem, inst: uint8 CUDA pictures (inst None with supplied instances) -> the launched PanopticDecode."""
+    _check_panoptic_args(merge["dist_type"], instances_kw)
+    if (inst is None) == (instances is None):
+        raise TypeError("panoptic: give either the painted coco_pano_inst picture or instances=dict(masks=, scores=, classes=None)")
+    dec = None
+    if inst is not None:
+        a = dict(_INSTANCE_ARGS, **instances_kw)
+        k = len(_semantic_palette_array(semseg_palette))
+        tail = PanopticDecode.out_bytes(int(sem.shape[0]), int(sem.shape[1]), k, int(n_things), int(a["max_num"]))
+        dec = InstanceDecode(inst, a["palette"], a["dist_thr"], a["nms_pre"], a["max_num"], a["kernel"], a["sigma"], tail=tail)
+    elif instances_kw:
+        raise TypeError("panoptic: %s belong to the instance decode, which supplied instances skip" % sorted(instances_kw))
+    return PanopticDecode(sem, dec, instances, semseg_palette, n_things, **merge)
+
+
+def panoptic(semseg_picture, inst_picture=None, *, instances=None, semseg_palette=None, n_things=80, dist_type="abs", overlap_threshold=0.5,
+             stuff_area_thresh=8192, instances_score_thresh=0.55, device="cuda", **instances_kw):
+    """COCOPanopticEvaluatorCustom.merge_inst_semseg_result_to_panoseg (COCOPanoEvaluatorCustom.py:203-257) without its files: the
+    semantic map of the painted `coco_pano_semseg` picture (nearest of the `semseg_palette` colours, default `semantic_palette()`), a
+    class for every instance by vote (:259-276), then combine_semantic_and_instance_outputs_custom (:47-134).  The defaults are those of
+    get_args_parser_pano_seg (:279-297).
+
+    inst_picture: the painted `coco_pano_inst` picture; it is decoded as `instances(inst_picture, **instances_kw)` does and the merge is
+    chained behind that decode on the device -- one output buffer, one copy back, one synchronisation.  Or instances = dict(masks= bool /
+    uint8 [n][H][W] (numpy or a CUDA tensor on the picture's device), scores= [n], classes= [n] or None (lists, numpy or tensors; they
+    are read on the host)) for pre-computed instances (:229-248); given classes skip the vote.
+
+    -> dict(panoptic int32 [H][W] (0 = unassigned), segments = list of dicts as the reference builds them (things: id, isthing, score,
+    category_id, instance_id; stuff: id, isthing, category_id, area), areas int32 per segment (pixels that carry its id), classes int32
+    [n], scores float32 [n], masks bool [n][H][W] (supplied masks: the caller's own object), rgb uint8 [H][W][3] = id2rgb(panoptic), what
+    the evaluator encodes as PNG).  When the
+    instance decode finds no candidate the instances are the reference's single zero mask with score 0 and class 0, which adds nothing."""
+    tensors = [p for p in (semseg_picture, inst_picture) if torch.is_tensor(p)]
+    for t in tensors + [m for m in [(instances or {}).get("masks")] if torch.is_tensor(m)]:
+        _require_cuda(t.device)
+    device = _require_cuda(tensors[0].device if tensors else device)
+    if len({t.device for t in tensors}) > 1:
+        raise RuntimeError("painter_engine: the two pictures are on %s" % " and ".join(str(t.device) for t in tensors))
+    sem = _picture(semseg_picture, device)
+    inst = None if inst_picture is None else _picture(inst_picture, device)
+    merge = dict(dist_type=dist_type, overlap_threshold=overlap_threshold, stuff_area_thresh=stuff_area_thresh,
+                 instances_score_thresh=instances_score_thresh)
+    return _launch_panoptic(sem, inst, instances, semseg_palette, n_things, merge, instances_kw).result()
+
+
+def run_panoptic(semseg_engine, inst_engine, pictures, sizes=None, **kw):
+    """Two PainterEngines, one of task `coco_pano_semseg` and one of `coco_pano_inst`, each with its own prompt pair: forward and decode of
+    both as `run`, then `panoptic(semantic picture, instance picture, **kw)` of every pair straight from the decode plans' device-resident
+    uint8 outputs; the merges of a batch are all enqueued before the first copy back.  -> one dict per picture, as `panoptic` returns it."""
+    if semseg_engine.task != "coco_pano_semseg" or inst_engine.task != "coco_pano_inst":
+        raise ValueError("painter_engine: run_panoptic takes a coco_pano_semseg engine and a coco_pano_inst engine, not %r and %r"
+                         % (semseg_engine.task, inst_engine.task))
+    kw = dict(kw)
+    kw.pop("device", None)
+    top = dict(semseg_palette=None, n_things=80)
+    merge = dict(dist_type="abs", overlap_threshold=0.5, stuff_area_thresh=8192, instances_score_thresh=0.55)
+    top.update((k, kw.pop(k)) for k in list(kw) if k in top)
+    merge.update((k, kw.pop(k)) for k in list(kw) if k in merge)
+    _check_panoptic_args(merge["dist_type"], kw)          # before the first forward is enqueued, as run_instances does
+    view = lambda plan, v: plan.out[v[0]:v[0] + int(np.prod(v[1]))].view(v[1])
+
+    def batch(pics, sizes):
+        sem = semseg_engine._launch_batch(pics, sizes, False)
+        jobs, step = [], inst_engine.batch_size
+        for j in range(0, len(pics), step):
+            inst = inst_engine._launch_batch(pics[j:j + step], sizes[j:j + step], False)
+            jobs += [_launch_panoptic(view(sem, sv), view(inst, iv), None, top["semseg_palette"], top["n_things"], merge, kw)
+                     for sv, iv in zip(sem.views[j:j + step], inst.views)]
+        return [j.result() for j in jobs]
+
+    was_training = inst_engine.model.training
+    inst_engine.model.eval()
+    try:
+        return [o for b in semseg_engine._run(pictures, sizes, batch) for o in b]
+    finally:
+        inst_engine.model.train(was_training)
 
 
 class PainterEngine:
