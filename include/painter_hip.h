@@ -564,6 +564,30 @@ int pa_pano_decode(const void* image, const float* palette, const void* masks_u3
                    double stuff_area_thresh, double instances_score_thresh, void* workspace, void* out_panoptic, void* out_rgb, void* out_count,
                    void* out_segments, void* out_classes, hipStream_t stream);
 
+/* Keypoints of painted `coco_pose` pictures, csrc/painter_pose.hip: TopDownCustom.forward_pseudo_test (mmpose_custom/model/top_down.py:
+ * 163-258) and mmpose's keypoints_from_heatmaps (post_process 'default', no UDP) without a heat map in memory; tests/painter_pose_host.py
+ * is the definition.
+ * pictures: uint8 [n][h][w][3]; flipped: the pictures painted for the mirrored boxes, same shape, or NULL for no flip test;
+ * palette_i32: DEVICE int32 [n_keypoints + 1][2], the (G, B) colour of every channel, background LAST (define_colors_gb_mean_sep,
+ * data/pipelines/custom_transform.py:10-33); pair_i32: DEVICE int32 [n_keypoints], the channel that a mirror swaps each channel with
+ * (pair[pair[k]] == k; values outside 0..n_keypoints-1 are clamped).  A pixel's class is the first minimum of |G - g_c| + |B - b_c|; the
+ * heat of channel k is float32(R) / 255 where the class is k, else 0.  With `flipped`: F_k(y, x) = heat of channel pair[k] of the flipped
+ * picture at (y, w - 1 - x); shift != 0 moves F one column right (column 0 keeps its value); out = (heat + F) / 2 in float32 -- one float32
+ * add of two table values and an exact halving, which decides ties exactly as the reference's arrays do.  Without: out = heat.
+ * n, h, w >= 1, h * w < 2^31, 1 <= n_keypoints <= 32, n * ceil(h * w / 256) < 2^31; otherwise, or for a null required pointer,
+ * hipErrorInvalidValue before anything is launched. */
+/* host only: bytes of pa_pose_keypoints's workspace (one 64-bit key per box and channel), -1 for bad arguments. */
+int64_t pa_pose_workspace_bytes(int n, int n_keypoints);
+/* Per box and channel the first maximum of `out` in row-major order: out_maxvals float32 [n][n_keypoints], out_preds float32
+ * [n][n_keypoints][2] = (x, y) in heat-map pixels, moved by 0.25 * sign(out[y][x + 1] - out[y][x - 1]) (and likewise over rows) where
+ * 1 < x < w - 1 and 1 < y < h - 1; (-1, -1) and 0 for a channel without a positive value.  workspace: pa_pose_workspace_bytes, 8-byte
+ * aligned.  Nothing but a memset and two launches on `stream`; deterministic. */
+int pa_pose_keypoints(const void* pictures, const void* flipped, const void* palette_i32, const void* pair_i32, int n, int h, int w,
+                      int n_keypoints, int shift, void* workspace, float* out_preds, float* out_maxvals, hipStream_t stream);
+/* `out` itself, float32 [n][n_keypoints][h][w]: what forward_pseudo_test returns with return_heatmap=True. */
+int pa_pose_heatmaps(const void* pictures, const void* flipped, const void* palette_i32, const void* pair_i32, int n, int h, int w,
+                     int n_keypoints, int shift, float* out_heatmaps, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

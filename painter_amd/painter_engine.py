@@ -23,12 +23,16 @@ gets the thing class its pixels vote for in the painted `coco_pano_semseg` pictu
 a panoptic map with its segment list (COCOPanoEvaluatorCustom.py:47-134, 203-276; COCOInstSegEvaluatorCustom.py:169-194) -- chained
 behind the instance decode on the device, one copy back (tests/painter_pano_host.py is the definition).
 
+`keypoints`, `pose_heatmaps` and `PainterEngine.run_pose` turn painted `coco_pose` pictures into keypoints (csrc/painter_pose.hip):
+TopDownCustom.forward_pseudo_test with its flip test (mmpose_custom/model/top_down.py:163-258) and mmpose's heat-map peak rule, straight
+from the bytes of the two pictures -- no heat map in memory, 51 floats per box back (tests/painter_pose_host.py is the definition).
+
 Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
 (`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
 `cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
-canvases the script built, or pass an already resized 448 x 448 uint8 query to `run`); PSNR / SSIM; the detectron2 / mmpose
+canvases the script built, or pass an already resized 448 x 448 uint8 query to `run`); PSNR / SSIM; the detectron2
 evaluators apart from the colour -> class decode (`class_map`), the instance decode (`instances`) and the panoptic merge (`panoptic`);
-PQ computation and PNG encoding.
+PQ computation and PNG encoding; of the pose route mmpose's OKS NMS, rescoring and COCOeval, and the 34 numbers per box of `to_image`.
 
 There is no CPU fallback: a CPU device or a missing libpainter_hip.so raises.
 """
@@ -256,6 +260,118 @@ def instances(picture, palette=None, dist_thr=19.0, nms_pre=2000, max_num=100, k
     device = _require_cuda(picture.device if torch.is_tensor(picture) else device)
     img = picture if torch.is_tensor(picture) else torch.from_numpy(np.ascontiguousarray(picture)).to(device)
     return InstanceDecode(img, palette, dist_thr, nms_pre, max_num, kernel, sigma).result()
+
+
+# ---- pose keypoints (csrc/painter_pose.hip)
+# configs/_base_/coco.py: the left / right partners (`swap`) of COCO's 17 keypoints
+COCO_FLIP_PAIRS = ((1, 2), (3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16))
+
+
+@functools.lru_cache(maxsize=4)
+def pose_palette(num_locations=17):
+    """The (G, B) colours the `coco_pose` targets are painted with, one per keypoint, plus the background row (0, 0) LAST, as int32
+    [num_locations + 1][2] (define_colors_gb_mean_sep, mmpose_custom/data/pipelines/custom_transform.py:10-33; the row TopDownCustom
+    appends, model/top_down.py:28-30): green steps down by 256 // (isqrt(n) + 1) per row of the grid, blue by the same per column."""
+    per = int(num_locations ** (1 / 2)) + 1
+    sep, k = 256 // per, np.arange(num_locations)
+    pal = np.concatenate([np.stack([255 - k // per * sep, 255 - k % per * sep], -1), [[0, 0]]]).astype(np.int32)
+    assert pal.min() >= 0 and len({tuple(c) for c in pal.tolist()}) == len(pal)
+    pal.setflags(write=False)                  # cached: every caller sees the same array
+    return pal
+
+
+def _pose_batch(pictures, device):
+    """uint8 [n][H][W][3] or a list of [H][W][3] of one size (numpy or CUDA tensors) -> contiguous uint8 CUDA tensor [n][H][W][3]."""
+    if isinstance(pictures, (list, tuple)):
+        assert len(pictures) >= 1 and len({tuple(p.shape) for p in pictures}) == 1, "painter_engine: the pictures of a pose batch have one size"
+        pictures = torch.stack(list(pictures)) if torch.is_tensor(pictures[0]) else np.stack(pictures)
+    x = pictures if torch.is_tensor(pictures) else torch.from_numpy(np.ascontiguousarray(pictures)).to(device)
+    if _require_cuda(x.device) != device:
+        raise RuntimeError("painter_engine: the pictures are on %s, expected %s" % (x.device, device))
+    assert x.dtype == torch.uint8 and x.dim() == 4 and x.shape[3] == 3, (x.dtype, tuple(x.shape))
+    return x.contiguous()
+
+
+class PoseDecode:
+    """One launched pa_pose_keypoints (or pa_pose_heatmaps): preds and maxvals sit in ONE device buffer, so `result()` is one copy back
+    and one synchronisation."""
+
+    def __init__(self, pictures, flipped=None, palette=None, flip_pairs=COCO_FLIP_PAIRS, shift_heatmap=True, heatmaps=False):
+        self.img, self.flip = img, flip = pictures, flipped
+        dev = img.device
+        assert flip is None or (flip.device == dev and flip.shape == img.shape), "painter_engine: pictures and flipped pictures differ"
+        pal = np.ascontiguousarray(np.asarray(pose_palette() if palette is None else palette)).astype(np.int32)
+        assert pal.ndim == 2 and pal.shape[1] == 2 and pal.shape[0] >= 1, "painter_engine: the pose palette is [K + 1][2], background last"
+        self.n, self.h, self.w, self.k = int(img.shape[0]), int(img.shape[1]), int(img.shape[2]), int(pal.shape[0]) - 1
+        pair = np.arange(max(self.k, 0), dtype=np.int32)
+        for a, b in flip_pairs:
+            assert 0 <= a < self.k and 0 <= b < self.k and pair[a] == a and pair[b] == b, "painter_engine: flip_pairs are disjoint pairs of channels"
+            pair[a], pair[b] = b, a
+        shape = (self.n, self.h, self.w, self.k)
+        what = "pa_pose_heatmaps" if heatmaps else "pa_pose_keypoints"
+        nbytes = lib.pa_pose_workspace_bytes(self.n, self.k)
+        if nbytes < 0 or self.h < 1 or self.w < 1:
+            check(1, "%s (sizes %s)" % (what, shape))
+        self.tables = torch.from_numpy(np.concatenate([pal.ravel(), pair])).to(dev, non_blocking=True)
+        args = (img.data_ptr(), None if flip is None else flip.data_ptr(), self.tables.data_ptr(), self.tables.data_ptr() + 4 * pal.size,
+                *shape, 1 if shift_heatmap else 0)
+        if heatmaps:
+            self.out = torch.empty((self.n, self.k, self.h, self.w), dtype=torch.float32, device=dev)
+            check(lib.pa_pose_heatmaps(*args, self.out.data_ptr(), _stream()), "%s (sizes %s)" % (what, shape))
+        else:
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.out = torch.empty(3 * self.n * self.k, dtype=torch.float32, device=dev)           # preds [n][K][2] | maxvals [n][K]
+            check(lib.pa_pose_keypoints(*args, self.workspace.data_ptr(), self.out.data_ptr(), self.out.data_ptr() + 8 * self.n * self.k,
+                                        _stream()), "%s (sizes %s)" % (what, shape))
+
+    def result(self):
+        """The copy back (and the one synchronisation) -> dict(preds float32 [n][K][2], maxvals float32 [n][K])."""
+        a, m = self.out.cpu().numpy(), 2 * self.n * self.k
+        return dict(preds=a[:m].reshape(self.n, self.k, 2), maxvals=a[m:].reshape(self.n, self.k))
+
+
+def _pose_inputs(pictures, flipped, device):
+    tensors = [p for x in (pictures, flipped) if x is not None for p in (x if isinstance(x, (list, tuple)) else [x]) if torch.is_tensor(p)]
+    for t in tensors:
+        _require_cuda(t.device)
+    device = _require_cuda(tensors[0].device if tensors else device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return _pose_batch(pictures, device), None if flipped is None else _pose_batch(flipped, device)
+
+
+def keypoints(pictures, flipped=None, palette=None, flip_pairs=COCO_FLIP_PAIRS, shift_heatmap=True, device="cuda"):
+    """TopDownCustom.forward_pseudo_test (mmpose_custom/model/top_down.py:163-258) and the head's decode, mmpose 0.x
+    keypoints_from_heatmaps with post_process='default' and no UDP, for n painted person boxes at once.
+
+    pictures: the painted `coco_pose` pictures, uint8 [n][H][W][3] or a list of [H][W][3] of one size (numpy or CUDA tensors); flipped:
+    what the network painted for the mirrored boxes (the reference's `_flip` directory), same shape, or None for no flip test; palette:
+    int [K + 1][2] (G, B) colours, background last (default `pose_palette()`); flip_pairs: the channels a mirror swaps; shift_heatmap:
+    the one-column shift of the flipped heat maps (`shift_heatmap=True` of configs/coco_256x192_test_offline.py).
+
+    -> dict(preds float32 [n][K][2] = (x, y) in heat-map pixels, maxvals float32 [n][K]): per channel the first maximum of
+    (heat + flipped heat) / 2 in row-major order, moved a quarter pixel towards the larger neighbour inside the border; (-1, -1) and 0
+    for a channel no pixel shows.  The float32 values are the reference's own (one add of two `R / 255` table values, one halving), so
+    ties fall as its argmax lets them.  `to_image` maps preds to the photo."""
+    return PoseDecode(*_pose_inputs(pictures, flipped, device), palette, flip_pairs, shift_heatmap).result()
+
+
+def pose_heatmaps(pictures, flipped=None, palette=None, flip_pairs=COCO_FLIP_PAIRS, shift_heatmap=True, device="cuda"):
+    """The `output_heatmap` of forward_pseudo_test(return_heatmap=True) for the arguments of `keypoints` -> float32 numpy [n][K][H][W].
+    `keypoints` never builds it."""
+    return PoseDecode(*_pose_inputs(pictures, flipped, device), palette, flip_pairs, shift_heatmap, heatmaps=True).out.cpu().numpy()
+
+
+def to_image(preds, center, scale, heatmap_size):
+    """Heat-map pixels -> photo pixels for one box: preds [K][2], center (x, y) and scale (w, h) / 200 of the box as mmpose's
+    img_metas carry them, heatmap_size (W, H).  Restates mmpose 0.x `transform_preds(coords, center, scale, output_size, use_udp=False)`
+    from its published source; mmpose is not available where this project is tested, so the formula is unverified against it."""
+    preds = np.asarray(preds)
+    full = np.asarray(scale, dtype=np.float64) * 200.0
+    out = np.ones_like(preds)
+    out[:, 0] = preds[:, 0] * (full[0] / heatmap_size[0]) + center[0] - full[0] * 0.5
+    out[:, 1] = preds[:, 1] * (full[1] / heatmap_size[1]) + center[1] - full[1] * 0.5
+    return out
 
 
 # ---- panoptic merge (csrc/painter_pano.hip)
@@ -607,6 +723,63 @@ class PainterEngine:
                                    args["max_num"], args["kernel"], args["sigma"]) for off, shape in plan.views]
             return [j.result() for j in jobs]
         return [o for b in self._run(pictures, sizes, batch) for o in b]
+
+
+    def run_pose(self, pictures, flipped=None, sizes=None, **kw):
+        """coco_pose: forward and decode as `run` (nearest), then `keypoints` of every batch straight from the decode plan's
+        device-resident uint8 output -- no PNG, no copy back of a picture, one copy back of preds / maxvals per batch.
+
+        pictures: the person boxes' query pictures; flipped: None (no flip test), a list with one flipped query per picture (the
+        reference's `_flip` files), or "mirror": the columns of every query are mirrored on the host before upload.  Queries and their
+        flipped twins go through the same batched forwards.  sizes: (width, height) of the painted pictures, all equal within a call
+        (default (192, 256) for every picture).  kw: palette, flip_pairs, shift_heatmap of `keypoints`.
+        -> one dict(preds float32 [K][2], maxvals float32 [K]) per picture."""
+        if self.task != "coco_pose":
+            raise ValueError("painter_engine: run_pose decodes the pictures of coco_pose, not of %r" % self.task)
+        kw.pop("device", None)
+        args = dict(palette=None, flip_pairs=COCO_FLIP_PAIRS, shift_heatmap=True)
+        unknown = set(kw) - set(args)
+        if unknown:
+            raise TypeError("run_pose: unexpected arguments %s" % sorted(unknown))
+        args.update(kw)
+        pictures = list(pictures)
+        sizes = [(192, 256)] * len(pictures) if sizes is None else [(int(w), int(h)) for w, h in sizes]
+        assert len(sizes) == len(pictures)
+        assert len(set(sizes)) <= 1, "painter_engine: run_pose needs one output size within a call, got %s" % sorted(set(sizes))
+        if isinstance(flipped, str):
+            if flipped != "mirror":
+                raise ValueError("painter_engine: flipped is None, a list of pictures or \"mirror\", not %r" % flipped)
+            flipped = [np.ascontiguousarray(np.asarray(p)[:, ::-1]) for p in pictures]
+        elif flipped is not None:
+            flipped = list(flipped)
+            assert len(flipped) == len(pictures), "painter_engine: one flipped query per picture"
+        if not pictures:
+            return []
+        pixels = sizes[0][0] * sizes[0][1] * 3
+        shape = (sizes[0][1], sizes[0][0], 3)
+        step = self.batch_size if flipped is None else max(1, self.batch_size // 2)          # boxes per batch: twins share the forward
+
+        def painted(plans, first, count):
+            """Pictures first .. first + count of the batch's decode plans as one uint8 tensor [count][H][W][3] (a view when one plan
+            holds them all)."""
+            flat = plans[0].out if len(plans) == 1 else torch.cat([p.out for p in plans])
+            return flat[first * pixels:(first + count) * pixels].view((count,) + shape)
+
+        def batch(pics, twins):
+            m, both = len(pics), pics + (twins or [])
+            plans = [self._launch_batch(both[j:j + self.batch_size], sizes[:1] * len(both[j:j + self.batch_size]), False)
+                     for j in range(0, len(both), self.batch_size)]
+            res = PoseDecode(painted(plans, 0, m), painted(plans, m, m) if twins else None, args["palette"], args["flip_pairs"],
+                             args["shift_heatmap"]).result()
+            return [dict(preds=res["preds"][i], maxvals=res["maxvals"][i]) for i in range(m)]
+
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            return [o for i in range(0, len(pictures), step)
+                    for o in batch(pictures[i:i + step], None if flipped is None else flipped[i:i + step])]
+        finally:
+            self.model.train(was_training)
 
 
 @torch.no_grad()
