@@ -250,3 +250,9 @@ DEVI uint2 cvt4(float a, float b, float c, float d, bf16*) { return make_uint2(p
 // value returned after the launch belongs to this launch.
 #define PA_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 #define LAUNCH_CHECK() return (int)hipGetLastError()
+// Inside an entry point that returns a hipError_t as int: leave with the first error.  PA_LAUNCH_TRY = launch, then leave if it failed.
+#define PA_TRY(expr) do { const int e_ = (int)(expr); if (e_ != 0) return e_; } while (0)
+#define PA_LAUNCH_TRY(...) do { PA_LAUNCH(__VA_ARGS__); PA_TRY(hipGetLastError()); } while (0)
+
+typedef unsigned long long u64;                                                          // what atomicAdd's 64-bit overload takes
+inline int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }                    // workspace sections start on 256 bytes

@@ -22,13 +22,11 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/painter_hip.h"
-#include "common.h"
+#include "painter_post.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int MAX_THR = 8;            // thresholds per decode
 constexpr int MAX_CAND = 65536;       // T * K
@@ -46,8 +44,6 @@ struct Layout {
     int64_t cnt, sum, rank, meta, inter, zero_end, surv_idx, surv_col, surv_cut, area, mness, score, ecomp, score2, src, masks, total;
     int ws;                           // mask row stride in words (multiple of 4: 16-byte panel loads)
 };
-
-inline int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 Layout layout(int h, int w, int K, int T, int nms_pre) {
     Layout L;
@@ -79,12 +75,6 @@ bool shape_ok(int h, int w, int K, int T) {
            (int64_t)T * K <= MAX_CAND;
 }
 
-DEVI uint32_t pack_colour(const float* __restrict__ pal, int c) {
-    return ((uint32_t)(int)pal[3 * c] & 255u) | (((uint32_t)(int)pal[3 * c + 1] & 255u) << 8) | (((uint32_t)(int)pal[3 * c + 2] & 255u) << 16);
-}
-DEVI uint32_t pack_pixel(const uint8_t* __restrict__ pic, int64_t p) {
-    return (uint32_t)pic[3 * p] | ((uint32_t)pic[3 * p + 1] << 8) | ((uint32_t)pic[3 * p + 2] << 16);
-}
 // The mask test  float(L1) / 3.0f < thr  is monotone in the integer L1 in [0, 765]: the number of L1 values that pass is the cut-off,
 // mask <=> L1 < cut.  All 256 threads of the workgroup call this; *s_cut must be visible as 0 before (the caller synchronises after).
 DEVI void count_cut(int* s_cut, float thr) {
@@ -381,8 +371,6 @@ int launch_inter(const uint32_t* masks, const int* n_dev, int n_rows, int ws, in
     return (int)hipGetLastError();
 }
 
-#define PA_TRY(expr) do { const int e_ = (int)(expr); if (e_ != 0) return e_; } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -461,27 +449,20 @@ int pa_inst_decode(const void* picture, const float* palette, const float* thres
     PA_TRY(hipMemsetAsync(out_candidates, 0, 4 * (size_t)max_num, stream));
     if (out_scores_f64) PA_TRY(hipMemsetAsync(out_scores_f64, 0, 8 * (size_t)max_num, stream));
     PA_TRY(launch_stats(pic, palette, thresholds, cnt, sum, h, w, n_colours, n_thr, stream));
-    PA_LAUNCH(inst_rank_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)((M + RANK_SPLIT - 1) / RANK_SPLIT)), dim3(256), 0, stream, cnt,
-              sum, rank, meta, M);
-    PA_TRY(hipGetLastError());
-    PA_LAUNCH(inst_select_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, cnt, sum, rank, palette, thresholds, surv_idx,
-              surv_col, surv_cut, area, mness, M, n_colours, n_thr, nms_pre);
-    PA_TRY(hipGetLastError());
+    PA_LAUNCH_TRY(inst_rank_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)((M + RANK_SPLIT - 1) / RANK_SPLIT)), dim3(256), 0, stream, cnt,
+                  sum, rank, meta, M);
+    PA_LAUNCH_TRY(inst_select_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, cnt, sum, rank, palette, thresholds, surv_idx,
+                  surv_col, surv_cut, area, mness, M, n_colours, n_thr, nms_pre);
     const unsigned pre_blocks = (unsigned)((nms_pre + 255) / 256);
-    PA_LAUNCH(inst_score_kernel, dim3(pre_blocks), dim3(256), 0, stream, mness, score, meta, nms_pre);
-    PA_TRY(hipGetLastError());
-    PA_LAUNCH(inst_bitmask_kernel, dim3((unsigned)((L.ws + 255) / 256), (unsigned)((nms_pre + MASK_GROUP - 1) / MASK_GROUP)), dim3(256), 0,
-              stream, pic, surv_col, surv_cut, meta, masks, npix, L.ws, nms_pre);
-    PA_TRY(hipGetLastError());
+    PA_LAUNCH_TRY(inst_score_kernel, dim3(pre_blocks), dim3(256), 0, stream, mness, score, meta, nms_pre);
+    PA_LAUNCH_TRY(inst_bitmask_kernel, dim3((unsigned)((L.ws + 255) / 256), (unsigned)((nms_pre + MASK_GROUP - 1) / MASK_GROUP)), dim3(256), 0,
+                  stream, pic, surv_col, surv_cut, meta, masks, npix, L.ws, nms_pre);
     PA_TRY(launch_inter(masks, meta + 1, nms_pre, L.ws, inter, nms_pre, stream));
     const dim3 nms_grid((unsigned)((nms_pre + 63) / 64)), nms_block(64, 16);
-    PA_LAUNCH(inst_nms_kernel<0>, nms_grid, nms_block, 0, stream, inter, nms_pre, area, meta, score, ecomp, score2, (double)sigma, kernel);
-    PA_TRY(hipGetLastError());
-    PA_LAUNCH(inst_nms_kernel<1>, nms_grid, nms_block, 0, stream, inter, nms_pre, area, meta, score, ecomp, score2, (double)sigma, kernel);
-    PA_TRY(hipGetLastError());
-    PA_LAUNCH(inst_final_kernel, dim3(pre_blocks), dim3(256), 0, stream, score2, surv_idx, meta, src, (int*)out_count, out_scores,
-              (double*)out_scores_f64, (int*)out_candidates, max_num);
-    PA_TRY(hipGetLastError());
+    PA_LAUNCH_TRY(inst_nms_kernel<0>, nms_grid, nms_block, 0, stream, inter, nms_pre, area, meta, score, ecomp, score2, (double)sigma, kernel);
+    PA_LAUNCH_TRY(inst_nms_kernel<1>, nms_grid, nms_block, 0, stream, inter, nms_pre, area, meta, score, ecomp, score2, (double)sigma, kernel);
+    PA_LAUNCH_TRY(inst_final_kernel, dim3(pre_blocks), dim3(256), 0, stream, score2, surv_idx, meta, src, (int*)out_count, out_scores,
+                  (double*)out_scores_f64, (int*)out_candidates, max_num);
     PA_LAUNCH(inst_gather_kernel, dim3((unsigned)((words + 255) / 256), (unsigned)max_num), dim3(256), 0, stream, masks, src,
               (const int*)out_count, (uint32_t*)out_masks, (uint8_t*)out_masks_u8, words, L.ws, npix);
     LAUNCH_CHECK();

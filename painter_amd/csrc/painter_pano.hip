@@ -23,13 +23,11 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/painter_hip.h"
-#include "common.h"
+#include "painter_post.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int64_t MAX_PIX = 1 << 24;  // h * w: S <= 2^24 * (765 + 195075) < 2^42
 constexpr int MAX_COL = 1024;         // n_colours
@@ -40,8 +38,6 @@ constexpr int PASTE_THREADS = 1024;
 struct Layout {
     int64_t S, hist, meta, U, zero_end, semmap, list, stuff_id, total;
 };
-
-inline int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 Layout layout(int h, int w, int K, int T, int max_inst) {
     Layout L;
@@ -63,12 +59,6 @@ bool shape_ok(int h, int w, int K, int T, int max_inst) {
     return h >= 1 && w >= 1 && (int64_t)h * w <= MAX_PIX && K >= 2 && K <= MAX_COL && T >= 2 && T <= K && max_inst >= 1 && max_inst <= MAX_INST;
 }
 
-DEVI uint32_t pack_colour(const float* __restrict__ pal, int c) {
-    return ((uint32_t)(int)pal[3 * c] & 255u) | (((uint32_t)(int)pal[3 * c + 1] & 255u) << 8) | (((uint32_t)(int)pal[3 * c + 2] & 255u) << 16);
-}
-DEVI uint32_t pack_pixel(const uint8_t* __restrict__ pic, int64_t p) {
-    return (uint32_t)pic[3 * p] | ((uint32_t)pic[3 * p + 1] << 8) | ((uint32_t)pic[3 * p + 2] << 16);
-}
 // The bits of word w that are pixels: all of them except in a last word that the picture does not fill.
 DEVI uint32_t pixel_bits(int w, int words, int64_t npix) {
     const int rest = (int)(npix & 31);
@@ -321,18 +311,15 @@ __global__ __launch_bounds__(256) void pano_paint_kernel(const int* __restrict__
         if (s_area[i]) atomicAdd(&seg[i].area, s_area[i]);
 }
 
-#define PA_TRY(expr) do { const int e_ = (int)(expr); if (e_ != 0) return e_; } while (0)
-
 int launch_vote(const uint8_t* pic, const float* pal, const uint32_t* masks, const int* n_dev, u64* S, int* classes, int h, int w, int T,
                 int dist_type, int max_inst, hipStream_t stream) {
     const int64_t npix = (int64_t)h * w;
     const int words = (int)((npix + 31) / 32);
     const dim3 grid((unsigned)((npix + PIX_CHUNK - 1) / PIX_CHUNK));
     PA_TRY(hipMemsetAsync(S, 0, 8 * (size_t)max_inst * T, stream));
-    if (dist_type == 0) PA_LAUNCH(pano_vote_kernel<0>, grid, dim3(256), 0, stream, pic, pal, masks, n_dev, S, npix, words, T, max_inst);
-    else if (dist_type == 1) PA_LAUNCH(pano_vote_kernel<1>, grid, dim3(256), 0, stream, pic, pal, masks, n_dev, S, npix, words, T, max_inst);
-    else PA_LAUNCH(pano_vote_kernel<2>, grid, dim3(256), 0, stream, pic, pal, masks, n_dev, S, npix, words, T, max_inst);
-    PA_TRY(hipGetLastError());
+    if (dist_type == 0) PA_LAUNCH_TRY(pano_vote_kernel<0>, grid, dim3(256), 0, stream, pic, pal, masks, n_dev, S, npix, words, T, max_inst);
+    else if (dist_type == 1) PA_LAUNCH_TRY(pano_vote_kernel<1>, grid, dim3(256), 0, stream, pic, pal, masks, n_dev, S, npix, words, T, max_inst);
+    else PA_LAUNCH_TRY(pano_vote_kernel<2>, grid, dim3(256), 0, stream, pic, pal, masks, n_dev, S, npix, words, T, max_inst);
     PA_LAUNCH(pano_classes_kernel, dim3((unsigned)((max_inst + 255) / 256)), dim3(256), 0, stream, S, n_dev, classes, T, max_inst);
     return (int)hipGetLastError();
 }
@@ -352,13 +339,10 @@ int launch_merge(const int* semmap, const uint32_t* masks, const float* scores, 
     int* stuff_id = (int*)(ws + L.stuff_id);
     PA_TRY(hipMemsetAsync(ws + L.hist, 0, (size_t)(L.zero_end - L.hist), stream));
     PA_TRY(hipMemsetAsync(seg, 0, sizeof(pa_pano_segment) * (size_t)(max_inst + K - T), stream));
-    PA_LAUNCH(pano_paste_kernel, dim3(1), dim3(PASTE_THREADS), 0, stream, masks, scores, n_dev, U, list, meta, words, npix, max_inst,
-              overlap_thr, score_thr);
-    PA_TRY(hipGetLastError());
-    PA_LAUNCH(pano_hist_kernel, dim3((unsigned)((npix + PIX_CHUNK - 1) / PIX_CHUNK)), dim3(256), 0, stream, semmap, U, hist, npix, T, K);
-    PA_TRY(hipGetLastError());
-    PA_LAUNCH(pano_ids_kernel, dim3(1), dim3(64), 0, stream, hist, list, classes, scores, meta, stuff_id, seg, out_count, T, K, stuff_thr);
-    PA_TRY(hipGetLastError());
+    PA_LAUNCH_TRY(pano_paste_kernel, dim3(1), dim3(PASTE_THREADS), 0, stream, masks, scores, n_dev, U, list, meta, words, npix, max_inst,
+                  overlap_thr, score_thr);
+    PA_LAUNCH_TRY(pano_hist_kernel, dim3((unsigned)((npix + PIX_CHUNK - 1) / PIX_CHUNK)), dim3(256), 0, stream, semmap, U, hist, npix, T, K);
+    PA_LAUNCH_TRY(pano_ids_kernel, dim3(1), dim3(64), 0, stream, hist, list, classes, scores, meta, stuff_id, seg, out_count, T, K, stuff_thr);
     PA_LAUNCH(pano_paint_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, semmap, masks, U, list, meta, stuff_id, panoptic,
               rgb, seg, npix, words, T, K);
     return (int)hipGetLastError();

@@ -27,13 +27,9 @@
 
 namespace {
 
-typedef unsigned long long u64;
-
 constexpr int MAX_K = 32;             // keypoint channels
 constexpr int PIX_CHUNK = 2048;       // pixels per workgroup of the peak search
 constexpr int THREADS = 256;
-
-#define PA_TRY(expr) do { const int e_ = (int)(expr); if (e_ != 0) return e_; } while (0)
 
 struct Pose {
     const uint8_t* P;      // [n][H][W][3]
@@ -237,8 +233,7 @@ int pa_pose_keypoints(const void* pictures, const void* flipped, const void* pal
     const int chunks = (int)(((int64_t)h * w + PIX_CHUNK - 1) / PIX_CHUNK);
     const int64_t total = (int64_t)n * n_keypoints;
     PA_TRY(hipMemsetAsync(workspace, 0, 8 * (size_t)total, stream));
-    PA_LAUNCH(pose_peak_kernel, dim3((unsigned)((int64_t)chunks * n)), dim3(THREADS), 0, stream, a, (u64*)workspace, chunks);
-    PA_TRY(hipGetLastError());
+    PA_LAUNCH_TRY(pose_peak_kernel, dim3((unsigned)((int64_t)chunks * n)), dim3(THREADS), 0, stream, a, (u64*)workspace, chunks);
     PA_LAUNCH(pose_finish_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, a, (const u64*)workspace,
               out_preds, out_maxvals, total);
     LAUNCH_CHECK();

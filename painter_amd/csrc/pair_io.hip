@@ -19,8 +19,6 @@
 
 namespace {
 
-typedef unsigned long long u64;
-
 // float32 division with IEEE rounding irrespective of the compiler's fp32-division mode: the double quotient rounded to float is the
 // correctly rounded float quotient (53 >= 2 * 24 + 2 bits, so the double rounding is innocuous).
 DEVI float fdiv(float a, float b) { return (float)((double)a / (double)b); }

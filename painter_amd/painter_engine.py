@@ -34,8 +34,13 @@ canvases the script built, or pass an already resized 448 x 448 uint8 query to `
 evaluators apart from the colour -> class decode (`class_map`), the instance decode (`instances`) and the panoptic merge (`panoptic`);
 PQ computation and PNG encoding; of the pose route mmpose's OKS NMS, rescoring and COCOeval, and the 34 numbers per box of `to_image`.
 
+One host path serves the routes: `_device` / `_pictures` put the inputs of a call on one indexed CUDA device; INSTANCE_DEFAULTS,
+MERGE_DEFAULTS and POSE_DEFAULTS hold the keyword defaults and `_check_arguments` refuses the rest before a forward is enqueued; an output
+buffer is one list of sections (`_layout`): its size, the pointers handed to the library and the slices of `result()` all come from it.
+
 There is no CPU fallback: a CPU device or a missing libpainter_hip.so raises.
 """
+import contextlib
 import ctypes
 import functools
 
@@ -78,11 +83,79 @@ def _unwrap(model):
     return model.module if hasattr(model, "module") else model          # the scripts wrap the model in DistributedDataParallel
 
 
-def _require_cuda(device):
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("painter_amd.painter_engine runs its image kernels on an MI355X only (no CPU fallback); got %s" % device)
-    return device
+def _device(inputs=(), device="cuda"):
+    """The one device of a call, always with its index: that of the tensors among `inputs` (pictures, masks, lists of them, None), else
+    `device`.  CPU is refused first -- a host address must never reach a kernel -- and so are tensors on two devices."""
+    tensors = [t for x in inputs for t in (x if isinstance(x, (list, tuple)) else [x]) if torch.is_tensor(t)]
+    devices = {t.device for t in tensors} or {torch.device(device)}
+    for d in devices:
+        if d.type != "cuda":
+            raise RuntimeError("painter_amd.painter_engine runs its image kernels on an MI355X only (no CPU fallback); got %s" % d)
+    if len(devices) > 1:
+        raise RuntimeError("painter_engine: the inputs are on %s" % " and ".join(sorted(str(d) for d in devices)))
+    d = devices.pop()
+    return d if d.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _pictures(x, device, batch=False):
+    """A picture [H][W][3] or, with `batch`, [n][H][W][3] / a list of [H][W][3] of one size (numpy or CUDA tensors) -> contiguous uint8
+    CUDA tensor on `device` (what `_device` returned)."""
+    if batch and isinstance(x, (list, tuple)):
+        assert len(x) >= 1 and len({tuple(p.shape) for p in x}) == 1, "painter_engine: the pictures of a batch have one size"
+        x = torch.stack(list(x)) if torch.is_tensor(x[0]) else np.stack(x)
+    x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).to(device)
+    if x.device != device:
+        raise RuntimeError("painter_engine: the pictures are on %s, expected %s" % (x.device, device))
+    assert x.dtype == torch.uint8 and x.dim() == 3 + batch and x.shape[-1] == 3, (x.dtype, tuple(x.shape))
+    return x.contiguous()
+
+
+def _rgb_palette(palette, default):
+    """[K][3] colours, or None for `default()` -> float32 numpy [K][3], a copy (the default palettes are cached and read-only)."""
+    pal = np.array(default() if palette is None else palette, dtype=np.float32, order="C")
+    assert pal.ndim == 2 and pal.shape[1] == 3 and (pal == np.floor(pal)).all() and pal.min() >= 0 and pal.max() <= 255, \
+        "painter_engine: the palette holds integer colours 0..255"
+    return pal
+
+
+def _check_arguments(who, kw, *tables):
+    """What can be refused before anything is enqueued: a keyword no default table has, an unknown `dist_type` or NMS `kernel`."""
+    unknown = set(kw).difference(*tables)
+    if unknown:
+        raise TypeError("%s: unexpected arguments %s" % (who, sorted(unknown)))
+    if "dist_type" in kw and kw["dist_type"] not in DIST_TYPES:
+        raise NotImplementedError(kw["dist_type"])
+    if "kernel" in kw and kw["kernel"] not in NMS_KERNELS:
+        raise NotImplementedError("%s kernel is not supported in matrix nms!" % kw["kernel"])
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """The model in eval mode; it goes back to the mode it had."""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
+
+
+def _layout(sections, base=0):
+    """sections = [(name, dtype, count, alignment)] in buffer order, from byte `base` -> ({name: (byte offset, dtype, count)}, end).  An
+    empty section takes no room, not even its padding: `end` is where the last section that holds something ends."""
+    at, o, end = {}, base, base
+    for name, dtype, count, align in sections:
+        o, dtype, count = -(-o // align) * align, np.dtype(dtype), int(count)
+        at[name] = (o, dtype, count)
+        o += dtype.itemsize * count
+        end = o if count else end
+    return at, end
+
+
+def _section(host, at, name, count=None):
+    """The first `count` elements (default: all) of a section of `_layout` in the buffer's host copy, in the section's dtype."""
+    off, dtype, n = at[name]
+    return host[off:off + dtype.itemsize * (n if count is None else count)].view(dtype)
 
 
 def _forward(model, imgs, tgts):
@@ -136,6 +209,17 @@ class DecodePlan:
             check(lib.pa_painter_decode_f64(*args, _stream()), "pa_painter_decode_f64")
         return self
 
+    def picture(self, i):
+        """Picture i of the output as a device view [H][W][3] (depth: [H][W])."""
+        off, shape = self.views[i]
+        return self.out[off:off + int(np.prod(shape))].view(shape)
+
+    def run_of(self, first, count):
+        """Pictures first .. first + count, all of one size, as ONE device view [count][H][W][3]."""
+        off, shape = self.views[first]
+        assert all(v[1] == shape for v in self.views[first:first + count]) and first + count <= self.n_jobs
+        return self.out[off:off + count * int(np.prod(shape))].view((count,) + shape)
+
     def pictures(self):
         """The copy back (and the one synchronisation) -> one numpy array per picture."""
         return _split(self.out, self.views)
@@ -160,11 +244,9 @@ def _split(flat, views):
 def class_map(picture, palette, dist_type="abs", device="cuda"):
     """ADE20kSemSegEvaluatorCustom.post_process_segm_output (:114-141): uint8 [H][W][3] picture (numpy or CUDA tensor), palette
     [K][3] -> int32 [H][W] numpy, the index of the nearest palette colour (first minimum)."""
-    device = _require_cuda(picture.device if torch.is_tensor(picture) else device)
-    if dist_type not in DIST_TYPES:
-        raise NotImplementedError(dist_type)
-    img = picture if torch.is_tensor(picture) else torch.from_numpy(np.ascontiguousarray(picture)).to(device)
-    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.is_contiguous(), (img.dtype, tuple(img.shape))
+    device = _device([picture], device)
+    _check_arguments("class_map", dict(dist_type=dist_type), MERGE_DEFAULTS)
+    img = _pictures(picture, device)
     pal = torch.as_tensor(np.asarray(palette), dtype=torch.float32).to(device).contiguous()
     assert pal.dim() == 2 and pal.shape[1] == 3, tuple(pal.shape)
     h, w = int(img.shape[0]), int(img.shape[1])
@@ -175,6 +257,11 @@ def class_map(picture, palette, dist_type="abs", device="cuda"):
 
 
 NMS_KERNELS = {"gaussian": 0, "linear": 1}
+# The keyword families and their defaults, written once: the run_* entry points read them, the public signatures repeat them for their
+# readers (tests/test_painter_pano_cpu.py holds them to it).  INSTANCE_ and POSE_DEFAULTS are in InstanceDecode's / PoseDecode's order.
+INSTANCE_DEFAULTS = dict(palette=None, dist_thr=19.0, nms_pre=2000, max_num=100, kernel="gaussian", sigma=2.0)
+MERGE_DEFAULTS = dict(semseg_palette=None, n_things=80, dist_type="abs", overlap_threshold=0.5, stuff_area_thresh=8192,
+                      instances_score_thresh=0.55)                                   # get_args_parser_pano_seg (COCOPanoEvaluatorCustom.py:279-297)
 
 
 @functools.lru_cache(maxsize=4)
@@ -196,14 +283,10 @@ class InstanceDecode:
 
     def __init__(self, picture, palette, thresholds, nms_pre, max_num, kernel, sigma, tail=0):
         """tail: further bytes at the end of the output buffer, from offset `self.tail`, for what a caller chains behind the decode."""
-        if kernel not in NMS_KERNELS:
-            raise NotImplementedError("%s kernel is not supported in matrix nms!" % kernel)
-        self.img = img = picture
-        dev = img.device
-        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.is_contiguous(), (img.dtype, tuple(img.shape))
-        pal = np.ascontiguousarray(np.asarray(location_palette() if palette is None else palette, dtype=np.float32))
-        assert pal.ndim == 2 and pal.shape[1] == 3 and (pal == np.floor(pal)).all() and pal.min() >= 0 and pal.max() <= 255, \
-            "painter_engine: the palette holds integer colours 0..255"
+        _check_arguments("InstanceDecode", dict(kernel=kernel), INSTANCE_DEFAULTS)
+        dev = picture.device
+        self.img = img = _pictures(picture, dev)
+        pal = _rgb_palette(palette, location_palette)
         thr = np.atleast_1d(np.asarray(thresholds, dtype=np.float32))
         self.h, self.w, self.k, self.n_thr = int(img.shape[0]), int(img.shape[1]), int(pal.shape[0]), int(thr.size)
         self.nms_pre, self.max_num = int(nms_pre), int(max_num)
@@ -215,16 +298,17 @@ class InstanceDecode:
         self.shape = shape
         self.params = torch.from_numpy(np.concatenate([pal.ravel(), thr])).to(dev, non_blocking=True)
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        m, hw = self.max_num, self.h * self.w
-        # ONE byte buffer: int32 count | float64 scores [m] | float32 scores [m] | int32 candidates [m] | bit masks [m][words] | byte masks [m][h * w]
-        self.o64, self.o32, self.oidx, self.obits = 8, 8 + 8 * m, 8 + 12 * m, 8 + 16 * m
-        self.obytes = self.obits + 4 * m * self.words
-        self.tail = (self.obytes + m * hw + 15) // 16 * 16
-        self.out = torch.zeros(self.tail + int(tail) if tail else self.obytes + m * hw, dtype=torch.uint8, device=dev)
-        at = lambda off: self.out.data_ptr() + off
+        m = self.max_num
+        # ONE byte buffer, every output a section of it
+        self.at, size = _layout([("count", np.int32, 1, 1), ("scores_f64", np.float64, m, 8), ("scores", np.float32, m, 1),
+                                 ("candidates", np.int32, m, 1), ("bits", np.uint32, m * self.words, 1), ("masks", np.bool_, m * self.h * self.w, 1),
+                                 ("tail", np.uint8, int(tail), 16)])
+        self.o32, self.obits, self.obytes, self.tail = (self.at[name][0] for name in ("scores", "bits", "masks", "tail"))
+        self.out = torch.zeros(size, dtype=torch.uint8, device=dev)
+        ptr = lambda name: self.out.data_ptr() + self.at[name][0]
         check(lib.pa_inst_decode(img.data_ptr(), self.params.data_ptr(), self.params.data_ptr() + 4 * pal.size, self.h, self.w, self.k,
-                                 self.n_thr, self.nms_pre, m, float(sigma), NMS_KERNELS[kernel], self.workspace.data_ptr(), at(0),
-                                 at(self.o32), at(self.o64), at(self.oidx), at(self.obits), at(self.obytes), _stream()), "pa_inst_decode")
+                                 self.n_thr, self.nms_pre, m, float(sigma), NMS_KERNELS[kernel], self.workspace.data_ptr(), ptr("count"),
+                                 ptr("scores"), ptr("scores_f64"), ptr("candidates"), ptr("bits"), ptr("masks"), _stream()), "pa_inst_decode")
 
     def section(self, which, dtype, count):
         """A section of the workspace (pa_inst_workspace_offset) as a numpy array: for tests and tools."""
@@ -235,20 +319,20 @@ class InstanceDecode:
         """The copy back (and the one synchronisation).  The bool masks are a view of the bytes the device wrote.  host: the output
         buffer as numpy, if the caller has copied it back already."""
         a = self.out.cpu().numpy() if host is None else host
-        n, m, hw = int(a[:4].view(np.int32)[0]), self.max_num, self.h * self.w
+        n = int(_section(a, self.at, "count")[0])
         if n == 0:              # no candidate: the reference's single all-zero mask with score 0 and label 0 (:302-310)
             res = dict(scores=np.zeros(1, np.float32), labels=np.zeros(1, np.float32), masks=np.zeros((1, self.h, self.w), bool),
                        candidates=np.full(1, -1, np.int32))
             if with_f64:
                 res["scores_f64"] = np.zeros(1)
             return res
-        res = dict(scores=a[self.o32:self.o32 + 4 * n].view(np.float32), labels=np.ones(n, np.float32),
-                   masks=a[self.obytes:self.obytes + n * hw].view(bool).reshape(n, self.h, self.w),
-                   candidates=a[self.oidx:self.oidx + 4 * n].view(np.int32))
+        res = dict(scores=_section(a, self.at, "scores", n), labels=np.ones(n, np.float32),
+                   masks=_section(a, self.at, "masks", n * self.h * self.w).reshape(n, self.h, self.w),
+                   candidates=_section(a, self.at, "candidates", n))
         if with_f64:
-            res["scores_f64"] = a[self.o64:self.o64 + 8 * n].view(np.float64)
+            res["scores_f64"] = _section(a, self.at, "scores_f64", n)
         if with_bits:
-            res["bits"] = a[self.obits:self.obits + 4 * m * self.words].view(np.uint32).reshape(m, self.words)[:n]
+            res["bits"] = _section(a, self.at, "bits", n * self.words).reshape(n, self.words)
         return res
 
 
@@ -257,14 +341,13 @@ def instances(picture, palette=None, dist_thr=19.0, nms_pre=2000, max_num=100, k
     uint8 [H][W][3] picture (numpy or CUDA tensor), palette [K][3] (default `location_palette()`), dist_thr a threshold or a list of them
     -> dict(scores float32 [n], labels float32 [n], masks bool [n][H][W], candidates int32 [n] = t * K + c of each instance).
     Ties are defined (include/painter_hip.h): exact integer statistics, rational maskness order, stable sorts, float64 NMS."""
-    device = _require_cuda(picture.device if torch.is_tensor(picture) else device)
-    img = picture if torch.is_tensor(picture) else torch.from_numpy(np.ascontiguousarray(picture)).to(device)
-    return InstanceDecode(img, palette, dist_thr, nms_pre, max_num, kernel, sigma).result()
+    return InstanceDecode(_pictures(picture, _device([picture], device)), palette, dist_thr, nms_pre, max_num, kernel, sigma).result()
 
 
 # ---- pose keypoints (csrc/painter_pose.hip)
 # configs/_base_/coco.py: the left / right partners (`swap`) of COCO's 17 keypoints
 COCO_FLIP_PAIRS = ((1, 2), (3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16))
+POSE_DEFAULTS = dict(palette=None, flip_pairs=COCO_FLIP_PAIRS, shift_heatmap=True)
 
 
 @functools.lru_cache(maxsize=4)
@@ -278,18 +361,6 @@ def pose_palette(num_locations=17):
     assert pal.min() >= 0 and len({tuple(c) for c in pal.tolist()}) == len(pal)
     pal.setflags(write=False)                  # cached: every caller sees the same array
     return pal
-
-
-def _pose_batch(pictures, device):
-    """uint8 [n][H][W][3] or a list of [H][W][3] of one size (numpy or CUDA tensors) -> contiguous uint8 CUDA tensor [n][H][W][3]."""
-    if isinstance(pictures, (list, tuple)):
-        assert len(pictures) >= 1 and len({tuple(p.shape) for p in pictures}) == 1, "painter_engine: the pictures of a pose batch have one size"
-        pictures = torch.stack(list(pictures)) if torch.is_tensor(pictures[0]) else np.stack(pictures)
-    x = pictures if torch.is_tensor(pictures) else torch.from_numpy(np.ascontiguousarray(pictures)).to(device)
-    if _require_cuda(x.device) != device:
-        raise RuntimeError("painter_engine: the pictures are on %s, expected %s" % (x.device, device))
-    assert x.dtype == torch.uint8 and x.dim() == 4 and x.shape[3] == 3, (x.dtype, tuple(x.shape))
-    return x.contiguous()
 
 
 class PoseDecode:
@@ -331,13 +402,8 @@ class PoseDecode:
 
 
 def _pose_inputs(pictures, flipped, device):
-    tensors = [p for x in (pictures, flipped) if x is not None for p in (x if isinstance(x, (list, tuple)) else [x]) if torch.is_tensor(p)]
-    for t in tensors:
-        _require_cuda(t.device)
-    device = _require_cuda(tensors[0].device if tensors else device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return _pose_batch(pictures, device), None if flipped is None else _pose_batch(flipped, device)
+    device = _device([pictures, flipped], device)
+    return _pictures(pictures, device, batch=True), None if flipped is None else _pictures(flipped, device, batch=True)
 
 
 def keypoints(pictures, flipped=None, palette=None, flip_pairs=COCO_FLIP_PAIRS, shift_heatmap=True, device="cuda"):
@@ -377,7 +443,6 @@ def to_image(preds, center, scale, heatmap_size):
 # ---- panoptic merge (csrc/painter_pano.hip)
 SEGMENT = np.dtype([("id", np.int32), ("isthing", np.int32), ("category_id", np.int32), ("instance_id", np.int32), ("area", np.int32),
                     ("score", np.float32)])                                             # pa_pano_segment of include/painter_hip.h
-_INSTANCE_ARGS = dict(palette=None, dist_thr=19.0, nms_pre=2000, max_num=100, kernel="gaussian", sigma=2.0)
 
 
 @functools.lru_cache(maxsize=4)
@@ -398,19 +463,6 @@ def id2rgb(id_map):
     return np.stack([m % 256, m // 256 % 256, m // 65536], -1).astype(np.uint8)
 
 
-def _picture(picture, device):
-    img = picture if torch.is_tensor(picture) else torch.from_numpy(np.ascontiguousarray(picture)).to(device)
-    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.is_contiguous(), (img.dtype, tuple(img.shape))
-    return img
-
-
-def _semantic_palette_array(palette):
-    pal = np.array(semantic_palette() if palette is None else palette, dtype=np.float32, order="C")          # a copy: the cached palette is read-only
-    assert pal.ndim == 2 and pal.shape[1] == 3 and (pal == np.floor(pal)).all() and pal.min() >= 0 and pal.max() <= 255, \
-        "painter_engine: the palette holds integer colours 0..255"
-    return pal
-
-
 def _host_array(values, dtype):
     """Scores / classes of supplied instances (list, numpy or a tensor on any device) -> flat numpy array."""
     return np.asarray(values.detach().cpu() if torch.is_tensor(values) else values).astype(dtype).ravel()
@@ -418,10 +470,13 @@ def _host_array(values, dtype):
 
 def _bit_masks(masks, h, w, device):
     """bool / uint8 [n][H][W] (numpy or CUDA tensor), or bit masks uint32 [n][ceil(H W / 32)] (the `bits` of an InstanceDecode) -> int32
-    CUDA tensor [max(n, 1)][words] in pa_inst_decode's bit layout, n.  device: the picture tensor's own device (with its index); a mask
-    tensor anywhere else is refused."""
+    CUDA tensor [max(n, 1)][words] in pa_inst_decode's bit layout, n.  device: what `_device` returned for the call; a mask tensor
+    anywhere else is refused."""
     words = (h * w + 31) // 32
-    if not torch.is_tensor(masks):
+    if torch.is_tensor(masks):
+        if _device([masks]) != device:                               # a host or foreign address must never reach a kernel
+            raise RuntimeError("painter_engine: the masks are on %s, the picture on %s" % (masks.device, device))
+    else:
         masks = np.asarray(masks)
         if masks.dtype == np.uint32:
             assert masks.ndim == 2 and masks.shape[1] == words, masks.shape
@@ -429,8 +484,6 @@ def _bit_masks(masks, h, w, device):
         else:
             masks = np.ascontiguousarray(masks).view(np.uint8) if masks.dtype == bool else np.ascontiguousarray(masks, dtype=np.uint8)
         masks = torch.from_numpy(masks).to(device)
-    if _require_cuda(masks.device) != device:                        # a host or foreign address must never reach a kernel
-        raise RuntimeError("painter_engine: the masks are on %s, the picture on %s" % (masks.device, device))
     n = int(masks.shape[0])
     if masks.dtype == torch.int32:
         assert masks.dim() == 2 and masks.shape[1] == words, tuple(masks.shape)
@@ -448,14 +501,10 @@ def classify_instances(semseg_picture, masks, palette=None, n_things=80, dist_ty
     to in sum, as exact integers, ties to the lower class, class 0 for an empty mask.  semseg_picture: the painted `coco_pano_semseg`
     picture, uint8 [H][W][3] (numpy or CUDA tensor); masks: bool / uint8 [n][H][W] (numpy or CUDA tensor) or the uint32 `bits` of an
     InstanceDecode -> int32 [n] numpy."""
-    device = _require_cuda(semseg_picture.device if torch.is_tensor(semseg_picture) else device)
-    if torch.is_tensor(masks):
-        _require_cuda(masks.device)
-    if dist_type not in DIST_TYPES:
-        raise NotImplementedError(dist_type)
-    img = _picture(semseg_picture, device)
-    device = img.device
-    pal = _semantic_palette_array(palette)
+    device = _device([semseg_picture, masks], device)
+    _check_arguments("classify_instances", dict(dist_type=dist_type), MERGE_DEFAULTS)
+    img = _pictures(semseg_picture, device)
+    pal = _rgb_palette(palette, semantic_palette)
     h, w, k = int(img.shape[0]), int(img.shape[1]), int(pal.shape[0])
     bits, n = _bit_masks(masks, h, w, device)
     m = int(bits.shape[0])
@@ -474,17 +523,22 @@ class PanopticDecode:
     back and one synchronisation for both.  With supplied instances (dict(masks=, scores=, classes=None)) it owns its output buffer."""
 
     @staticmethod
+    def sections(h, w, k, n_things, max_inst):
+        """The output buffer: count (a 16-byte slot), a segment per instance and stuff class, the instances' classes, the map, its id2rgb."""
+        return [("count", np.int32, 1, 1), ("segments", SEGMENT, max_inst + k - n_things, 16), ("classes", np.int32, max_inst, 1),
+                ("panoptic", np.int32, h * w, 1), ("rgb", np.uint8, 3 * h * w, 1)]
+
+    @staticmethod
     def out_bytes(h, w, k, n_things, max_inst):
-        return 16 + SEGMENT.itemsize * (max_inst + k - n_things) + 4 * max_inst + 7 * h * w
+        return _layout(PanopticDecode.sections(h, w, k, n_things, max_inst))[1]
 
     def __init__(self, semseg_picture, decode=None, supplied=None, palette=None, n_things=80, dist_type="abs", overlap_threshold=0.5,
                  stuff_area_thresh=8192, instances_score_thresh=0.55):
-        if dist_type not in DIST_TYPES:
-            raise NotImplementedError(dist_type)
+        _check_arguments("PanopticDecode", dict(dist_type=dist_type), MERGE_DEFAULTS)
         assert (decode is None) != (supplied is None)
-        self.img = img = semseg_picture
-        dev = img.device
-        pal = _semantic_palette_array(palette)
+        dev = semseg_picture.device
+        self.img = img = _pictures(semseg_picture, dev)
+        pal = _rgb_palette(palette, semantic_palette)
         self.h, self.w, self.k, self.n_things = int(img.shape[0]), int(img.shape[1]), int(pal.shape[0]), int(n_things)
         self.decode, self.supplied = decode, supplied
         given = None
@@ -508,64 +562,47 @@ class PanopticDecode:
         nbytes = lib.pa_pano_workspace_bytes(*shape)
         if nbytes < 0:
             check(1, "pa_pano_decode (sizes %s)" % (shape,))
+        self.at, end = _layout(self.sections(*shape), self.base)
         if decode is None:
-            self.out = torch.zeros(self.out_bytes(*shape), dtype=torch.uint8, device=dev)
-        assert self.out.numel() >= self.base + self.out_bytes(*shape)
-        self.cap = self.max_inst + self.k - self.n_things
-        self.oseg, hw = self.base + 16, self.h * self.w
-        self.ocls = self.oseg + SEGMENT.itemsize * self.cap
-        self.opan = self.ocls + 4 * self.max_inst
-        self.orgb = self.opan + 4 * hw
+            self.out = torch.zeros(end, dtype=torch.uint8, device=dev)
+        assert self.out.numel() >= end
         self.palette = torch.from_numpy(pal).to(dev, non_blocking=True)
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        at = lambda off: self.out.data_ptr() + off
+        ptr = lambda name: self.out.data_ptr() + self.at[name][0]
         check(lib.pa_pano_decode(img.data_ptr(), self.palette.data_ptr(), masks, scores, count, None if given is None else given.data_ptr(),
                                  *shape[:4], DIST_TYPES[dist_type], self.max_inst, float(overlap_threshold), float(stuff_area_thresh),
-                                 float(instances_score_thresh), self.workspace.data_ptr(), at(self.opan), at(self.orgb), at(self.base),
-                                 at(self.oseg), at(self.ocls), _stream()), "pa_pano_decode")
+                                 float(instances_score_thresh), self.workspace.data_ptr(), ptr("panoptic"), ptr("rgb"), ptr("count"),
+                                 ptr("segments"), ptr("classes"), _stream()), "pa_pano_decode")
 
     def result(self):
         """The copy back (and the one synchronisation) -> the dict `panoptic` documents."""
         a = self.out.cpu().numpy()
-        hw = self.h * self.w
         if self.decode is not None:
             inst = self.decode.result(host=a)
-            scores, masks, n = inst["scores"], inst["masks"], int(a[:4].view(np.int32)[0])
+            scores, masks, n = inst["scores"], inst["masks"], int(_section(a, self.decode.at, "count")[0])
         else:
             masks = self.supplied["masks"]                          # handed back as they came: no copy of what the caller has
             scores, n = _host_array(self.supplied["scores"], np.float32), self.n
-        count = int(a[self.base:self.base + 4].view(np.int32)[0])
-        table = a[self.oseg:self.oseg + SEGMENT.itemsize * count].view(SEGMENT)
+        table = _section(a, self.at, "segments", int(_section(a, self.at, "count")[0]))
         segments = [dict(id=int(s["id"]), isthing=True, score=float(s["score"]), category_id=int(s["category_id"]),
                          instance_id=int(s["instance_id"])) if s["isthing"] else
                     dict(id=int(s["id"]), isthing=False, category_id=int(s["category_id"]), area=int(s["area"])) for s in table]
-        classes = a[self.ocls:self.ocls + 4 * n].view(np.int32) if n else np.zeros(len(scores), np.int32)
-        return dict(panoptic=a[self.opan:self.opan + 4 * hw].view(np.int32).reshape(self.h, self.w), segments=segments, classes=classes,
-                    scores=scores, masks=masks, rgb=a[self.orgb:self.orgb + 3 * hw].reshape(self.h, self.w, 3), areas=table["area"].copy())
-
-
-def _check_panoptic_args(dist_type, instances_kw):
-    """What can be refused before anything is enqueued."""
-    unknown = set(instances_kw) - set(_INSTANCE_ARGS)
-    if unknown:
-        raise TypeError("panoptic: unexpected arguments %s" % sorted(unknown))
-    if dist_type not in DIST_TYPES:
-        raise NotImplementedError(dist_type)
-    if instances_kw.get("kernel", "gaussian") not in NMS_KERNELS:
-        raise NotImplementedError("%s kernel is not supported in matrix nms!" % instances_kw["kernel"])
+        classes = _section(a, self.at, "classes", n) if n else np.zeros(len(scores), np.int32)
+        return dict(panoptic=_section(a, self.at, "panoptic").reshape(self.h, self.w), segments=segments, classes=classes, scores=scores,
+                    masks=masks, rgb=_section(a, self.at, "rgb").reshape(self.h, self.w, 3), areas=table["area"].copy())
 
 
 def _launch_panoptic(sem, inst, instances, semseg_palette, n_things, merge, instances_kw):
     """sem, inst: uint8 CUDA pictures (inst None with supplied instances) -> the launched PanopticDecode."""
-    _check_panoptic_args(merge["dist_type"], instances_kw)
+    _check_arguments("panoptic", dict(instances_kw, **merge), INSTANCE_DEFAULTS, MERGE_DEFAULTS)
     if (inst is None) == (instances is None):
         raise TypeError("panoptic: give either the painted coco_pano_inst picture or instances=dict(masks=, scores=, classes=None)")
     dec = None
     if inst is not None:
-        a = dict(_INSTANCE_ARGS, **instances_kw)
-        k = len(_semantic_palette_array(semseg_palette))
+        a = dict(INSTANCE_DEFAULTS, **instances_kw)
+        k = len(_rgb_palette(semseg_palette, semantic_palette))
         tail = PanopticDecode.out_bytes(int(sem.shape[0]), int(sem.shape[1]), k, int(n_things), int(a["max_num"]))
-        dec = InstanceDecode(inst, a["palette"], a["dist_thr"], a["nms_pre"], a["max_num"], a["kernel"], a["sigma"], tail=tail)
+        dec = InstanceDecode(inst, *a.values(), tail=tail)
     elif instances_kw:
         raise TypeError("panoptic: %s belong to the instance decode, which supplied instances skip" % sorted(instances_kw))
     return PanopticDecode(sem, dec, instances, semseg_palette, n_things, **merge)
@@ -588,14 +625,9 @@ def panoptic(semseg_picture, inst_picture=None, *, instances=None, semseg_palett
     [n], scores float32 [n], masks bool [n][H][W] (supplied masks: the caller's own object), rgb uint8 [H][W][3] = id2rgb(panoptic), what
     the evaluator encodes as PNG).  When the
     instance decode finds no candidate the instances are the reference's single zero mask with score 0 and class 0, which adds nothing."""
-    tensors = [p for p in (semseg_picture, inst_picture) if torch.is_tensor(p)]
-    for t in tensors + [m for m in [(instances or {}).get("masks")] if torch.is_tensor(m)]:
-        _require_cuda(t.device)
-    device = _require_cuda(tensors[0].device if tensors else device)
-    if len({t.device for t in tensors}) > 1:
-        raise RuntimeError("painter_engine: the two pictures are on %s" % " and ".join(str(t.device) for t in tensors))
-    sem = _picture(semseg_picture, device)
-    inst = None if inst_picture is None else _picture(inst_picture, device)
+    device = _device([semseg_picture, inst_picture, (instances or {}).get("masks")], device)
+    sem = _pictures(semseg_picture, device)
+    inst = None if inst_picture is None else _pictures(inst_picture, device)
     merge = dict(dist_type=dist_type, overlap_threshold=overlap_threshold, stuff_area_thresh=stuff_area_thresh,
                  instances_score_thresh=instances_score_thresh)
     return _launch_panoptic(sem, inst, instances, semseg_palette, n_things, merge, instances_kw).result()
@@ -608,30 +640,21 @@ def run_panoptic(semseg_engine, inst_engine, pictures, sizes=None, **kw):
     if semseg_engine.task != "coco_pano_semseg" or inst_engine.task != "coco_pano_inst":
         raise ValueError("painter_engine: run_panoptic takes a coco_pano_semseg engine and a coco_pano_inst engine, not %r and %r"
                          % (semseg_engine.task, inst_engine.task))
-    kw = dict(kw)
-    kw.pop("device", None)
-    top = dict(semseg_palette=None, n_things=80)
-    merge = dict(dist_type="abs", overlap_threshold=0.5, stuff_area_thresh=8192, instances_score_thresh=0.55)
-    top.update((k, kw.pop(k)) for k in list(kw) if k in top)
-    merge.update((k, kw.pop(k)) for k in list(kw) if k in merge)
-    _check_panoptic_args(merge["dist_type"], kw)          # before the first forward is enqueued, as run_instances does
-    view = lambda plan, v: plan.out[v[0]:v[0] + int(np.prod(v[1]))].view(v[1])
+    kw = {k: v for k, v in kw.items() if k != "device"}
+    _check_arguments("panoptic", kw, INSTANCE_DEFAULTS, MERGE_DEFAULTS)          # before the first forward is enqueued
+    merge = {k: kw.pop(k, v) for k, v in MERGE_DEFAULTS.items()}                 # kw keeps what belongs to the instance decode
+    palette, n_things = merge.pop("semseg_palette"), merge.pop("n_things")
 
     def batch(pics, sizes):
         sem = semseg_engine._launch_batch(pics, sizes, False)
         jobs, step = [], inst_engine.batch_size
         for j in range(0, len(pics), step):
             inst = inst_engine._launch_batch(pics[j:j + step], sizes[j:j + step], False)
-            jobs += [_launch_panoptic(view(sem, sv), view(inst, iv), None, top["semseg_palette"], top["n_things"], merge, kw)
-                     for sv, iv in zip(sem.views[j:j + step], inst.views)]
+            jobs += [_launch_panoptic(sem.picture(j + i), inst.picture(i), None, palette, n_things, merge, kw) for i in range(inst.n_jobs)]
         return [j.result() for j in jobs]
 
-    was_training = inst_engine.model.training
-    inst_engine.model.eval()
-    try:
+    with _eval_mode(inst_engine.model):
         return [o for b in semseg_engine._run(pictures, sizes, batch) for o in b]
-    finally:
-        inst_engine.model.train(was_training)
 
 
 class PainterEngine:
@@ -639,7 +662,7 @@ class PainterEngine:
     (`Image.resize((input_size, input_size))`, Pillow-exact) and kept on the device."""
 
     def __init__(self, model, device, task, prompt_img, prompt_tgt, input_size=448, batch_size=8):
-        self.device = _require_cuda(device)
+        self.device = _device((), device)
         self.task, self.spec = task, _task(task)
         self.model = _unwrap(model)
         self.res = int(input_size)
@@ -676,20 +699,14 @@ class PainterEngine:
         plan = self._launch_batch(pictures, sizes, saved)
         return plan.pictures(), (plan.saved_pictures() if saved else None)
 
-    def _run(self, pictures, sizes, batch):
-        """batch(pictures, sizes) -> one result per picture, called once per `batch_size` pictures with the model in eval mode."""
+    def _run(self, pictures, sizes, batch, step=None):
+        """batch(pictures, sizes) -> one result per picture, called once per `step` (default `batch_size`) pictures in eval mode."""
         if sizes is None:
             sizes = [(p.shape[1], p.shape[0]) for p in pictures]
         assert len(sizes) == len(pictures)
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            outs = []
-            for i in range(0, len(pictures), self.batch_size):
-                outs.append(batch(pictures[i:i + self.batch_size], sizes[i:i + self.batch_size]))
-        finally:
-            self.model.train(was_training)
-        return outs
+        step = step or self.batch_size
+        with _eval_mode(self.model):
+            return [batch(pictures[i:i + step], sizes[i:i + step]) for i in range(0, len(pictures), step)]
 
     def run(self, pictures, sizes=None):
         """pictures: list of RGB uint8 arrays [H][W][3] of any sizes -> one array per picture at its own size, or at sizes[i] =
@@ -711,19 +728,14 @@ class PainterEngine:
         if self.task != "coco_pano_inst":
             raise ValueError("painter_engine: run_instances decodes the pictures of coco_pano_inst, not of %r" % self.task)
         kw.pop("device", None)
-        args = dict(palette=None, dist_thr=19.0, nms_pre=2000, max_num=100, kernel="gaussian", sigma=2.0)
-        unknown = set(kw) - set(args)
-        if unknown:
-            raise TypeError("run_instances: unexpected arguments %s" % sorted(unknown))
-        args.update(kw)
+        _check_arguments("run_instances", kw, INSTANCE_DEFAULTS)          # before the first forward is enqueued
+        args = dict(INSTANCE_DEFAULTS, **kw)
 
         def batch(pics, sizes):
             plan = self._launch_batch(pics, sizes, False)
-            jobs = [InstanceDecode(plan.out[off:off + int(np.prod(shape))].view(shape), args["palette"], args["dist_thr"], args["nms_pre"],
-                                   args["max_num"], args["kernel"], args["sigma"]) for off, shape in plan.views]
+            jobs = [InstanceDecode(plan.picture(i), *args.values()) for i in range(plan.n_jobs)]
             return [j.result() for j in jobs]
         return [o for b in self._run(pictures, sizes, batch) for o in b]
-
 
     def run_pose(self, pictures, flipped=None, sizes=None, **kw):
         """coco_pose: forward and decode as `run` (nearest), then `keypoints` of every batch straight from the decode plan's
@@ -737,11 +749,8 @@ class PainterEngine:
         if self.task != "coco_pose":
             raise ValueError("painter_engine: run_pose decodes the pictures of coco_pose, not of %r" % self.task)
         kw.pop("device", None)
-        args = dict(palette=None, flip_pairs=COCO_FLIP_PAIRS, shift_heatmap=True)
-        unknown = set(kw) - set(args)
-        if unknown:
-            raise TypeError("run_pose: unexpected arguments %s" % sorted(unknown))
-        args.update(kw)
+        _check_arguments("run_pose", kw, POSE_DEFAULTS)                   # before the first forward is enqueued
+        args = dict(POSE_DEFAULTS, **kw)
         pictures = list(pictures)
         sizes = [(192, 256)] * len(pictures) if sizes is None else [(int(w), int(h)) for w, h in sizes]
         assert len(sizes) == len(pictures)
@@ -753,33 +762,22 @@ class PainterEngine:
         elif flipped is not None:
             flipped = list(flipped)
             assert len(flipped) == len(pictures), "painter_engine: one flipped query per picture"
-        if not pictures:
-            return []
-        pixels = sizes[0][0] * sizes[0][1] * 3
-        shape = (sizes[0][1], sizes[0][0], 3)
         step = self.batch_size if flipped is None else max(1, self.batch_size // 2)          # boxes per batch: twins share the forward
 
         def painted(plans, first, count):
             """Pictures first .. first + count of the batch's decode plans as one uint8 tensor [count][H][W][3] (a view when one plan
             holds them all)."""
-            flat = plans[0].out if len(plans) == 1 else torch.cat([p.out for p in plans])
-            return flat[first * pixels:(first + count) * pixels].view((count,) + shape)
+            if len(plans) == 1:
+                return plans[0].run_of(first, count)
+            return torch.cat([p.run_of(0, p.n_jobs) for p in plans])[first:first + count]
 
-        def batch(pics, twins):
-            m, both = len(pics), pics + (twins or [])
+        def batch(boxes, sizes):
+            m, both = len(boxes), [b[0] for b in boxes] + ([b[1] for b in boxes] if flipped else [])
             plans = [self._launch_batch(both[j:j + self.batch_size], sizes[:1] * len(both[j:j + self.batch_size]), False)
                      for j in range(0, len(both), self.batch_size)]
-            res = PoseDecode(painted(plans, 0, m), painted(plans, m, m) if twins else None, args["palette"], args["flip_pairs"],
-                             args["shift_heatmap"]).result()
+            res = PoseDecode(painted(plans, 0, m), painted(plans, m, m) if flipped else None, *args.values()).result()
             return [dict(preds=res["preds"][i], maxvals=res["maxvals"][i]) for i in range(m)]
-
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            return [o for i in range(0, len(pictures), step)
-                    for o in batch(pictures[i:i + step], None if flipped is None else flipped[i:i + step])]
-        finally:
-            self.model.train(was_training)
+        return [o for b in self._run(list(zip(pictures, flipped or pictures)), sizes, batch, step) for o in b]
 
 
 @torch.no_grad()
@@ -787,7 +785,7 @@ def run_one_image(img, tgt, size, model, out_path, device, task):
     """The scripts' `run_one_image(img, tgt, size, model, out_path, device)` plus the task name: img, tgt = the normalised float
     arrays [2*res][res][3] the script built, size = (width, height).  Decodes on the device and writes the file the script writes
     (u8 / depth tasks); the three restoration tasks return the float64 array [H][W][3] as theirs do."""
-    device = _require_cuda(device)
+    device = _device((), device)
     spec = _task(task)
     m = _unwrap(model)
     x = torch.as_tensor(np.asarray(img)).unsqueeze(0).permute(0, 3, 1, 2).float().to(device).contiguous()

@@ -193,6 +193,51 @@ def test_arguments_are_refused_before_anything_is_enqueued():
     assert E._host_array(torch.tensor([0.25, 0.5]), np.float32).tolist() == [0.25, 0.5] and E._host_array([3, 4], np.int32).dtype == np.int32
 
 
+def test_run_instances_and_run_pose_refuse_arguments_before_anything_is_enqueued():
+    """The same stand-ins for the two other engine routes: an unknown keyword and an unsupported NMS kernel never reach a forward."""
+    import types
+    from painter_amd import painter_engine as E
+
+    def never(*a, **k):
+        raise AssertionError("a forward was enqueued")
+    pictures = [np.zeros((4, 4, 3), np.uint8)]
+    inst = types.SimpleNamespace(task="coco_pano_inst", _run=never, _launch_batch=never, batch_size=2, model=None)
+    pose = types.SimpleNamespace(task="coco_pose", _run=never, _launch_batch=never, batch_size=2, model=None)
+    with pytest.raises(TypeError, match="nms_iou"):
+        E.PainterEngine.run_instances(inst, pictures, nms_iou=0.5)
+    with pytest.raises(TypeError, match="dist_thr"):
+        E.PainterEngine.run_pose(pose, pictures, None, dist_thr=3.0)
+    with pytest.raises(NotImplementedError, match="cubic"):
+        E.PainterEngine.run_instances(inst, pictures, kernel="cubic")
+
+
+def test_out_bytes_is_the_closed_formula_and_signatures_repeat_the_default_tables():
+    """The section list of PanopticDecode gives the byte count its buffer has always had.  The keyword defaults are written once, in the
+    tables; every public signature that repeats one for its readers agrees with them."""
+    import inspect
+    from painter_amd import painter_engine as E
+    for h, w, k, n_things, max_inst in ((480, 640, 133, 80, 100), (61, 83, 133, 80, 100), (4, 4, 2, 2, 1)):
+        assert E.PanopticDecode.out_bytes(h, w, k, n_things, max_inst) == \
+            16 + E.SEGMENT.itemsize * (max_inst + k - n_things) + 4 * max_inst + 7 * h * w
+    assert E.SEGMENT.itemsize == 24
+
+    def defaults(fn, rename={}):
+        return {rename.get(k, k): v.default for k, v in inspect.signature(fn).parameters.items() if v.default is not inspect.Parameter.empty}
+    for fn, table, rename in ((E.instances, E.INSTANCE_DEFAULTS, {}), (E.panoptic, E.MERGE_DEFAULTS, {}),
+                              (E.PanopticDecode.__init__, E.MERGE_DEFAULTS, {"palette": "semseg_palette"}),
+                              (E.classify_instances, dict(E.MERGE_DEFAULTS), {"palette": "semseg_palette"}),
+                              (E.keypoints, E.POSE_DEFAULTS, {}), (E.pose_heatmaps, E.POSE_DEFAULTS, {}), (E.PoseDecode.__init__, E.POSE_DEFAULTS, {})):
+        have = defaults(fn, rename)
+        shared = set(have) & set(table)
+        assert shared and all(have[k] == table[k] for k in shared), (fn.__qualname__, have)
+    assert set(E.INSTANCE_DEFAULTS) <= set(defaults(E.instances)) and set(E.MERGE_DEFAULTS) <= set(defaults(E.panoptic))
+    assert set(E.POSE_DEFAULTS) <= set(defaults(E.keypoints))
+    # the tables are passed on by position: their order is the constructors'
+    assert list(inspect.signature(E.InstanceDecode.__init__).parameters)[2:8] == \
+        ["palette", "thresholds", "nms_pre", "max_num", "kernel", "sigma"] and list(E.INSTANCE_DEFAULTS)[1] == "dist_thr"
+    assert list(inspect.signature(E.PoseDecode.__init__).parameters)[3:6] == list(E.POSE_DEFAULTS)
+
+
 # ---- with a reference checkout: the live reference
 def _reference():
     from oracle import ref_import
