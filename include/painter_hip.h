@@ -588,6 +588,46 @@ int pa_pose_keypoints(const void* pictures, const void* flipped, const void* pal
 int pa_pose_heatmaps(const void* pictures, const void* flipped, const void* palette_i32, const void* pair_i32, int n, int h, int w,
                      int n_keypoints, int shift, float* out_heatmaps, hipStream_t stream);
 
+/* Scoring of painted pictures against ground-truth maps, csrc/painter_score.hip: only the sums leave the device;
+ * tests/painter_score_host.py is the definition.  Both entry points take a DEVICE job table, one record per picture, pictures of any
+ * sizes in one launch; null pointers, n_jobs outside 1 .. 65535 or the ranges named below return hipErrorInvalidValue before anything is
+ * launched. */
+typedef struct pa_score_job {
+    const void* picture;        /* uint8 [h][w][3], the painted picture */
+    const void* gt;             /* uint8 [h][w], the ground-truth labels */
+    int32_t h, w;               /* a job with h < 1 or w < 1 adds nothing */
+} pa_score_job;
+/* SemSegEvaluatorCustom.process (ade20k_semantic/ADE20kSemSegEvaluatorCustom.py:75-112, coco_panoptic/COCOPanoSemSegEvaluatorCustom.py:
+ * 67-106) without its boundary branch: for every pixel of every job conf[(n_colours + 1) * pred + gt'] += 1, pred = the class
+ * pa_palette_argmin gives the pixel (the same float32 operations, first minimum; palette: DEVICE float32 [n_colours][3]; dist_type: its
+ * codes), gt' = n_colours where gt == ignore_label, else gt.  A pixel whose gt >= n_colours is not the ignore label (the reference's
+ * reshape fails on it) adds 1 to invalid[0] and to no bin.  conf_i64: int64 [(n_colours + 1)^2], invalid_i64: int64 [1], both 8-byte
+ * aligned and ACCUMULATED in place: one buffer serves a data set.  total_pixels: the sum of h * w over the table, 1 .. 2^31 (it sizes the
+ * grid; a workgroup counts into 32-bit bins in LDS, which a launch of at most 2^31 pixels cannot wrap).  1 <= n_colours <= 255 (gt is a
+ * byte).  bins: 0 = the workgroups' private bins are in LDS whenever pa_semseg_lds_bins(n_colours) (n_colours <= 199: 12 n_colours
+ * rounded up to 16, plus 4 (n_colours + 1)^2 bytes within 160 KB), else every run of equal neighbours adds to conf_i64 directly; 1 = the
+ * direct form at any n_colours (measurements).  Integer atomics only: the result does not depend on their order. */
+int pa_semseg_lds_bins(int n_colours);
+int pa_semseg_confusion(const pa_score_job* jobs, int n_jobs, int64_t total_pixels, const float* palette, int n_colours, int dist_type,
+                        int ignore_label, int bins, void* conf_i64, void* invalid_i64, hipStream_t stream);
+typedef struct pa_depth_job {
+    const void* pred;           /* int32 [h][w], what pa_painter_decode_depth writes */
+    const void* gt;             /* uint16 [h][w], the ground-truth depth PNG's values */
+    int32_t h, w;
+    int32_t y0, y1, x0, x1;     /* the evaluated box, rows y0 .. y1 - 1 and columns x0 .. x1 - 1, clipped to the picture */
+} pa_depth_job;
+/* nyuv2_depth/eval_with_pngs.py:148-209 (eval, dataset nyu) and :50-71 (compute_errors) up to the sums.  Per pixel of the box, the
+ * float32 steps in float32: p = float(pred) / divisor clamped to [min_depth, max_depth] (:100, :177-178), g = float(gt) / divisor (:136);
+ * the pixel counts when min_depth < g < max_depth (:184); t = max(g / p, p / g) (:51).  out_f64: double [n_jobs][10] = n, the counts of
+ * t < 1.25, t < 1.5625, t < 1.953125, then the float64 sums over float64 terms of (g - p)^2, (ln g - ln p)^2, |g - p| / g, (g - p)^2 / g,
+ * ln p - ln g and |log10 p - log10 g|, from which the nine numbers of :71 follow.  The eigen crop of :205 is the box 45, 471, 41, 601; the
+ * KITTI branches are not here.  divisor > 0 (1000 for NYU), 0 < min_depth < max_depth < inf.  workspace: pa_depth_workspace_bytes(n_jobs),
+ * 8-byte aligned, as out_f64.  Two launches, no floating-point atomics: a workgroup's partial is summed in a fixed order and a job's
+ * partials are added in index order, so two runs give the same bits. */
+int64_t pa_depth_workspace_bytes(int n_jobs);     /* host only; -1 for bad arguments */
+int pa_depth_errors(const pa_depth_job* jobs, int n_jobs, float divisor, float min_depth, float max_depth, void* out_f64, void* workspace,
+                    hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,9 +25,11 @@ FLAGS = FLAGS + os.environ.get("PA_EXTRA_FLAGS", "").split()
 # multiply-add there except the explicit fma() calls of painter_io.hip's bilinear resize.  painter_inst.hip: its float64 NMS arithmetic
 # is stated operation by operation (tests/painter_inst_host.py).  painter_pano.hip: one float64 division feeds a comparison the
 # reference makes in Python floats (tests/painter_pano_host.py).  painter_pose.hip: the float32 add and halving of two heat values decide
-# the reference's argmax (tests/painter_pose_host.py).
+# the reference's argmax (tests/painter_pose_host.py).  painter_score.hip: the float32 divisions, clamp and ratio of the depth evaluation
+# decide its threshold counts, and a pixel's class is the float32 arg-min of painter_io.hip (tests/painter_score_host.py).
 EXTRA = {"seggpt_io.hip": ["-ffp-contract=off"], "pair_io.hip": ["-ffp-contract=off"], "painter_io.hip": ["-ffp-contract=off"],
-         "painter_inst.hip": ["-ffp-contract=off"], "painter_pano.hip": ["-ffp-contract=off"], "painter_pose.hip": ["-ffp-contract=off"]}
+         "painter_inst.hip": ["-ffp-contract=off"], "painter_pano.hip": ["-ffp-contract=off"], "painter_pose.hip": ["-ffp-contract=off"],
+         "painter_score.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

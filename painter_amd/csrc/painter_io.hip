@@ -27,6 +27,7 @@
 #include "../../include/painter_hip.h"
 #include "common.h"
 #include "image_io.h"
+#include "painter_post.h"
 
 #pragma clang fp contract(off)
 
@@ -165,14 +166,8 @@ __global__ __launch_bounds__(256) void painter_decode_kernel(const float* __rest
     }
 }
 
-// One pixel per lane, the palette staged in LDS once per workgroup (every lane reads the same colour: a broadcast, no bank
-// conflict).  DIST: 0 abs, 1 square, 2 (abs + square) / 2 per channel, summed over the channels in float32; strict < keeps the first
-// minimum.
-template <int DIST> DEVI float channel_dist(float d) {
-    if constexpr (DIST == 0) return fabsf(d);
-    else if constexpr (DIST == 1) return d * d;
-    else return (fabsf(d) + d * d) / 2.f;
-}
+// One pixel per lane, the palette staged in LDS once per workgroup; the distance and the first minimum are nearest_colour of
+// painter_post.h, which pa_semseg_confusion (painter_score.hip) shares.
 template <int DIST>
 __global__ __launch_bounds__(256) void palette_argmin_kernel(const uint8_t* __restrict__ image, const float* __restrict__ palette,
                                                              int32_t* __restrict__ out, int64_t n_pixels, int K) {
@@ -181,18 +176,7 @@ __global__ __launch_bounds__(256) void palette_argmin_kernel(const uint8_t* __re
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_pixels) return;
-    const float p0 = (float)image[i * 3], p1 = (float)image[i * 3 + 1], p2 = (float)image[i * 3 + 2];
-    float best = 0.f;
-    int arg = 0;
-    for (int k = 0; k < K; ++k) {
-        float e = channel_dist<DIST>(p0 - pal_lds[3 * k]) + channel_dist<DIST>(p1 - pal_lds[3 * k + 1]);
-        e = e + channel_dist<DIST>(p2 - pal_lds[3 * k + 2]);
-        if (k == 0 || e < best) {
-            best = e;
-            arg = k;
-        }
-    }
-    out[i] = arg;
+    out[i] = nearest_colour<DIST>((float)image[i * 3], (float)image[i * 3 + 1], (float)image[i * 3 + 2], pal_lds, K);
 }
 
 bool decode_args_ok(int n_jobs, int n_samples, int max_h, int max_w, int res_h, int res_w, int patch) {

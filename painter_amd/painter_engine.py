@@ -27,15 +27,24 @@ behind the instance decode on the device, one copy back (tests/painter_pano_host
 TopDownCustom.forward_pseudo_test with its flip test (mmpose_custom/model/top_down.py:163-258) and mmpose's heat-map peak rule, straight
 from the bytes of the two pictures -- no heat map in memory, 51 floats per box back (tests/painter_pose_host.py is the definition).
 
+`SemsegScore`, `depth_errors`, `PainterEngine.run_semseg_score` and `run_depth_errors` score painted pictures against ground-truth maps
+(csrc/painter_score.hip): the confusion matrix of SemSegEvaluatorCustom.process (ADE20kSemSegEvaluatorCustom.py:75-112,
+COCOPanoSemSegEvaluatorCustom.py:67-106) accumulated on the device over a whole data set -- one launch per batch, nothing copied back
+until `matrix()` -- and per picture the ten sums behind the nine numbers of nyuv2_depth/eval_with_pngs.py:50-71, 148-217
+(tests/painter_score_host.py is the definition).
+
 Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
 (`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
 `cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
-canvases the script built, or pass an already resized 448 x 448 uint8 query to `run`); PSNR / SSIM; the detectron2
-evaluators apart from the colour -> class decode (`class_map`), the instance decode (`instances`) and the panoptic merge (`panoptic`);
+canvases the script built, or pass an already resized 448 x 448 uint8 query to `run`); PSNR / SSIM; of the detectron2
+evaluators what is left after the colour -> class decode (`class_map`), the confusion count (`SemsegScore`), the instance decode
+(`instances`) and the panoptic merge (`panoptic`): the boundary-IoU branch (`_compute_boundary_iou`, cv2 erosion), `encode_json_sem_seg`
+and its RLE, the final ratios of `evaluate` (`SemsegScore.scores` restates them on the host); of the depth evaluation its KITTI branches
+(`do_kb_crop`, `garg_crop`) and the division of the sums;
 PQ computation and PNG encoding; of the pose route mmpose's OKS NMS, rescoring and COCOeval, and the 34 numbers per box of `to_image`.
 
 One host path serves the routes: `_device` / `_pictures` put the inputs of a call on one indexed CUDA device; INSTANCE_DEFAULTS,
-MERGE_DEFAULTS and POSE_DEFAULTS hold the keyword defaults and `_check_arguments` refuses the rest before a forward is enqueued; an output
+MERGE_DEFAULTS, POSE_DEFAULTS and DEPTH_DEFAULTS hold the keyword defaults and `_check_arguments` refuses the rest before a forward is enqueued; an output
 buffer is one list of sections (`_layout`): its size, the pointers handed to the library and the slices of `result()` all come from it.
 
 There is no CPU fallback: a CPU device or a missing libpainter_hip.so raises.
@@ -108,6 +117,26 @@ def _pictures(x, device, batch=False):
         raise RuntimeError("painter_engine: the pictures are on %s, expected %s" % (x.device, device))
     assert x.dtype == torch.uint8 and x.dim() == 3 + batch and x.shape[-1] == 3, (x.dtype, tuple(x.shape))
     return x.contiguous()
+
+
+def _maps(x, device, dtype):
+    """A one-channel map [H][W] (numpy or CUDA tensor) of `dtype` (a torch dtype; uint16 may also arrive as its int16 bits) -> contiguous
+    CUDA tensor on `device` (what `_device` returned)."""
+    if not torch.is_tensor(x):
+        x = np.ascontiguousarray(x)
+        x = torch.from_numpy(x.view(np.int16) if x.dtype == np.uint16 else x).to(device)
+    if x.device != device:
+        raise RuntimeError("painter_engine: the maps are on %s, expected %s" % (x.device, device))
+    ok = (torch.uint16, torch.int16) if dtype == torch.uint16 else (dtype,)
+    assert x.dtype in ok and x.dim() == 2, (x.dtype, tuple(x.shape))
+    return x.contiguous()
+
+
+def _job_table(jobs, device):
+    """A ctypes array of job records -> (its pinned host copy, the table on the device).  Pinned + asynchronous: the copy is ordered on the
+    stream and the host does not wait for work enqueued earlier."""
+    host = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).pin_memory()
+    return host, host.to(device, non_blocking=True)
 
 
 def _rgb_palette(palette, default):
@@ -189,9 +218,7 @@ class DecodePlan:
             jobs[i].out2 = None if self.out8 is None else self.out8.data_ptr() + off
             jobs[i].sample = i if samples is None else int(samples[i])
             jobs[i].out_h, jobs[i].out_w = shape[0], shape[1]
-        # pinned + asynchronous: the copy is ordered on the stream and the host does not wait for work enqueued earlier
-        self._table_host = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).pin_memory()
-        self.table = self._table_host.to(device, non_blocking=True)
+        self._table_host, self.table = _job_table(jobs, device)
         self.n_jobs = n
         self.max_h, self.max_w = max(v[1][0] for v in self.views), max(v[1][1] for v in self.views)
 
@@ -438,6 +465,190 @@ def to_image(preds, center, scale, heatmap_size):
     out[:, 0] = preds[:, 0] * (full[0] / heatmap_size[0]) + center[0] - full[0] * 0.5
     out[:, 1] = preds[:, 1] * (full[1] / heatmap_size[1]) + center[1] - full[1] * 0.5
     return out
+
+
+# ---- scoring against ground truth (csrc/painter_score.hip)
+DEPTH_DEFAULTS = dict(min_depth=1e-3, max_depth=80.0, crop=None, divisor=1000.0)      # eval_with_pngs.py:43-44, no crop, :100 / :136 (nyu)
+EIGEN_CROP = (45, 471, 41, 601)                                                        # eval_with_pngs.py:205, of 480 x 640 pictures
+
+
+class ScoreJob(ctypes.Structure):
+    """pa_score_job of include/painter_hip.h."""
+    _fields_ = [("picture", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
+class DepthJob(ctypes.Structure):
+    """pa_depth_job of include/painter_hip.h."""
+    _fields_ = [("pred", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("y0", ctypes.c_int32),
+                ("y1", ctypes.c_int32), ("x0", ctypes.c_int32), ("x1", ctypes.c_int32)]
+
+
+def _same_sizes(who, pictures, gts):
+    if len(pictures) != len(gts):
+        raise ValueError("%s: %d pictures, %d ground-truth maps" % (who, len(pictures), len(gts)))
+    for i, (p, g) in enumerate(zip(pictures, gts)):
+        if tuple(p.shape[:2]) != tuple(g.shape):
+            raise ValueError("%s: picture %d is %s, its ground truth %s" % (who, i, tuple(p.shape[:2]), tuple(g.shape)))
+
+
+def semseg_scores(matrix):
+    """detectron2's SemSegEvaluator.evaluate (detectron2/evaluation/sem_seg_evaluation.py) from the confusion matrix int64
+    [K + 1][K + 1] (rows = predictions, columns = ground truth, the last column = ignored pixels), in float64: -> dict(mIoU, fwIoU, mACC,
+    pACC in percent, IoU and ACC float64 [K] in percent, NaN for a class without ground-truth pixels).  A class that the ground truth does
+    not show is left out of every mean (the release with the boundary-IoU branch, which the reference's evaluators are written against);
+    the ignore column and the (empty) ignore row enter nothing.
+    Restated from detectron2's published source; detectron2 is not available where this project is tested, so the formulas are
+    unverified against detectron2."""
+    conf = np.asarray(matrix)
+    assert conf.ndim == 2 and conf.shape[0] == conf.shape[1] and conf.shape[0] >= 2, conf.shape
+    k = conf.shape[0] - 1
+    tp = conf.diagonal()[:-1].astype(np.float64)
+    pos_gt = conf[:-1, :-1].sum(axis=0).astype(np.float64)
+    pos_pred = conf[:-1, :-1].sum(axis=1).astype(np.float64)
+    class_weight = pos_gt / pos_gt.sum() if pos_gt.sum() else np.zeros(k)
+    acc_valid = pos_gt > 0
+    acc = np.full(k, np.nan)
+    acc[acc_valid] = tp[acc_valid] / pos_gt[acc_valid]
+    union = pos_gt + pos_pred - tp
+    iou_valid = acc_valid & (union > 0)
+    iou = np.full(k, np.nan)
+    iou[iou_valid] = tp[iou_valid] / union[iou_valid]
+    macc = acc[acc_valid].sum() / acc_valid.sum() if acc_valid.any() else np.nan
+    miou = iou[iou_valid].sum() / iou_valid.sum() if iou_valid.any() else np.nan
+    fiou = (iou[iou_valid] * class_weight[iou_valid]).sum()
+    pacc = tp.sum() / pos_gt.sum() if pos_gt.sum() else np.nan
+    return dict(mIoU=100 * miou, fwIoU=100 * fiou, mACC=100 * macc, pACC=100 * pacc, IoU=100 * iou, ACC=100 * acc)
+
+
+class SemsegScore:
+    """The confusion matrix of a data set of painted semantic pictures, kept on the device (pa_semseg_confusion):
+    SemSegEvaluatorCustom.process (ADE20kSemSegEvaluatorCustom.py:75-112, COCOPanoSemSegEvaluatorCustom.py:67-106) without the distance
+    tensor, the copy of the class map and np.bincount.  palette: [K][3] integer colours, K <= 255; a class is `class_map`'s."""
+
+    def __init__(self, palette, dist_type="abs", ignore_label=255, device="cuda"):
+        self.device = _device((), device)
+        _check_arguments("SemsegScore", dict(dist_type=dist_type), MERGE_DEFAULTS)
+        pal = _rgb_palette(palette, None)
+        self.k, self.dist_type, self.ignore_label = int(pal.shape[0]), dist_type, int(ignore_label)
+        self.bins = 0                                        # pa_semseg_confusion's `bins`: 1 forces the direct form (tools/painter_score_bench.py)
+        self.palette = torch.from_numpy(pal).to(self.device)
+        self.at, size = _layout([("conf", np.int64, (self.k + 1) ** 2, 8), ("invalid", np.int64, 1, 8)])
+        self.out = torch.zeros(size, dtype=torch.uint8, device=self.device)
+        self._last = None
+
+    def reset(self):
+        self.out.zero_()
+
+    def add(self, pictures, gts):
+        """pictures: painted pictures uint8 [H][W][3] of any sizes, gts: their label maps uint8 [H][W] (lists of numpy arrays or CUDA
+        tensors).  ONE launch for the list, nothing is copied back."""
+        pictures, gts = list(pictures), list(gts)
+        if _device([pictures, gts], self.device) != self.device:
+            raise RuntimeError("painter_engine: this SemsegScore lives on %s" % self.device)
+        _same_sizes("SemsegScore.add", pictures, gts)
+        if not pictures:
+            return self
+        pics = [_pictures(p, self.device) for p in pictures]
+        maps = [_maps(g, self.device, torch.uint8) for g in gts]
+        jobs = (ScoreJob * len(pics))()
+        for job, p, g in zip(jobs, pics, maps):
+            job.picture, job.gt, job.h, job.w = p.data_ptr(), g.data_ptr(), int(p.shape[0]), int(p.shape[1])
+        total = sum(int(p.shape[0]) * int(p.shape[1]) for p in pics)
+        host, table = _job_table(jobs, self.device)
+        ptr = lambda name: self.out.data_ptr() + self.at[name][0]
+        check(lib.pa_semseg_confusion(table.data_ptr(), len(pics), total, self.palette.data_ptr(), self.k, DIST_TYPES[self.dist_type],
+                                      self.ignore_label, self.bins, ptr("conf"), ptr("invalid"), _stream()),
+              "pa_semseg_confusion (%d jobs, %d pixels, %d colours)" % (len(pics), total, self.k))
+        self._last = (pics, maps, host, table)               # what the enqueued launch reads, until the next one
+        return self
+
+    def matrix(self):
+        """The one copy back (and synchronisation) -> int64 numpy [K + 1][K + 1], rows = predicted class, columns = ground truth with
+        the ignored pixels in column K.  ValueError if a ground-truth value in [K, 255] other than the ignore label was met."""
+        a = self.out.cpu().numpy()
+        invalid = int(_section(a, self.at, "invalid")[0])
+        if invalid > 0:
+            raise ValueError("SemsegScore: %d ground-truth pixels hold a label >= %d that is not the ignore label %d"
+                             % (invalid, self.k, self.ignore_label))
+        return _section(a, self.at, "conf").reshape(self.k + 1, self.k + 1).copy()
+
+    def scores(self):
+        """`semseg_scores(self.matrix())`: mIoU, fwIoU, mACC, pACC, IoU and ACC per class, on the host in float64 -- detectron2's
+        formulas restated, unverified against detectron2."""
+        return semseg_scores(self.matrix())
+
+
+def _crop_box(crop, h, w):
+    if crop is None:
+        return (0, h, 0, w)
+    if isinstance(crop, str):
+        if crop != "eigen":
+            raise ValueError("painter_engine: crop is None, \"eigen\" or (y0, y1, x0, x1), not %r" % crop)
+        if (h, w) != (480, 640):
+            raise ValueError("painter_engine: the eigen crop %s belongs to 480 x 640 pictures, not %d x %d" % (EIGEN_CROP, h, w))
+        return EIGEN_CROP
+    y0, y1, x0, x1 = (int(v) for v in crop)
+    if not (0 <= y0 <= y1 <= h and 0 <= x0 <= x1 <= w):
+        raise ValueError("painter_engine: the crop box %s leaves the %d x %d picture" % ((y0, y1, x0, x1), h, w))
+    return (y0, y1, x0, x1)
+
+
+class DepthErrors:
+    """One launched pa_depth_errors over a list of (prediction, ground truth) device maps: `result()` is one copy back of ten doubles
+    per picture and one synchronisation."""
+
+    def __init__(self, preds, gts, min_depth=1e-3, max_depth=80.0, crop=None, divisor=1000.0):
+        _same_sizes("depth_errors", preds, gts)
+        self.n = len(preds)
+        if not self.n:
+            return
+        dev = preds[0].device
+        self.keep = (preds, gts)
+        jobs = (DepthJob * self.n)()
+        for job, p, g in zip(jobs, preds, gts):
+            h, w = int(p.shape[0]), int(p.shape[1])
+            job.pred, job.gt, job.h, job.w = p.data_ptr(), g.data_ptr(), h, w
+            job.y0, job.y1, job.x0, job.x1 = _crop_box(crop, h, w)
+        self._table_host, self.table = _job_table(jobs, dev)
+        self.workspace = torch.empty(max(lib.pa_depth_workspace_bytes(self.n), 8), dtype=torch.uint8, device=dev)
+        self.out = torch.empty((self.n, 10), dtype=torch.float64, device=dev)
+        check(lib.pa_depth_errors(self.table.data_ptr(), self.n, float(divisor), float(min_depth), float(max_depth), self.out.data_ptr(),
+                                  self.workspace.data_ptr(), _stream()),
+              "pa_depth_errors (%d jobs, divisor %r, depths %r .. %r)" % (self.n, divisor, min_depth, max_depth))
+
+    def sums(self):
+        """The copy back -> float64 [n][10]: n, the three threshold counts, the six sums (include/painter_hip.h)."""
+        return self.out.cpu().numpy() if self.n else np.zeros((0, 10))
+
+    def result(self):
+        return depth_metrics(self.sums())
+
+
+def depth_metrics(sums):
+    """float64 [n][10] of pa_depth_errors -> (float64 [n][9] in the order of compute_errors (eval_with_pngs.py:71): silog, log10,
+    abs_rel, sq_rel, rmse, rmse_log, d1, d2, d3; int64 [n] valid pixels).  A picture without a valid pixel gives nine NaN, as the
+    reference's mean of nothing does."""
+    s = np.asarray(sums, dtype=np.float64).reshape(-1, 10)
+    n = s[:, 0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = s[:, 1:] / n[:, None]
+        d1, d2, d3, sq, lg2, abs_rel, sq_rel, err, l10 = mean.T
+        silog = np.sqrt(lg2 - err ** 2) * 100
+        out = np.stack([silog, l10, abs_rel, sq_rel, np.sqrt(sq), np.sqrt(lg2), d1, d2, d3], -1)
+    return out, n.astype(np.int64)
+
+
+def depth_errors(preds, gts, min_depth=1e-3, max_depth=80.0, crop=None, divisor=1000.0, device="cuda"):
+    """nyuv2_depth/eval_with_pngs.py:148-217 (`eval`, dataset nyu) with compute_errors (:50-71) for a list of pictures in two launches.
+    preds: int32 [H][W] depth pictures as `PainterEngine.run` returns them for `nyuv2_depth`; gts: uint16 [H][W], the values of the
+    ground-truth PNG (numpy arrays or CUDA tensors, any sizes).  crop: None, "eigen" (the box 45:471, 41:601 of :205, 480 x 640 pictures
+    only) or (y0, y1, x0, x1), half-open.  The float32 steps of the reference are float32, so n and d1 .. d3 are its own; the other six
+    numbers come from float64 sums where the reference sums in float32.
+    -> (float64 [n][9]: silog, log10, abs_rel, sq_rel, rmse, rmse_log, d1, d2, d3; int64 [n]: valid pixels); nine NaN where n = 0."""
+    preds, gts = list(preds), list(gts)
+    device = _device([preds, gts], device)
+    return DepthErrors([_maps(p, device, torch.int32) for p in preds], [_maps(g, device, torch.uint16) for g in gts],
+                       min_depth, max_depth, crop, divisor).result()
 
 
 # ---- panoptic merge (csrc/painter_pano.hip)
@@ -778,6 +989,47 @@ class PainterEngine:
             res = PoseDecode(painted(plans, 0, m), painted(plans, m, m) if flipped else None, *args.values()).result()
             return [dict(preds=res["preds"][i], maxvals=res["maxvals"][i]) for i in range(m)]
         return [o for b in self._run(list(zip(pictures, flipped or pictures)), sizes, batch, step) for o in b]
+
+    def run_semseg_score(self, pictures, gts, score, sizes=None):
+        """ade20k_semseg / coco_pano_semseg: forward and decode as `run`, then `score.add` (a SemsegScore) of every batch straight from
+        the decode plan's device-resident uint8 output -- the painted pictures are never copied back, and nothing else is before
+        `score.matrix()`.  gts: one uint8 label map per picture, of the painted picture's size (sizes[i], default the query's own).
+        -> score."""
+        if self.task not in ("ade20k_semseg", "coco_pano_semseg"):
+            raise ValueError("painter_engine: run_semseg_score scores the pictures of ade20k_semseg / coco_pano_semseg, not of %r" % self.task)
+        pictures, gts = list(pictures), list(gts)
+        sizes = [(p.shape[1], p.shape[0]) for p in pictures] if sizes is None else [(int(w), int(h)) for w, h in sizes]
+        _same_sizes("run_semseg_score", [np.empty((h, w, 0)) for w, h in sizes], gts)          # before the first forward is enqueued
+        assert len(sizes) == len(pictures)
+
+        def batch(pairs, sizes):
+            plan = self._launch_batch([p for p, _ in pairs], sizes, False)
+            score.add([plan.picture(i) for i in range(plan.n_jobs)], [g for _, g in pairs])
+        self._run(list(zip(pictures, gts)), sizes, batch)
+        return score
+
+    def run_depth_errors(self, pictures, gts, sizes=None, **kw):
+        """nyuv2_depth: forward and decode as `run`, then `depth_errors(picture, gt, **kw)` of every batch straight from the decode plan's
+        device-resident int32 output -- no PNG, no copy back of a picture, ten doubles per picture back.  gts: one uint16 map per picture,
+        of the painted picture's size.  kw: min_depth, max_depth, crop, divisor.  -> what `depth_errors` returns, for all pictures."""
+        if self.task != "nyuv2_depth":
+            raise ValueError("painter_engine: run_depth_errors scores the pictures of nyuv2_depth, not of %r" % self.task)
+        kw.pop("device", None)
+        _check_arguments("run_depth_errors", kw, DEPTH_DEFAULTS)          # before the first forward is enqueued
+        args = dict(DEPTH_DEFAULTS, **kw)
+        pictures, gts = list(pictures), list(gts)
+        sizes = [(p.shape[1], p.shape[0]) for p in pictures] if sizes is None else [(int(w), int(h)) for w, h in sizes]
+        _same_sizes("run_depth_errors", [np.empty((h, w, 0)) for w, h in sizes], gts)
+        for w, h in sizes:
+            _crop_box(args["crop"], h, w)
+        assert len(sizes) == len(pictures)
+
+        def batch(pairs, sizes):
+            plan = self._launch_batch([p for p, _ in pairs], sizes, False)
+            maps = [_maps(g, self.device, torch.uint16) for _, g in pairs]
+            return DepthErrors([plan.picture(i) for i in range(plan.n_jobs)], maps, *args.values()).sums()
+        sums = self._run(list(zip(pictures, gts)), sizes, batch)
+        return depth_metrics(np.concatenate(sums) if sums else np.zeros((0, 10)))
 
 
 @torch.no_grad()
