@@ -628,6 +628,42 @@ int64_t pa_depth_workspace_bytes(int n_jobs);     /* host only; -1 for bad argum
 int pa_depth_errors(const pa_depth_job* jobs, int n_jobs, float divisor, float min_depth, float max_depth, void* out_f64, void* workspace,
                     hipStream_t stream);
 
+/* PSNR and SSIM of restored pictures against their ground truth, csrc/painter_restore.hip: what painter_inference_lol.py:166-169 asks of
+ * skimage and what derain's evaluate_PSNR_SSIM.m computes from the saved PNGs, up to the sums; tests/painter_restore_host.py is the
+ * definition.  Pictures of any sizes in one call.  Unlike the tables above this one is a HOST array: the entry point reads it, so that a
+ * picture smaller than the window is refused before anything is enqueued, and copies it into the workspace on the stream (keep it valid
+ * until that copy has run; pinned memory makes the copy asynchronous). */
+#define PA_RESTORE_RGB_F64 0    /* pred: float64 [h][w][3], clipped to [0, 1] in the kernel; gt: uint8 [h][w][3], gt / 255. in float64;
+                                 * the three channels are scored separately */
+#define PA_RESTORE_Y_U8 1       /* pred, gt: uint8 [h][w][3]; one channel, Y = 16 + (65481 R + 128553 G + 24966 B + 127500) / 255000 in
+                                 * integers: the Y row of rgb2ycbcr rounded half up, exact */
+typedef struct pa_restore_job {
+    const void* pred;           /* DEVICE picture, by mode; float64 pictures 8-byte aligned */
+    const void* gt;             /* DEVICE uint8 [h][w][3] */
+    int32_t h, w;               /* both >= win */
+} pa_restore_job;
+/* host only: the side of a workgroup's tile of output windows (24).  A job of mode m has channels(m) * ceil((h - win + 1) / tile) *
+ * ceil((w - win + 1) / tile) tiles; channels = 3 for PA_RESTORE_RGB_F64, 1 for PA_RESTORE_Y_U8. */
+int pa_restore_tile(void);
+/* host only: bytes of pa_restore_scores's workspace for a table of n_jobs jobs with total_tiles tiles in all (16 bytes per tile and the
+ * device copy of the table); -1 for n_jobs outside 1 .. 1024 or total_tiles outside 1 .. 2^24. */
+int64_t pa_restore_workspace_bytes(int n_jobs, int64_t total_tiles);
+/* Per window of `win` x `win` pixels with the separable weights weights_f64[win] (HOST; 1/7 x 7 for skimage's uniform window, the
+ * normalised 11-tap Gaussian of sigma 1.5 for SSIM_index), full windows only: ux, uy, uxx, uyy, uxy = the weighted means of x, y, x x,
+ * y y, x y (x = prediction plane, y = ground-truth plane, rows first, then columns); vx = cov_norm (uxx - ux ux), vy likewise, vxy =
+ * cov_norm (uxy - ux uy); S = (2 ux uy + c1)(2 vxy + c2) / ((ux ux + uy uy + c1)(vx + vy + c2)), float64 throughout, one IEEE division, no
+ * fused multiply-add.  out_f64: double [n_jobs][8] = the element count channels * h * w; the sum of (x - y)^2 over all elements (Y mode:
+ * accumulated as int64, so exact as a double up to 2^53); then per channel the sum of S and the window count (h - win + 1)(w - win + 1);
+ * channels a mode does not have hold zeros.  Ratios and logarithms are the host's (painter_engine.restoration_metrics).
+ * 1 <= win <= 11, finite weights, cov_norm, c1, c2 > 0 and finite, n_jobs 1 .. 1024 (every workgroup walks the table), at most 2^24 tiles
+ * (2^32 work-items in the grid);
+ * otherwise, for a null pointer (in the table too), a misaligned out_f64 / workspace / float64 picture, or a job with h < win or w < win:
+ * hipErrorInvalidValue before anything is enqueued.  workspace: pa_restore_workspace_bytes, 8-byte aligned, as out_f64.  One copy of the
+ * table and two launches; no floating-point atomics: a workgroup's partial is summed in a fixed order and a job's partials are added in
+ * index order, so two runs give the same bits and a picture's numbers do not depend on which other pictures share the call. */
+int pa_restore_scores(const pa_restore_job* jobs, int n_jobs, int mode, int win, const double* weights_f64, double cov_norm, double c1,
+                      double c2, void* out_f64, void* workspace, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,10 +33,17 @@ COCOPanoSemSegEvaluatorCustom.py:67-106) accumulated on the device over a whole 
 until `matrix()` -- and per picture the ten sums behind the nine numbers of nyuv2_depth/eval_with_pngs.py:50-71, 148-217
 (tests/painter_score_host.py is the definition).
 
+`restoration_scores`, `RestorationScores` and `PainterEngine.run_restoration_scores` score restored pictures (csrc/painter_restore.hip):
+PSNR and SSIM as painter_inference_lol.py:166-169 asks them of skimage (metric "skimage") or as derain's evaluate_PSNR_SSIM.m computes
+them from the saved PNGs (metric "matlab_y"), from the decode's device-resident float64 / saved uint8 output -- a float64 window stencil
+over a job table, eight doubles per picture back (tests/painter_restore_host.py is the definition; both metrics are restated from
+published sources and unverified against skimage / MATLAB).
+
 Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
 (`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
 `cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
-canvases the script built, or pass an already resized 448 x 448 uint8 query to `run`); PSNR / SSIM; of the detectron2
+canvases the script built, or pass an already resized 448 x 448 uint8 query to `run`) and its eval_sidd.m (MATLAB's built-in ssim /
+psnr); of the detectron2
 evaluators what is left after the colour -> class decode (`class_map`), the confusion count (`SemsegScore`), the instance decode
 (`instances`) and the panoptic merge (`panoptic`): the boundary-IoU branch (`_compute_boundary_iou`, cv2 erosion), `encode_json_sem_seg`
 and its RLE, the final ratios of `evaluate` (`SemsegScore.scores` restates them on the host); of the depth evaluation its KITTI branches
@@ -246,6 +253,11 @@ class DecodePlan:
         off, shape = self.views[first]
         assert all(v[1] == shape for v in self.views[first:first + count]) and first + count <= self.n_jobs
         return self.out[off:off + count * int(np.prod(shape))].view((count,) + shape)
+
+    def saved_picture(self, i):
+        """f64 tasks planned with `saved`: picture i of the uint8 output as a device view [H][W][3]."""
+        off, shape = self.views[i]
+        return self.out8[off:off + int(np.prod(shape))].view(shape)
 
     def pictures(self):
         """The copy back (and the one synchronisation) -> one numpy array per picture."""
@@ -651,6 +663,135 @@ def depth_errors(preds, gts, min_depth=1e-3, max_depth=80.0, crop=None, divisor=
                        min_depth, max_depth, crop, divisor).result()
 
 
+# ---- restoration scores (csrc/painter_restore.hip)
+RESTORE_METRICS = ("skimage", "matlab_y")
+RESTORE_DEFAULT_METRIC = {"lol": "skimage", "derain": "matlab_y", "sidd": None}      # what each task's own evaluation uses; sidd: see below
+RESTORE_OUT = 8                                                                       # doubles per picture (include/painter_hip.h)
+
+
+class RestoreJob(ctypes.Structure):
+    """pa_restore_job of include/painter_hip.h."""
+    _fields_ = [("pred", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
+def _restore_setup(metric, data_range=2.0):
+    """-> (mode, 1-D window weights float64, cov_norm, C1, C2) of a metric; ValueError for an unknown one.
+    skimage: `structural_similarity`'s defaults -- 7 x 7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance -- with `data_range`;
+    matlab_y: SSIM_index of evaluate_PSNR_SSIM.m -- 11 x 11 Gaussian of sigma 1.5, normalised, L = 255 (`data_range` does not enter)."""
+    if metric == "skimage":
+        r = float(data_range)
+        if not (r > 0 and np.isfinite(r)):
+            raise ValueError("painter_engine: data_range must be positive and finite, not %r" % (data_range,))
+        return 0, np.full(7, 1.0 / 7.0), 49.0 / 48.0, (0.01 * r) ** 2, (0.03 * r) ** 2
+    if metric == "matlab_y":
+        k = np.arange(11, dtype=np.float64) - 5.0
+        g = np.exp(-(k * k) / (2.0 * 1.5 * 1.5))
+        return 1, g / g.sum(), 1.0, (0.01 * 255.0) ** 2, (0.03 * 255.0) ** 2
+    raise ValueError("painter_engine: metric is one of %s, not %r" % (", ".join(RESTORE_METRICS), metric))
+
+
+def _restore_sizes(who, sizes, gts, win):
+    """sizes: (h, w) of every prediction; gts: their ground truths.  ValueError for a count or size mismatch, or a picture below the window."""
+    if len(sizes) != len(gts):
+        raise ValueError("%s: %d pictures, %d ground-truth pictures" % (who, len(sizes), len(gts)))
+    for i, ((h, w), g) in enumerate(zip(sizes, gts)):
+        if tuple(g.shape) != (h, w, 3):
+            raise ValueError("%s: picture %d is %s, its ground truth %s" % (who, i, (h, w, 3), tuple(g.shape)))
+        if h < win or w < win:
+            raise ValueError("%s: picture %d (%d x %d) is smaller than the %d x %d window" % (who, i, h, w, win, win))
+
+
+def _f64_pictures(x, device):
+    """A float64 picture [H][W][3] (numpy or CUDA tensor) -> contiguous CUDA tensor on `device` (what `_device` returned)."""
+    x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).to(device)
+    if x.device != device:
+        raise RuntimeError("painter_engine: the pictures are on %s, expected %s" % (x.device, device))
+    assert x.dtype == torch.float64 and x.dim() == 3 and x.shape[-1] == 3, (x.dtype, tuple(x.shape))
+    return x.contiguous()
+
+
+class RestorationScores:
+    """One launched pa_restore_scores over a list of (prediction, ground truth) device pictures of any sizes: `sums()` is the one copy
+    back (eight doubles per picture) and the one synchronisation.  preds: float64 [H][W][3] (metric "skimage") or uint8 [H][W][3]
+    ("matlab_y") CUDA tensors, contiguous; gts: uint8 [H][W][3] CUDA tensors."""
+
+    def __init__(self, preds, gts, metric, data_range=2.0):
+        self.metric = metric
+        mode, weights, cov_norm, c1, c2 = _restore_setup(metric, data_range)
+        win = len(weights)
+        _restore_sizes("restoration_scores", [tuple(p.shape[:2]) for p in preds], gts, win)
+        self.n = len(preds)
+        if not self.n:
+            return
+        want = torch.float64 if mode == 0 else torch.uint8
+        assert all(p.dtype == want and p.is_cuda and p.is_contiguous() for p in preds), "painter_engine: %s scores %s pictures" % (metric, want)
+        assert all(g.dtype == torch.uint8 and g.is_cuda and g.is_contiguous() for g in gts)
+        dev = preds[0].device
+        self.keep = (preds, gts)
+        tile, ch = lib.pa_restore_tile(), 3 if mode == 0 else 1
+        jobs = (RestoreJob * self.n)()
+        tiles = 0
+        for job, p, g in zip(jobs, preds, gts):
+            job.pred, job.gt, job.h, job.w = p.data_ptr(), g.data_ptr(), int(p.shape[0]), int(p.shape[1])
+            tiles += ch * (-(-(job.h - win + 1) // tile)) * (-(-(job.w - win + 1) // tile))
+        nbytes = lib.pa_restore_workspace_bytes(self.n, tiles)
+        if nbytes < 0:
+            check(1, "pa_restore_scores (%d jobs, %d tiles)" % (self.n, tiles))
+        # the library reads the table on the host and copies it on the stream: pinned, and kept until the next synchronisation
+        self._table_host = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).pin_memory()
+        self._weights = np.ascontiguousarray(weights, dtype=np.float64)
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.out = torch.empty((self.n, RESTORE_OUT), dtype=torch.float64, device=dev)
+        check(lib.pa_restore_scores(self._table_host.data_ptr(), self.n, mode, win, self._weights.ctypes.data, cov_norm, c1, c2,
+                                    self.out.data_ptr(), self.workspace.data_ptr(), _stream()),
+              "pa_restore_scores (%d jobs, %d tiles, metric %s)" % (self.n, tiles, metric))
+
+    def sums(self):
+        """The copy back -> float64 [n][8]: element count, squared sum, then (sum of S, windows) per channel (include/painter_hip.h)."""
+        return self.out.cpu().numpy() if self.n else np.zeros((0, RESTORE_OUT))
+
+    def result(self):
+        return restoration_metrics(self.sums(), self.metric)
+
+
+def restoration_metrics(sums, metric):
+    """float64 [n][8] of pa_restore_scores -> dict(psnr float64 [n], ssim float64 [n]).  skimage: psnr = 10 log10(1 / mse) (data range 1:
+    the clipped prediction is >= 0), ssim = the mean of the three channels' mean S; matlab_y: psnr = 20 log10(255 / sqrt(mse)), ssim = the
+    mean S of the Y plane.  A perfect prediction gives inf and exactly 1.0."""
+    _restore_setup(metric)
+    s = np.asarray(sums, dtype=np.float64).reshape(-1, RESTORE_OUT)
+    ch = 3 if metric == "skimage" else 1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mse = s[:, 1] / s[:, 0]
+        psnr = 10 * np.log10(1 / mse) if metric == "skimage" else 20 * np.log10(255 / np.sqrt(mse))
+        ssim = sum(s[:, 2 + 2 * c] / s[:, 3 + 2 * c] for c in range(ch)) / ch
+    return dict(psnr=psnr, ssim=ssim)
+
+
+def restoration_scores(preds, gts, metric="skimage", data_range=2.0, device="cuda"):
+    """PSNR and SSIM of restored pictures, per picture, in one copy of the job table and two launches for the whole list.
+
+    metric "skimage": what painter_inference_lol.py:166-169 computes -- preds float64 [H][W][3] as `PainterEngine.run` returns them
+    (clipped to [0, 1] on the device), gts uint8 [H][W][3] taken as gt / 255.; `peak_signal_noise_ratio` with data range 1 and
+    `structural_similarity(multichannel=True)` with its defaults: 7 x 7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance, the map
+    cropped by 3 pixels, the mean of the three channel means.  data_range defaults to 2.0: skimage takes it from the float dtype's range
+    (-1, 1) when none is passed, and that is the release whose call signature (`multichannel=`) the reference uses; pass 1.0 for
+    C1 = 0.01^2, C2 = 0.03^2.
+    metric "matlab_y": derain's evaluate_PSNR_SSIM.m -- preds uint8 [H][W][3], the `saved` pictures of `run_restoration`; both pictures
+    to Y (rgb2ycbcr's row in exact integers, rounded half up), PSNR of the Y planes at peak 255, SSIM_index with its 11 x 11 Gaussian.
+    Both are restated from published sources and unverified against skimage / MATLAB, which are not available where this project is
+    tested; tests/painter_restore_host.py is the definition and says what is and is not known.  This is NOT sidd's eval_sidd.m, which
+    uses MATLAB's built-in ssim / psnr on single blocks.
+
+    preds, gts: lists of numpy arrays or CUDA tensors, any sizes.  A picture smaller than the window is a ValueError.
+    -> dict(psnr float64 [n], ssim float64 [n])."""
+    preds, gts = list(preds), list(gts)
+    device = _device([preds, gts], device)
+    mode = _restore_setup(metric, data_range)[0]
+    return RestorationScores([_f64_pictures(p, device) if mode == 0 else _pictures(p, device) for p in preds],
+                             [_pictures(g, device) for g in gts], metric, data_range).result()
+
+
 # ---- panoptic merge (csrc/painter_pano.hip)
 SEGMENT = np.dtype([("id", np.int32), ("isthing", np.int32), ("category_id", np.int32), ("instance_id", np.int32), ("area", np.int32),
                     ("score", np.float32)])                                             # pa_pano_segment of include/painter_hip.h
@@ -931,6 +1072,35 @@ class PainterEngine:
             raise ValueError("painter_engine: task %r saves its output as it is; run_restoration is for derain / lol / sidd" % self.task)
         pairs = self._run(pictures, sizes, lambda p, s: self._run_batch(p, s, True))
         return [o for b in pairs for o in b[0]], [o for b in pairs for o in b[1]]
+
+    def run_restoration_scores(self, pictures, gts, sizes=None, metric=None, data_range=2.0):
+        """derain / lol / sidd: forward and decode as `run`, then `restoration_scores` of every batch straight from the decode plan's
+        device-resident output -- "skimage" reads the float64 pictures, "matlab_y" the `saved` uint8 pictures of the same decode launch;
+        no picture is copied back, eight doubles per picture are.  gts: one uint8 [H][W][3] ground truth per picture, of the restored
+        picture's size (sizes[i], default the query's own).  metric: None for the task's own -- lol: "skimage", derain: "matlab_y"; sidd's
+        eval_sidd.m (MATLAB's built-in ssim / psnr on single blocks) is not restated, so sidd has no default and a metric must be named.
+        -> dict(psnr float64 [n], ssim float64 [n]), as `restoration_scores` returns it."""
+        if self.task not in RESTORE_DEFAULT_METRIC:
+            raise ValueError("painter_engine: run_restoration_scores scores the pictures of derain / lol / sidd, not of %r" % self.task)
+        if metric is None:
+            metric = RESTORE_DEFAULT_METRIC[self.task]
+            if metric is None:
+                raise ValueError("painter_engine: %s has no default metric (eval_sidd.m is not restated): pass metric=\"skimage\" or "
+                                 "metric=\"matlab_y\" and say which one the numbers are" % self.task)
+        win = len(_restore_setup(metric, data_range)[1])                    # everything is checked before the first forward is enqueued
+        pictures, gts = list(pictures), list(gts)
+        sizes = [(p.shape[1], p.shape[0]) for p in pictures] if sizes is None else [(int(w), int(h)) for w, h in sizes]
+        assert len(sizes) == len(pictures)
+        _restore_sizes("run_restoration_scores", [(h, w) for w, h in sizes], gts, win)
+        saved = metric == "matlab_y"
+
+        def batch(pairs, sizes):
+            truths = [_pictures(g, self.device) for _, g in pairs]
+            plan = self._launch_batch([p for p, _ in pairs], sizes, saved)
+            preds = [plan.saved_picture(i) if saved else plan.picture(i) for i in range(plan.n_jobs)]
+            return RestorationScores(preds, truths, metric, data_range).sums()
+        sums = self._run(list(zip(pictures, gts)), sizes, batch)
+        return restoration_metrics(np.concatenate(sums) if sums else np.zeros((0, RESTORE_OUT)), metric)
 
     def run_instances(self, pictures, sizes=None, **kw):
         """coco_pano_inst: forward and decode as `run`, then `instances(picture, **kw)` of every decoded picture straight from the
