@@ -37,8 +37,8 @@ enum {
 };
 
 /* Bumped whenever an entry point's argument list changes (2: `tables` in pa_attn_fwd / pa_attn_bwd; 3: `head_dim` in the attention and
- * rel-pos entry points; 4: `dxT_colsum` in pa_layernorm_bwd, `relpos_part` in pa_attn_bwd, `dx_colsum` in pa_linear_dgrad; 5: the bf16 GELU side output is gelu'(pre), pa_debug_set(9) is a test knob of the conv3x3 weight gradient, pa_attn4_trace is gone, pa_attn_bwd takes `out` / `ldo`, pa_debug_get / pa_attn_launch_counts are new; 6: the bf16 GELU side output is an 8-bit code (uint8, row pitch ldo bytes), pa_debug_set knobs 10 .. 15; 7: the *_skip entry points (DropPath skipping) and pa_debug_set knob 16 -- every earlier entry point keeps its argument list; 8: the pa_painter_* / pa_palette_argmin entry points of Painter task inference -- every earlier entry point keeps its argument list).  painter_amd/_lib.py refuses a library whose pa_abi_version() differs from the header it parsed. */
-#define PA_ABI_VERSION 8
+ * rel-pos entry points; 4: `dxT_colsum` in pa_layernorm_bwd, `relpos_part` in pa_attn_bwd, `dx_colsum` in pa_linear_dgrad; 5: the bf16 GELU side output is gelu'(pre), pa_debug_set(9) is a test knob of the conv3x3 weight gradient, pa_attn4_trace is gone, pa_attn_bwd takes `out` / `ldo`, pa_debug_get / pa_attn_launch_counts are new; 6: the bf16 GELU side output is an 8-bit code (uint8, row pitch ldo bytes), pa_debug_set knobs 10 .. 15; 7: the *_skip entry points (DropPath skipping) and pa_debug_set knob 16 -- every earlier entry point keeps its argument list; 8: the pa_painter_* / pa_palette_argmin entry points of Painter task inference -- every earlier entry point keeps its argument list; 9: `steps` of pa_adamw_step is one count per table record (float[ntensors]) instead of one per group, its `beta1` / `beta2` are doubles, and PaOptGroups loses `active`).  painter_amd/_lib.py refuses a library whose pa_abi_version() differs from the header it parsed. */
+#define PA_ABI_VERSION 9
 int pa_abi_version(void);
 /* diagnostics only (tools/): which = 0 start-up stagger of alternate workgroup rows of the 256x256 GEMM in shader cycles,
  * 1 drop that kernel's epilogue stores (never set by the product path); 2 = tile order of that kernel: 0 blocked 4 x 8 patches per XCD and, for
@@ -343,18 +343,20 @@ typedef struct PaOptTensor {
 } PaOptTensor;
 typedef struct PaOptGroups {                     /* HOST struct, passed by value to the kernel: at most 64 parameter groups */
     float lr[64], wd[64];                        /* learning rate (already times lr_scale), weight decay */
-    int32_t active[64];                          /* 1 = the group has gradients in this step (its step count advances) */
 } PaOptGroups;
 int pa_opt_chunk_elems(void);
 int64_t pa_grad_sumsq_workspace_bytes(int nchunks);
 /* out2 (device, 2 floats): [0] = sum over all gradients of g^2 (as stored, i.e. still multiplied by the loss scale),
  * [1] = 0 if every gradient is finite */
 int pa_grad_sumsq(const PaOptTensor* table, int ntensors, int nchunks, float* out2, void* workspace, hipStream_t stream);
-/* steps: DEVICE float[64], the per-group AdamW step counts (advanced here unless the step is skipped);
+/* steps: DEVICE float[ntensors], one AdamW step count per table record, as torch.optim.AdamW keeps one per parameter: steps[t] is
+ * advanced here exactly when record t has a gradient (g != NULL) and the step is not skipped, and record t's bias corrections
+ * are taken from steps[t] alone -- a parameter that sits out a step keeps its count, whatever its group's other parameters do;
  * norm_info = out2 of pa_grad_sumsq or NULL (no clipping / no finiteness gate); grad_scale = device scalar the gradients are
  * divided by, or NULL; found_inf = device scalar, nonzero skips the step (torch GradScaler protocol), or NULL;
- * max_norm <= 0 disables clipping.  groups is a HOST pointer. */
-int pa_adamw_step(const PaOptTensor* table, int ntensors, int nchunks, const PaOptGroups* groups, float beta1, float beta2,
+ * max_norm <= 0 disables clipping.  groups is a HOST pointer.  beta1 / beta2 are doubles: 1 - beta and 1 - beta^step are formed in
+ * double from the unrounded values, as torch forms them, and only then rounded to float. */
+int pa_adamw_step(const PaOptTensor* table, int ntensors, int nchunks, const PaOptGroups* groups, double beta1, double beta2,
                   float eps, float* steps, const float* norm_info, const float* grad_scale, const float* found_inf,
                   float max_norm, hipStream_t stream);
 

@@ -34,16 +34,20 @@ def adamw_update(p, g, m, v, step, lr, weight_decay, beta1, beta2, eps):
 
 def scaled_clipped_step(params, grads, state, groups, scale, clip_grad, beta1=0.9, beta2=0.999, eps=1e-8):
     """params/grads/state: parallel lists (state[i] = dict(step, exp_avg, exp_avg_sq)); groups[i] = (lr, weight_decay) of tensor i;
-    grads are still multiplied by `scale`.  -> (unscaled pre-clip norm, skipped?)."""
-    g32 = [g.float() / scale for g in grads]
-    finite = all(bool(torch.isfinite(g).all()) for g in g32)
-    norm = total_grad_norm(g32) if finite else torch.tensor(float("nan"))
+    grads are still multiplied by `scale`.  A gradient may be None, as torch.optim.AdamW allows: that parameter and its moments are
+    left alone, its own step count does not advance, and it takes no part in the norm.  -> (unscaled pre-clip norm, skipped?)."""
+    g32 = [None if g is None else g.float() / scale for g in grads]
+    live = [g for g in g32 if g is not None]
+    finite = all(bool(torch.isfinite(g).all()) for g in live)
+    norm = (total_grad_norm(live) if live else torch.tensor(0.0)) if finite else torch.tensor(float("nan"))
     if not finite:
         return norm, True
     coef = 1.0
     if clip_grad is not None and clip_grad > 0:
         coef = min(1.0, float(clip_grad) / (float(norm) + 1e-6))
     for p, g, st, (lr, wd) in zip(params, g32, state, groups):
+        if g is None:
+            continue
         st["step"] += 1
         adamw_update(p, g * coef, st["exp_avg"], st["exp_avg_sq"], st["step"], lr, wd, beta1, beta2, eps)
     return norm, False

@@ -87,10 +87,13 @@ __global__ __launch_bounds__(256) void grad_sumsq_final_kernel(const float* __re
 
 // torch.optim.AdamW single-tensor update, in its operation order (torch/optim/adamw.py, _single_tensor_adamw):
 //   p *= 1 - lr*wd;  m += (g - m)*(1 - b1);  v = v*b2 + (1 - b2)*g*g;  p -= (lr / bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
-DEVI void adamw1(float& p, float& m, float& v, float g, float lr, float wd, float b1, float b2, float eps, float step_size, float rsqrt_bc2) {
+// omb1 / omb2 are 1 - beta taken in double from the unrounded betas, as torch takes them: 1.f - 0.999f is off by 1.3e-5 of itself, and
+// the second moment would carry that error for good
+DEVI void adamw1(float& p, float& m, float& v, float g, float lr, float wd, float omb1, float b2, float omb2, float eps, float step_size,
+                 float rsqrt_bc2) {
     p = p * (1.f - lr * wd);
-    m = m + (g - m) * (1.f - b1);
-    v = v * b2 + (1.f - b2) * g * g;
+    m = m + (g - m) * omb1;
+    v = v * b2 + omb2 * g * g;
     const float denom = sqrtf(v) * rsqrt_bc2 + eps;
     p = p - step_size * (m / denom);
 }
@@ -101,15 +104,17 @@ DEVI void adamw1(float& p, float& m, float& v, float g, float lr, float wd, floa
 DEVI bool skip_step(const float* norm_info, const float* found_inf) {
     return (found_inf != nullptr && found_inf[0] != 0.f) || (norm_info != nullptr && (norm_info[1] != 0.f || !(norm_info[0] <= 3.0e38f)));
 }
-// steps[g] += 1 for every group that takes part in this step, unless the step is skipped (inf/nan): the per-group step count
-// lives on the device so that the skip needs no host round trip (torch's capturable / fused AdamW keeps it there too)
-__global__ void opt_advance_kernel(float* __restrict__ steps, PaOptGroups grp, const float* __restrict__ norm_info,
-                                   const float* __restrict__ found_inf) {
-    const int g = threadIdx.x;
-    if (g < 64 && grp.active[g] && !skip_step(norm_info, found_inf)) steps[g] += 1.f;
+// steps[t] += 1 for every table record that has a gradient in this step, unless the step is skipped (inf/nan).  One count per
+// parameter, as in torch.optim.AdamW: a parameter that sits out a step (SegGPT's unused type token, a layer released later) keeps
+// its own count and bias corrections.  The counts live on the device so that the skip needs no host round trip (torch's
+// capturable / fused AdamW keeps them there too)
+__global__ __launch_bounds__(OPT_NT) void opt_advance_kernel(float* __restrict__ steps, const TensorRec* __restrict__ tab, int nt,
+                                                             const float* __restrict__ norm_info, const float* __restrict__ found_inf) {
+    const int t = blockIdx.x * OPT_NT + threadIdx.x;
+    if (t < nt && tab[t].g != nullptr && !skip_step(norm_info, found_inf)) steps[t] += 1.f;
 }
 
-__global__ __launch_bounds__(OPT_NT) void adamw_step_kernel(const TensorRec* __restrict__ tab, int nt, PaOptGroups grp, float b1, float b2, float eps,
+__global__ __launch_bounds__(OPT_NT) void adamw_step_kernel(const TensorRec* __restrict__ tab, int nt, PaOptGroups grp, double beta1, double beta2, float eps,
                                                             const float* __restrict__ steps, const float* __restrict__ norm_info,
                                                             const float* __restrict__ scale_ptr, const float* __restrict__ found_inf,
                                                             float max_norm) {
@@ -128,8 +133,9 @@ __global__ __launch_bounds__(OPT_NT) void adamw_step_kernel(const TensorRec* __r
     const TensorRec r = tab[t];
     if (r.g == nullptr) return;
     const int gi = r.group;
-    const double stepv = (double)steps[gi];                    // already advanced by opt_advance_kernel
-    const float bc1 = (float)(1.0 - pow((double)b1, stepv)), bc2 = (float)(1.0 - pow((double)b2, stepv));
+    const double stepv = (double)steps[t];                     // this record's own count, already advanced by opt_advance_kernel
+    const float bc1 = (float)(1.0 - pow(beta1, stepv)), bc2 = (float)(1.0 - pow(beta2, stepv));
+    const float omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
     const float lr = grp.lr[gi], wd = grp.wd[gi], step_size = lr / bc1, rsqrt_bc2 = 1.f / sqrtf(bc2);
     const int64_t base = (int64_t)(c - r.first_chunk) * OPT_CHUNK;
     const int len = (int)(min(r.n, base + OPT_CHUNK) - base);
@@ -145,22 +151,22 @@ __global__ __launch_bounds__(OPT_NT) void adamw_step_kernel(const TensorRec* __r
             float4 pp = *reinterpret_cast<const float4*>(p + i), mm = *reinterpret_cast<const float4*>(m + i),
                    vv = *reinterpret_cast<const float4*>(v + i);
             const float4 gg = *reinterpret_cast<const float4*>(g + i);
-            adamw1(pp.x, mm.x, vv.x, gg.x * gmul, lr, wd, b1, b2, eps, step_size, rsqrt_bc2);
-            adamw1(pp.y, mm.y, vv.y, gg.y * gmul, lr, wd, b1, b2, eps, step_size, rsqrt_bc2);
-            adamw1(pp.z, mm.z, vv.z, gg.z * gmul, lr, wd, b1, b2, eps, step_size, rsqrt_bc2);
-            adamw1(pp.w, mm.w, vv.w, gg.w * gmul, lr, wd, b1, b2, eps, step_size, rsqrt_bc2);
+            adamw1(pp.x, mm.x, vv.x, gg.x * gmul, lr, wd, omb1, b2, omb2, eps, step_size, rsqrt_bc2);
+            adamw1(pp.y, mm.y, vv.y, gg.y * gmul, lr, wd, omb1, b2, omb2, eps, step_size, rsqrt_bc2);
+            adamw1(pp.z, mm.z, vv.z, gg.z * gmul, lr, wd, omb1, b2, omb2, eps, step_size, rsqrt_bc2);
+            adamw1(pp.w, mm.w, vv.w, gg.w * gmul, lr, wd, omb1, b2, omb2, eps, step_size, rsqrt_bc2);
             *reinterpret_cast<float4*>(p + i) = pp;
             *reinterpret_cast<float4*>(m + i) = mm;
             *reinterpret_cast<float4*>(v + i) = vv;
             if (w16) *reinterpret_cast<uint2*>(w16 + i) = make_uint2(pack_bf16x2(pp.x, pp.y), pack_bf16x2(pp.z, pp.w));
         }
         for (int i = (len & ~3) + threadIdx.x; i < len; i += OPT_NT) {
-            adamw1(p[i], m[i], v[i], g[i] * gmul, lr, wd, b1, b2, eps, step_size, rsqrt_bc2);
+            adamw1(p[i], m[i], v[i], g[i] * gmul, lr, wd, omb1, b2, omb2, eps, step_size, rsqrt_bc2);
             if (w16) w16[i] = (bf16)p[i];
         }
     } else {
         for (int i = threadIdx.x; i < len; i += OPT_NT) {
-            adamw1(p[i], m[i], v[i], g[i] * gmul, lr, wd, b1, b2, eps, step_size, rsqrt_bc2);
+            adamw1(p[i], m[i], v[i], g[i] * gmul, lr, wd, omb1, b2, omb2, eps, step_size, rsqrt_bc2);
             if (w16) w16[i] = (bf16)p[i];
         }
     }
@@ -181,11 +187,12 @@ extern "C" int pa_grad_sumsq(const PaOptTensor* table, int ntensors, int nchunks
     LAUNCH_CHECK();
 }
 
-extern "C" int pa_adamw_step(const PaOptTensor* table, int ntensors, int nchunks, const PaOptGroups* groups, float beta1, float beta2, float eps,
+extern "C" int pa_adamw_step(const PaOptTensor* table, int ntensors, int nchunks, const PaOptGroups* groups, double beta1, double beta2, float eps,
                              float* steps, const float* norm_info, const float* grad_scale, const float* found_inf, float max_norm,
                              hipStream_t st) {
     if (ntensors <= 0 || nchunks <= 0 || groups == nullptr || steps == nullptr) return (int)hipErrorInvalidValue;
-    PA_LAUNCH(opt_advance_kernel, dim3(1), dim3(64), 0, st, steps, *groups, norm_info, found_inf);
+    PA_LAUNCH(opt_advance_kernel, dim3((ntensors + OPT_NT - 1) / OPT_NT), dim3(OPT_NT), 0, st, steps, reinterpret_cast<const TensorRec*>(table), ntensors,
+              norm_info, found_inf);
     int e = (int)hipGetLastError();
     if (e) return e;
     PA_LAUNCH(adamw_step_kernel, dim3(nchunks), dim3(OPT_NT), 0, st, reinterpret_cast<const TensorRec*>(table), ntensors, *groups, beta1, beta2, eps,

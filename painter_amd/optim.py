@@ -28,7 +28,7 @@ MAX_GROUPS = 64
 
 
 class _Groups(ctypes.Structure):
-    _fields_ = [("lr", ctypes.c_float * 64), ("wd", ctypes.c_float * 64), ("active", ctypes.c_int32 * 64)]
+    _fields_ = [("lr", ctypes.c_float * 64), ("wd", ctypes.c_float * 64)]
 
 
 class AdamW(torch.optim.Optimizer):
@@ -40,17 +40,29 @@ class AdamW(torch.optim.Optimizer):
         if lr < 0.0 or eps < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0) or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        if len(self.param_groups) > MAX_GROUPS:
-            raise NotImplementedError("at most %d parameter groups (the reference builds 52: util/lr_decay.py)" % MAX_GROUPS)
-        b = {tuple(g["betas"]) for g in self.param_groups}
-        e = {g["eps"] for g in self.param_groups}
-        if len(b) != 1 or len(e) != 1:
-            raise NotImplementedError("betas and eps must be shared by all groups (they are in the reference)")
         self._norm_info = None
         self._cached = None
         self._tab_dev = None
-        self._steps = None                   # device float32 [64]: per-group step counts (a skipped step must not advance them)
+        # device float32 array of step counts, one element per parameter as in torch.optim.AdamW (a parameter without gradient in a
+        # step keeps its count; a skipped step advances none).  `_slot[p]` is p's element; slots are handed out in the order the
+        # parameters first take part and never move, and the kernel's table lists the parameters in slot order, so that record t
+        # of the table owns element t.  state[p]["step"] is a 0-d view of that element.
+        self._steps = None
+        self._slot = {}
+        self._checked = {}                   # parameter -> addresses of (p, exp_avg, exp_avg_sq) that passed _table()'s checks
         self._model = None
+
+    def add_param_group(self, param_group):
+        """The kernel's lr / weight-decay tables hold MAX_GROUPS groups (the constructor adds its groups through here too); the
+        group's parameters get their step counts when they first take part in a step."""
+        if len(self.param_groups) >= MAX_GROUPS:
+            raise NotImplementedError("at most %d parameter groups (the reference builds 52: util/lr_decay.py)" % MAX_GROUPS)
+        super().add_param_group(param_group)
+        first, last = self.param_groups[0], self.param_groups[-1]
+        if tuple(last["betas"]) != tuple(first["betas"]) or last["eps"] != first["eps"]:
+            self.param_groups.pop()
+            raise NotImplementedError("betas and eps must be shared by all groups (they are in the reference)")
+        self._cached, self._norm_info = None, None
 
     def bind_model(self, model):
         """Let the update refresh the model's cached bf16 weight copies in the same pass (saves the per-step cast kernels).
@@ -59,27 +71,40 @@ class AdamW(torch.optim.Optimizer):
         return self
 
     # ------------------------------------------------------------------ state / table
-    def _steps_for(self, device):
-        if self._steps is None or self._steps.device != device:
-            self._steps = torch.zeros(MAX_GROUPS, dtype=torch.float32, device=device)
-        return self._steps
-
-    def _init_state(self, p, gi):
-        st = self.state[p]
-        if len(st) == 0:
-            st["step"] = self._steps_for(p.device)[gi]                   # 0-d device view (torch's capturable/fused layout)
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        return st
+    def _assign_slots(self, new):
+        """Give every parameter of `new` its own element of the step array and make state[p]["step"] a view of it.  The array grows
+        when parameters appear (the first step, add_param_group, a parameter whose requires_grad is switched on later): the old
+        counts are copied on the device and every view is re-pointed.  A `step` already in the state (a loaded checkpoint) is kept."""
+        if not new:
+            return
+        dev = new[0].device
+        if self._steps is not None and self._steps.device != dev:
+            raise RuntimeError("painter_amd.optim.AdamW: all parameters must live on one device")
+        have, need = len(self._slot), len(self._slot) + len(new)
+        if self._steps is None or self._steps.numel() < need:
+            grown = torch.zeros((need + 63) // 64 * 64, dtype=torch.float32, device=dev)
+            if have:
+                grown[:have].copy_(self._steps[:have])
+            self._steps = grown
+            for q, i in self._slot.items():
+                self.state[q]["step"] = grown[i]
+        for i, p in enumerate(new, have):
+            self._slot[p] = i
+            st = self.state[p]
+            if "step" in st:
+                self._steps[i].copy_(torch.as_tensor(st["step"]).detach().reshape(()))
+            st["step"] = self._steps[i]                                   # 0-d device view (torch's capturable/fused layout)
+            if "exp_avg" not in st:
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
 
     def state_dict(self):
-        """torch.optim layout.  `step` is stored per parameter as its own 0-d tensor: inside this class the steps of a group are
-        views of one element of a shared device array, and torch.save would keep that aliasing -- a torch.optim.AdamW resuming
-        from such a checkpoint would then advance the shared element once per parameter of the group."""
+        """torch.optim layout.  `step` is handed out per parameter as an independent 0-d tensor: inside this class the steps are
+        views of one device array, and torch.save would store that whole array once per parameter."""
         sd = super().state_dict()
-        for st in sd["state"].values():
-            if torch.is_tensor(st.get("step")):
-                st["step"] = st["step"].detach().clone().reshape(())
+        # the values of sd["state"] are the live per-parameter dicts: build new ones, the views in self.state stay views
+        sd["state"] = {k: {**st, "step": st["step"].detach().clone().reshape(())} if torch.is_tensor(st.get("step")) else dict(st)
+                       for k, st in sd["state"].items()}
         return sd
 
     def zero_grad(self, set_to_none=True):
@@ -87,54 +112,68 @@ class AdamW(torch.optim.Optimizer):
         return super().zero_grad(set_to_none=set_to_none)
 
     def load_state_dict(self, state_dict):
-        """Checkpoints written by torch.optim.AdamW or by this class: re-home the per-parameter `step` scalars in the per-group
-        device array."""
+        """Checkpoints written by torch.optim.AdamW or by this class: re-home every parameter's own `step` scalar in the step
+        array (parameters of one group may carry different counts)."""
         super().load_state_dict(state_dict)
-        for gi, group in enumerate(self.param_groups):
+        self._steps, self._slot, self._checked = None, {}, {}
+        self._cached, self._norm_info = None, None
+        loaded = []
+        for group in self.param_groups:
             for p in group["params"]:
                 st = self.state.get(p, {})
                 if "step" in st:
-                    steps = self._steps_for(p.device)
-                    steps[gi] = float(st["step"])
-                    st["step"] = steps[gi]
                     for k in ("exp_avg", "exp_avg_sq"):
                         st[k] = st[k].to(device=p.device, dtype=torch.float32).contiguous()
+                    loaded.append(p)
+        self._assign_slots(loaded)
 
     def _table(self):
         """Device table of (param, grad, exp_avg, exp_avg_sq) records in flat chunk order; rebuilt every step because the
-        gradient tensors are fresh allocations (a 14 KB pinned -> device copy on the step's stream)."""
+        gradient tensors are fresh allocations (a 14 KB pinned -> device copy on the step's stream).  Record t is the parameter
+        of step slot t: every parameter that has taken part so far is listed, with g = 0 while it has no gradient or is frozen."""
         chunk = int(lib.pa_opt_chunk_elems())
-        recs, dev = [], None
-        nchunks = 0
         self._fresh = []
         shadows = None
         if self._model is not None and getattr(self._model, "_hot", None) is not None:
             shadows = self._model._hot.shadow_buffers()
+        group_of, new = {}, []
         for gi, group in enumerate(self.param_groups):
             for p in group["params"]:
-                if not p.requires_grad:
-                    continue
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("painter_amd.optim.AdamW: parameters must be contiguous fp32 tensors on the MI355X")
-                dev = p.device
-                st = self._init_state(p, gi)
-                g = p.grad
-                gptr = 0
-                if g is not None:
-                    if g.dtype != torch.float32 or not g.is_contiguous() or g.is_sparse:
-                        raise RuntimeError("painter_amd.optim.AdamW: gradients must be dense contiguous fp32")
-                    gptr = g.data_ptr()
-                n = p.numel()
-                w16 = 0
-                if shadows is not None and gptr:
-                    buf = shadows.get(p.data_ptr())
-                    if buf is not None and buf.numel() == n:
-                        w16 = buf.data_ptr()
-                        self._fresh.append(p)
-                recs.append((p.data_ptr(), gptr, st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), w16, n, gi, nchunks))
-                nchunks += (n + chunk - 1) // chunk
-        if not recs:
+                group_of[p] = gi
+                if p.requires_grad and p not in self._slot:
+                    new.append(p)
+        self._assign_slots(new)
+        if not self._slot:
             return None, 0, 0, None
+        recs, nchunks = [], 0
+        dev = self._steps.device
+        ok = lambda t, n: t.is_cuda and t.device == dev and t.dtype == torch.float32 and not t.is_sparse and t.is_contiguous() and t.numel() == n
+        for p in self._slot:                                             # insertion order = slot order
+            st = self.state[p]
+            n = p.numel()
+            # the kernel gets raw pointers: parameter and moments of every record are checked whenever one of their addresses is new
+            # (first step, loaded state, a parameter moved or replaced through .data) -- on the other steps the three compares are all
+            ptrs = (p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr())
+            if self._checked.get(p) != ptrs:
+                if not ok(p, n):
+                    raise RuntimeError("painter_amd.optim.AdamW: parameters must be contiguous fp32 tensors on the MI355X")
+                if not ok(st["exp_avg"], n) or not ok(st["exp_avg_sq"], n):
+                    raise RuntimeError("painter_amd.optim.AdamW: exp_avg / exp_avg_sq must be contiguous fp32 tensors next to their parameter")
+                self._checked[p] = ptrs
+            g = p.grad if p.requires_grad else None
+            gptr = 0
+            if g is not None:                   # torch's .grad setter already pins type, device and shape to the parameter's
+                if g.dtype != torch.float32 or not g.is_contiguous() or g.is_sparse:
+                    raise RuntimeError("painter_amd.optim.AdamW: gradients must be dense contiguous fp32")
+                gptr = g.data_ptr()
+            w16 = 0
+            if shadows is not None and gptr:
+                buf = shadows.get(ptrs[0])
+                if buf is not None and buf.numel() == n:
+                    w16 = buf.data_ptr()
+                    self._fresh.append(p)
+            recs.append((ptrs[0], gptr, ptrs[1], ptrs[2], w16, n, group_of[p], nchunks))
+            nchunks += (n + chunk - 1) // chunk
         arr = np.array(recs, dtype=_REC)
         nbytes = arr.nbytes
         if self._tab_dev is None or self._tab_dev.numel() < nbytes or self._tab_dev.device != dev:
@@ -159,7 +198,7 @@ class AdamW(torch.optim.Optimizer):
         return out
 
     def _grad_ptrs(self):
-        return tuple(0 if p.grad is None else p.grad.data_ptr() for g in self.param_groups for p in g["params"] if p.requires_grad)
+        return tuple((id(p), 0 if p.grad is None else p.grad.data_ptr()) for g in self.param_groups for p in g["params"] if p.requires_grad)
 
     @torch.no_grad()
     def step(self, closure=None, *, grad_scale=None, found_inf=None, max_norm=None):
@@ -191,13 +230,12 @@ class AdamW(torch.optim.Optimizer):
         for gi, group in enumerate(self.param_groups):
             gs.lr[gi] = float(group["lr"])
             gs.wd[gi] = float(group["weight_decay"])
-            gs.active[gi] = int(any(p.requires_grad and p.grad is not None for p in group["params"]))
         f32 = lambda x: 0 if x is None else x.data_ptr()
         as_dev = lambda x: None if x is None else (x if torch.is_tensor(x) else torch.tensor(float(x))).to(device=dev, dtype=torch.float32).reshape(-1)
         grad_scale, found_inf = as_dev(grad_scale), as_dev(found_inf)
         self._keep = (grad_scale, found_inf, norm_info)       # keep the scalars alive until the kernel has been enqueued
         check(lib.pa_adamw_step(tab.data_ptr(), nt, nchunks, ctypes.byref(gs), float(b1), float(b2), float(eps),
-                                self._steps_for(dev).data_ptr(), f32(norm_info), f32(grad_scale), f32(found_inf),
+                                self._steps.data_ptr(), f32(norm_info), f32(grad_scale), f32(found_inf),
                                 float(max_norm) if max_norm else 0.0, ops.stream()), "pa_adamw_step")
         # the kernel rewrote the parameters behind autograd's back: bump their version counters so that everything keyed on
         # them (the engine's cached bf16 operand copies, autograd's saved-tensor checks) sees the update

@@ -131,7 +131,7 @@ def test_header_declares_and_library_resolves_the_entry_points():
     for name in ("pa_painter_stitch", "pa_painter_decode_u8", "pa_painter_decode_depth", "pa_painter_decode_f64", "pa_palette_argmin"):
         assert name in protos
         assert getattr(lib, name) is not None
-    assert lib.pa_abi_version() == 8
+    assert lib.pa_abi_version() == 9
 
 
 def test_engine_refuses_a_cpu_device():

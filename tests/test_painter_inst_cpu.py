@@ -75,7 +75,7 @@ def test_header_declares_and_library_resolves_the_entry_points():
     assert len(protos["pa_inst_decode"][1]) == 19
     assert lib.pa_inst_workspace_bytes(480, 640, 6400, 1, 2000) > 2000 * 480 * 640 // 8          # host only: no GPU needed
     assert lib.pa_inst_workspace_bytes(0, 640, 6400, 1, 2000) == -1 and lib.pa_inst_workspace_bytes(480, 640, 6400, 1, 4097) == -1
-    assert lib.pa_abi_version() == 8
+    assert lib.pa_abi_version() == 9
 
 
 def test_instances_refuses_a_cpu_device():

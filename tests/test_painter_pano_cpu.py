@@ -146,7 +146,7 @@ def test_header_declares_and_library_resolves_the_entry_points():
     for bad in ((0, 8, 133, 80, 100), (4097, 4096, 133, 80, 100), (8, 8, 1025, 80, 100), (8, 8, 133, 1, 100), (8, 8, 133, 134, 100),
                 (8, 8, 133, 80, 0), (8, 8, 133, 80, 1025)):
         assert lib.pa_pano_workspace_bytes(*bad) == -1, bad
-    assert lib.pa_abi_version() == 8
+    assert lib.pa_abi_version() == 9
 
 
 def test_panoptic_refuses_a_cpu_device():

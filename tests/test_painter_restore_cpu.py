@@ -25,7 +25,7 @@ def test_header_declares_and_library_resolves_the_entry_points():
     for name, n_args in (("pa_restore_scores", 11), ("pa_restore_workspace_bytes", 2), ("pa_restore_tile", 0)):
         assert name in protos and len(protos[name][1]) == n_args
         assert getattr(lib, name) is not None
-    assert lib.pa_abi_version() == 8
+    assert lib.pa_abi_version() == 9
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "painter_hip.h")).read()
     assert "pa_restore_job" in header and "#define PA_RESTORE_RGB_F64 0" in header and "#define PA_RESTORE_Y_U8 1" in header
     tile = lib.pa_restore_tile()

@@ -32,7 +32,7 @@ def test_header_declares_and_library_resolves_the_entry_points():
         assert name in protos
         assert getattr(lib, name) is not None
     assert len(protos["pa_semseg_confusion"][1]) == 11 and len(protos["pa_depth_errors"][1]) == 8
-    assert lib.pa_abi_version() == 8
+    assert lib.pa_abi_version() == 9
     # the LDS budget: 12 K bytes of palette rounded up to 16, plus 4 (K + 1)^2 bytes of bins, within 160 KB -- K = 199 is the last that fits
     for k in (1, 133, 150, 199, 200, 255):
         fits = -(-12 * k // 16) * 16 + 4 * (k + 1) ** 2 <= 160 * 1024
