@@ -666,6 +666,54 @@ int64_t pa_restore_workspace_bytes(int n_jobs, int64_t total_tiles);
 int pa_restore_scores(const pa_restore_job* jobs, int n_jobs, int mode, int win, const double* weights_f64, double cov_norm, double c1,
                       double c2, void* out_f64, void* workspace, hipStream_t stream);
 
+/* Panoptic quality of panoptic maps against ground-truth annotations, csrc/painter_pq.hip: panopticapi's pq_compute_single_core per
+ * picture and the sums of its PQStat over a data set, restated from panopticapi's published source and unverified against panopticapi;
+ * tests/painter_pq_host.py is the definition.  A DEVICE job table, one record per picture, pictures of any sizes in one call; the map,
+ * its segment table and the segment count may be the ones pa_pano_decode wrote and are read where it left them. */
+typedef struct pa_pq_gt_segment {
+    int id;              /* r + 256 g + 65536 b of its pixels in the annotation PNG, > 0 */
+    int category;        /* index 0 .. n_classes - 1 */
+    int iscrowd;
+    int area;            /* the annotation's own number; < 0 = count it from the map */
+    int rank;            /* position in the annotation's segments_info: of the crowd segments of a category the last one listed counts */
+    int reserved;
+} pa_pq_gt_segment;
+typedef struct pa_pq_job {
+    const void* pred;             /* int32 [h][w], 0 = VOID (pa_pano_decode's out_panoptic) */
+    const void* gt;               /* int32 [h][w] = r + 256 g + 65536 b of the annotation PNG, or uint8 [h][w][3] (gt_rgb != 0); 0 = VOID */
+    const void* pred_segments;    /* pa_pano_segment [p_cap]: id and category_id are read; ascending ids */
+    const void* gt_segments;      /* pa_pq_gt_segment [n_gt]; ascending ids */
+    const void* pred_count;       /* DEVICE int32 [1]: the number of predicted segments P, clamped to 0 .. p_cap */
+    int32_t h, w;                 /* a job with h < 1, w < 1 or h * w > 2^31 counts no pixel */
+    int32_t gt_rgb;
+    int32_t n_gt;                 /* G, clamped to 0 .. g_cap */
+    int32_t g_cap, p_cap;         /* what the job's tables hold; the call's capacities bound both once more */
+} pa_pq_job;
+/* 1 when a workgroup's private bins, 4 (g_cap + 2)(p_cap + 1) bytes, fit next to the two id maps (8 KB) in the 160 KB of LDS of a CU; 0
+ * otherwise and for capacities outside 1 <= g_cap <= 254, 1 <= p_cap <= 255. */
+int pa_pq_lds_bins(int g_cap, int p_cap);
+/* host only: bytes of pa_pq_add's workspace (a uint32 matrix (g_cap + 2) x (p_cap + 1) per job, 12 bytes per job and g slot, 8 bytes per
+ * job and category), -1 for n_jobs outside 1 .. 65535, capacities outside the ranges above or n_classes outside 1 .. 1024. */
+int64_t pa_pq_workspace_bytes(int n_jobs, int g_cap, int p_cap, int n_classes);
+/* Per job: C[g][p] = pixels with ground-truth row g (0 VOID, 1 .. G listed, G + 1 a non-zero id that is not listed) and predicted column
+ * p (0 VOID, 1 .. P listed); parea[p] = sum_g C[g][p]; garea[g] = the annotation's area, or sum_p C[g][p].  For g, p >= 1 with C[g][p] > 0,
+ * no crowd flag on g and equal categories: iou = (double)C[g][p] / (double)(parea[p] + garea[g] - C[g][p] - C[0][p]); iou > 0.5 is a match:
+ * tp[cat] += 1, iou[cat] += iou.  An unmatched g without crowd flag: fn[cat] += 1.  An unmatched p: fp[cat] += 1 unless (double)(C[0][p] +
+ * C[g_c][p]) / (double)parea[p] > 0.5, g_c = the crowd segment of cat[p] with the largest rank (of equal ranks the later entry).
+ * acc_tp / acc_fp / acc_fn: int64 [n_classes], acc_iou: float64 [n_classes], 8-byte aligned, ACCUMULATED in place: one set serves a data
+ * set.  The float64 additions are made by one thread per category, jobs in table order, matches in ascending g: two runs give the same
+ * bits, and so does the host statement.  Integer atomics only.
+ * flags_u32: uint32 [n_jobs], written.  A job with a non-zero flag word adds nothing: bit 0 a non-zero predicted id that is not listed (its
+ * pixels are not counted), 1 a listed predicted segment without a pixel, 2 a category outside [0, n_classes), 3 union <= 0, 4 a segment
+ * matched twice (both only with inconsistent annotation areas), 5 a table whose ids are not ascending from above 0.  With bit 2 or 5 nothing
+ * is matched, so bits 3 and 4 stay clear.
+ * max_pixels: the largest h * w of the table, 1 .. 2^31 (it sizes the grid only).  bins: 0 = the count kernel's private bins are in LDS
+ * whenever pa_pq_lds_bins(g_cap, p_cap), else every run of equal neighbours adds to the job's matrix directly; 1 = the direct form at any
+ * capacities (measurements).  workspace: pa_pq_workspace_bytes, 16-byte aligned.  Null pointers, sizes outside the ranges named here or
+ * misaligned buffers return hipErrorInvalidValue before anything is enqueued.  Two clears and three launches on `stream`. */
+int pa_pq_add(const pa_pq_job* jobs, int n_jobs, int64_t max_pixels, int g_cap, int p_cap, int n_classes, int bins, void* acc_tp_i64,
+              void* acc_fp_i64, void* acc_fn_i64, void* acc_iou_f64, void* flags_u32, void* workspace, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

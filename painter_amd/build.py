@@ -28,10 +28,11 @@ FLAGS = FLAGS + os.environ.get("PA_EXTRA_FLAGS", "").split()
 # the reference's argmax (tests/painter_pose_host.py).  painter_score.hip: the float32 divisions, clamp and ratio of the depth evaluation
 # decide its threshold counts, and a pixel's class is the float32 arg-min of painter_io.hip (tests/painter_score_host.py).
 # painter_restore.hip: the float64 window moments and S are stated operation by operation, and a perfect prediction must give exactly 1
-# (tests/painter_restore_host.py).
+# (tests/painter_restore_host.py).  painter_pq.hip: two float64 divisions feed the comparisons with 0.5 that panopticapi makes in Python
+# floats (tests/painter_pq_host.py).
 EXTRA = {"seggpt_io.hip": ["-ffp-contract=off"], "pair_io.hip": ["-ffp-contract=off"], "painter_io.hip": ["-ffp-contract=off"],
          "painter_inst.hip": ["-ffp-contract=off"], "painter_pano.hip": ["-ffp-contract=off"], "painter_pose.hip": ["-ffp-contract=off"],
-         "painter_score.hip": ["-ffp-contract=off"], "painter_restore.hip": ["-ffp-contract=off"]}
+         "painter_score.hip": ["-ffp-contract=off"], "painter_restore.hip": ["-ffp-contract=off"], "painter_pq.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -39,6 +39,12 @@ them from the saved PNGs (metric "matlab_y"), from the decode's device-resident 
 over a job table, eight doubles per picture back (tests/painter_restore_host.py is the definition; both metrics are restated from
 published sources and unverified against skimage / MATLAB).
 
+`PanopticQuality` and `run_panoptic_quality` score panoptic maps against COCO panoptic annotations (csrc/painter_pq.hip): the joint
+histogram of (ground-truth segment, predicted segment) per picture, the match at IoU > 0.5 and the false-negative / false-positive rules
+of panopticapi's pq_compute_single_core, read from the panoptic decode's device-resident map, segment table and count -- four numbers
+per category back for a whole data set (tests/painter_pq_host.py is the definition; restated from panopticapi's published source and
+unverified against panopticapi).
+
 Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
 (`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
 `cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
@@ -48,7 +54,7 @@ evaluators what is left after the colour -> class decode (`class_map`), the conf
 (`instances`) and the panoptic merge (`panoptic`): the boundary-IoU branch (`_compute_boundary_iou`, cv2 erosion), `encode_json_sem_seg`
 and its RLE, the final ratios of `evaluate` (`SemsegScore.scores` restates them on the host); of the depth evaluation its KITTI branches
 (`do_kb_crop`, `garg_crop`) and the division of the sums;
-PQ computation and PNG encoding; of the pose route mmpose's OKS NMS, rescoring and COCOeval, and the 34 numbers per box of `to_image`.
+PNG encoding, RLE and COCOeval; of the pose route mmpose's OKS NMS, rescoring and COCOeval, and the 34 numbers per box of `to_image`.
 
 One host path serves the routes: `_device` / `_pictures` put the inputs of a call on one indexed CUDA device; INSTANCE_DEFAULTS,
 MERGE_DEFAULTS, POSE_DEFAULTS and DEPTH_DEFAULTS hold the keyword defaults and `_check_arguments` refuses the rest before a forward is enqueued; an output
@@ -1007,6 +1013,242 @@ def run_panoptic(semseg_engine, inst_engine, pictures, sizes=None, **kw):
 
     with _eval_mode(inst_engine.model):
         return [o for b in semseg_engine._run(pictures, sizes, batch) for o in b]
+
+
+class PqJob(ctypes.Structure):
+    """pa_pq_job of include/painter_hip.h."""
+    _fields_ = [("pred", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("pred_segments", ctypes.c_void_p), ("gt_segments", ctypes.c_void_p),
+                ("pred_count", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("gt_rgb", ctypes.c_int32),
+                ("n_gt", ctypes.c_int32), ("g_cap", ctypes.c_int32), ("p_cap", ctypes.c_int32)]
+
+
+GT_SEGMENT = np.dtype([("id", np.int32), ("category", np.int32), ("iscrowd", np.int32), ("area", np.int32), ("rank", np.int32),
+                       ("reserved", np.int32)])                                         # pa_pq_gt_segment of include/painter_hip.h
+PQ_MAX_GT, PQ_MAX_PRED = 254, 255                                                       # pa_pq_add's capacities
+PQ_FLAGS = ("a non-zero predicted id that is not in its segment list", "a listed predicted segment without a pixel",
+            "a category outside the %d classes", "union <= 0 (inconsistent annotation areas)",
+            "a segment matched more than once (inconsistent annotation areas)", "a repeated or non-positive segment id")
+
+
+def pq_averages(tp, fp, fn, iou, isthing, labels=None):
+    """panopticapi's PQStat.pq_average over all categories, the things and the stuff, in Python floats: over the categories of a group
+    with tp + fp + fn > 0, pq = iou / (tp + fp / 2 + fn / 2), sq = iou / tp (0 without a true positive), rq = tp / (tp + fp / 2 + fn / 2),
+    the group's numbers their means (nan for a group without such a category, where panopticapi divides by zero).  -> dict with the
+    keys detectron2's COCOPanopticEvaluator prints, x 100 (PQ SQ RQ PQ_th SQ_th RQ_th PQ_st SQ_st RQ_st), `per_class` = {label: dict(pq,
+    sq, rq)} x 100 and `n` = dict(All, Things, Stuff), the categories averaged.  Restated from panopticapi's published source;
+    panopticapi is not available where this project is tested, so the formulas are unverified against panopticapi."""
+    k = len(tp)
+    labels = list(range(k)) if labels is None else list(labels)
+    rows = []
+    for c in range(k):
+        t, p, f, s = int(tp[c]), int(fp[c]), int(fn[c]), float(iou[c])
+        rows.append(None if t + p + f == 0 else (s / (t + 0.5 * p + 0.5 * f), s / t if t != 0 else 0, t / (t + 0.5 * p + 0.5 * f)))
+    res = {}
+    counts = {}
+    for suffix, name, want in (("", "All", None), ("_th", "Things", True), ("_st", "Stuff", False)):
+        pq = sq = rq = 0.0
+        n = 0
+        for c in range(k):
+            if rows[c] is None or (want is not None and bool(isthing[c]) != want):
+                continue
+            n += 1
+            pq, sq, rq = pq + rows[c][0], sq + rows[c][1], rq + rows[c][2]
+        counts[name] = n
+        for key, v in (("PQ", pq), ("SQ", sq), ("RQ", rq)):
+            res[key + suffix] = 100 * (v / n) if n else float("nan")
+    zero = (0.0, 0.0, 0.0)
+    res["per_class"] = {labels[c]: dict(zip(("pq", "sq", "rq"), (100 * v for v in (rows[c] or zero)))) for c in range(k)}
+    res["n"] = counts
+    return res
+
+
+class PanopticQuality:
+    """PQ of a data set, kept on the device (pa_pq_add, csrc/painter_pq.hip): panopticapi's pq_compute_single_core per picture -- the
+    joint histogram of (ground-truth segment, predicted segment), the match at IoU > 0.5, false negatives, false positives with the
+    VOID / crowd rule -- and the sums of PQStat.  Per `add` three launches for the whole list; nothing is copied back before `counts()` /
+    `result()`: 4 x n_classes numbers and a flag word per picture.  tests/painter_pq_host.py is the definition; it is restated from
+    panopticapi's published source and unverified against panopticapi.
+
+    Categories are indices 0 .. n_classes - 1, things first (isthing = index < n_things), which is what `panoptic` reports.  categories=
+    [dict(id=, isthing=), ...] instead names the data set's own ids: `category_id`s of `add` are then mapped through it on the host
+    (an id it does not hold refuses the picture) and `per_class` is keyed by them; the segments of `add_decodes` come from the device
+    and stay indices into that list.  RLE / COCOeval, splitting over cores and PNG / JSON I/O are not here."""
+
+    def __init__(self, n_classes=133, n_things=80, device="cuda", categories=None):
+        self.device = _device((), device)
+        if categories is not None:
+            n_classes = len(categories)
+            self.labels = [c["id"] for c in categories]
+            self.isthing = [bool(c["isthing"]) for c in categories]
+            self.index = {label: i for i, label in enumerate(self.labels)}
+            assert len(self.index) == n_classes, "PanopticQuality: a category id is listed twice"
+        else:
+            self.labels, self.index = list(range(int(n_classes))), None
+            self.isthing = [c < int(n_things) for c in range(int(n_classes))]
+        self.k = int(n_classes)
+        if not 1 <= self.k <= 1024:
+            raise ValueError("PanopticQuality: %d classes (1 .. 1024)" % self.k)
+        self.bins = 0                                        # pa_pq_add's `bins`: 1 forces the direct form (tools/painter_pq_bench.py)
+        self.min_caps = (1, 1)                               # capacities (G_cap, P_cap) a call has at least (tests, measurements)
+        self.at, size = _layout([("tp", np.int64, self.k, 8), ("fp", np.int64, self.k, 8), ("fn", np.int64, self.k, 8),
+                                 ("iou", np.float64, self.k, 8)])
+        self.out = torch.zeros(size, dtype=torch.uint8, device=self.device)
+        self._flags, self._last = [], None
+
+    def reset(self):
+        self.out.zero_()
+        self._flags, self._last = [], None
+
+    def _category(self, c):
+        return int(c) if self.index is None else self.index.get(c, -1)
+
+    def _gt_table(self, segments):
+        """dicts(id, category_id, iscrowd, area) -> GT_SEGMENT records in ascending id order; rank = position in the list."""
+        t = np.zeros(len(segments), GT_SEGMENT)
+        for rank, s in enumerate(segments):
+            area = s.get("area")
+            t[rank] = (int(s["id"]), self._category(s["category_id"]), int(bool(s.get("iscrowd", 0))), -1 if area is None else int(area), rank, 0)
+        return t[np.argsort(t["id"], kind="stable")]
+
+    def _pred_table(self, segments):
+        t = np.zeros(len(segments), SEGMENT)
+        for i, s in enumerate(segments):
+            t[i]["id"], t[i]["category_id"] = int(s["id"]), self._category(s["category_id"])
+        return t[np.argsort(t["id"], kind="stable")]
+
+    def _add(self, preds, gts, gt_segments, keep):
+        """preds: per picture (address of the int32 map, h, w, predicted table as SEGMENT records or its device address, address of the
+        device count or None, capacity of the table).  Tables, counts and the job table go up in ONE pinned copy."""
+        n = len(preds)
+        if not (n == len(gts) == len(gt_segments)):
+            raise ValueError("PanopticQuality: %d predictions, %d ground-truth maps, %d ground-truth segment lists" % (n, len(gts), len(gt_segments)))
+        if n == 0:
+            return self
+        if _device([[g for g in gts]], self.device) != self.device:
+            raise RuntimeError("painter_engine: this PanopticQuality lives on %s" % self.device)
+        maps = [_pictures(g, self.device) if g.ndim == 3 else _maps(g if torch.is_tensor(g) else np.ascontiguousarray(g, dtype=np.int32),
+                                                                     self.device, torch.int32) for g in gts]
+        for i, (p, g) in enumerate(zip(preds, maps)):
+            if (p[1], p[2]) != tuple(g.shape[:2]):
+                raise ValueError("PanopticQuality: prediction %d is %s, its ground truth %s" % (i, (p[1], p[2]), tuple(g.shape[:2])))
+        gtabs = [self._gt_table(s) for s in gt_segments]
+        g_cap = max([self.min_caps[0]] + [len(t) for t in gtabs])
+        p_cap = max([self.min_caps[1]] + [p[5] for p in preds])
+        if g_cap > PQ_MAX_GT or p_cap > PQ_MAX_PRED:
+            raise ValueError("PanopticQuality: %d ground-truth / %d predicted segments in a picture (at most %d / %d)"
+                             % (g_cap, p_cap, PQ_MAX_GT, PQ_MAX_PRED))
+        sections = [("jobs", np.uint8, ctypes.sizeof(PqJob) * n, 16)]
+        for i, (p, t) in enumerate(zip(preds, gtabs)):
+            sections += [("gt%d" % i, GT_SEGMENT, len(t), 8), ("pred%d" % i, SEGMENT, 0 if p[4] is not None else len(p[3]), 8),
+                         ("count%d" % i, np.int32, 0 if p[4] is not None else 1, 4)]
+        at, size = _layout(sections)
+        host = torch.zeros(max(size, 1), dtype=torch.uint8).pin_memory()
+        dev = torch.empty(max(size, 1), dtype=torch.uint8, device=self.device)
+        a, base = host.numpy(), dev.data_ptr()
+        jobs = (PqJob * n)()
+        for i, (job, p, g, t) in enumerate(zip(jobs, preds, maps, gtabs)):
+            _section(a, at, "gt%d" % i)[:] = t
+            job.pred, job.h, job.w, job.gt, job.gt_rgb = p[0], p[1], p[2], g.data_ptr(), int(g.dim() == 3)
+            job.gt_segments, job.n_gt, job.g_cap, job.p_cap = base + at["gt%d" % i][0], len(t), len(t), p[5]
+            if p[4] is not None:
+                job.pred_segments, job.pred_count = p[3], p[4]
+            else:
+                _section(a, at, "pred%d" % i)[:] = p[3]
+                _section(a, at, "count%d" % i)[:] = len(p[3])
+                job.pred_segments, job.pred_count = base + at["pred%d" % i][0], base + at["count%d" % i][0]
+        _section(a, at, "jobs")[:] = np.frombuffer(bytearray(jobs), np.uint8)
+        dev.copy_(host, non_blocking=True)
+        shape = (n, g_cap, p_cap, self.k)
+        nbytes = lib.pa_pq_workspace_bytes(*shape)
+        if nbytes < 0:
+            check(1, "pa_pq_add (sizes %s)" % (shape,))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        flags = torch.empty(n, dtype=torch.int32, device=self.device)
+        ptr = lambda name: self.out.data_ptr() + self.at[name][0]
+        check(lib.pa_pq_add(base + at["jobs"][0], n, max(p[1] * p[2] for p in preds), g_cap, p_cap, self.k, self.bins, ptr("tp"), ptr("fp"),
+                            ptr("fn"), ptr("iou"), flags.data_ptr(), workspace.data_ptr(), _stream()), "pa_pq_add (sizes %s)" % (shape,))
+        self._flags.append(flags)
+        self._last = (keep, maps, host, dev, workspace)      # what the enqueued launches read, until the next call
+        return self
+
+    def add(self, preds, pred_segments, gts, gt_segments):
+        """preds: panoptic maps int32 [H][W] of any sizes, 0 = VOID (numpy arrays or CUDA tensors); pred_segments: per picture the list of
+        dicts `panoptic` returns (id and category_id are read); gts: the annotation PNGs as uint8 [H][W][3] or as int32 [H][W] = r + 256 g +
+        65536 b; gt_segments: per picture the annotation's `segments_info` (id, category_id, iscrowd, area; area None = count it from
+        the map).  Nothing is copied back.  -> self."""
+        preds, pred_segments = list(preds), list(pred_segments)
+        if len(preds) != len(pred_segments):
+            raise ValueError("PanopticQuality.add: %d maps, %d segment lists" % (len(preds), len(pred_segments)))
+        if _device([preds], self.device) != self.device:
+            raise RuntimeError("painter_engine: this PanopticQuality lives on %s" % self.device)
+        maps = [_maps(p if torch.is_tensor(p) else np.ascontiguousarray(p, dtype=np.int32), self.device, torch.int32) for p in preds]
+        tables = [self._pred_table(s) for s in pred_segments]
+        return self._add([(m.data_ptr(), int(m.shape[0]), int(m.shape[1]), t, None, len(t)) for m, t in zip(maps, tables)], list(gts),
+                         list(gt_segments), maps)
+
+    def add_decodes(self, decodes, gts, gt_segments):
+        """decodes: launched PanopticDecodes (`_launch_panoptic`); map, segment table and count are read where each decode left them, so
+        neither has to be copied back first.  Their categories are the semantic palette's indices.  -> self."""
+        decodes = list(decodes)
+        srcs = []
+        for d in decodes:
+            if d.out.device != self.device:
+                raise RuntimeError("painter_engine: this PanopticQuality lives on %s" % self.device)
+            at = lambda name: d.out.data_ptr() + d.at[name][0]
+            srcs.append((at("panoptic"), d.h, d.w, at("segments"), at("count"), d.max_inst + d.k - d.n_things))
+        return self._add(srcs, list(gts), list(gt_segments), decodes)
+
+    def counts(self):
+        """The one copy back (and synchronisation), with the flag words -> tp, fp, fn int64 [n_classes], iou float64 [n_classes] (numpy).
+        ValueError names the first refused picture (counted over all `add` calls since `reset`) and why."""
+        a = torch.cat([self.out] + [f.view(torch.uint8) for f in self._flags]).cpu().numpy()
+        flags = a[self.out.numel():].view(np.uint32)
+        bad = np.flatnonzero(flags)
+        if len(bad):
+            word = int(flags[bad[0]])
+            bit = (word & -word).bit_length() - 1
+            why = PQ_FLAGS[bit] % self.k if "%d" in PQ_FLAGS[bit] else PQ_FLAGS[bit]
+            raise ValueError("PanopticQuality: picture %d is refused (flag bit %d, flags 0x%02x): %s; %d of %d pictures are refused and add "
+                             "nothing" % (bad[0], bit, word, why, len(bad), len(flags)))
+        return tuple(_section(a, self.at, name).copy() for name in ("tp", "fp", "fn", "iou"))
+
+    def result(self):
+        """`pq_averages` of `counts()`: PQ, SQ, RQ over all categories, things (`_th`) and stuff (`_st`) in percent, `per_class` and `n`
+        -- on the host in Python floats; panopticapi's formulas restated, unverified against panopticapi."""
+        return pq_averages(*self.counts(), self.isthing, self.labels)
+
+
+def run_panoptic_quality(semseg_engine, inst_engine, pictures, gts, gt_segments, score, sizes=None, **kw):
+    """`run_panoptic`'s loop ending in `score.add_decodes` (a PanopticQuality) instead of `result()`: the panoptic maps, their segment
+    tables and the byte masks are never copied back, and nothing else is before `score.counts()` / `score.result()`.  gts, gt_segments:
+    per picture the annotation (see PanopticQuality.add), of the painted picture's size (sizes[i], default the query's own).  -> score."""
+    if semseg_engine.task != "coco_pano_semseg" or inst_engine.task != "coco_pano_inst":
+        raise ValueError("painter_engine: run_panoptic_quality takes a coco_pano_semseg engine and a coco_pano_inst engine, not %r and %r"
+                         % (semseg_engine.task, inst_engine.task))
+    kw = {k: v for k, v in kw.items() if k != "device"}
+    _check_arguments("panoptic", kw, INSTANCE_DEFAULTS, MERGE_DEFAULTS)          # before the first forward is enqueued
+    merge = {k: kw.pop(k, v) for k, v in MERGE_DEFAULTS.items()}                 # kw keeps what belongs to the instance decode
+    palette, n_things = merge.pop("semseg_palette"), merge.pop("n_things")
+    pictures, gts, gt_segments = list(pictures), list(gts), list(gt_segments)
+    sizes = [(p.shape[1], p.shape[0]) for p in pictures] if sizes is None else [(int(w), int(h)) for w, h in sizes]
+    if not (len(pictures) == len(gts) == len(gt_segments) == len(sizes)):
+        raise ValueError("run_panoptic_quality: %d pictures, %d ground-truth maps, %d segment lists" % (len(pictures), len(gts), len(gt_segments)))
+    for i, ((w, h), g) in enumerate(zip(sizes, gts)):
+        if (h, w) != tuple(g.shape[:2]):
+            raise ValueError("run_panoptic_quality: picture %d is %s, its ground truth %s" % (i, (h, w), tuple(g.shape[:2])))
+
+    def batch(items, sizes):
+        pics = [p for p, _, _ in items]
+        sem = semseg_engine._launch_batch(pics, sizes, False)
+        jobs, step = [], inst_engine.batch_size
+        for j in range(0, len(pics), step):
+            inst = inst_engine._launch_batch(pics[j:j + step], sizes[j:j + step], False)
+            jobs += [_launch_panoptic(sem.picture(j + i), inst.picture(i), None, palette, n_things, merge, kw) for i in range(inst.n_jobs)]
+        score.add_decodes(jobs, [g for _, g, _ in items], [s for _, _, s in items])
+
+    with _eval_mode(inst_engine.model):
+        semseg_engine._run(list(zip(pictures, gts, gt_segments)), sizes, batch)
+    return score
 
 
 class PainterEngine:
