@@ -37,7 +37,7 @@ enum {
 };
 
 /* Bumped whenever an entry point's argument list changes (2: `tables` in pa_attn_fwd / pa_attn_bwd; 3: `head_dim` in the attention and
- * rel-pos entry points; 4: `dxT_colsum` in pa_layernorm_bwd, `relpos_part` in pa_attn_bwd, `dx_colsum` in pa_linear_dgrad; 5: the bf16 GELU side output is gelu'(pre), pa_debug_set(9) is a test knob of the conv3x3 weight gradient, pa_attn4_trace is gone, pa_attn_bwd takes `out` / `ldo`, pa_debug_get / pa_attn_launch_counts are new; 6: the bf16 GELU side output is an 8-bit code (uint8, row pitch ldo bytes), pa_debug_set knobs 10 .. 15; 7: the *_skip entry points (DropPath skipping) and pa_debug_set knob 16 -- every earlier entry point keeps its argument list; 8: the pa_painter_* / pa_palette_argmin entry points of Painter task inference -- every earlier entry point keeps its argument list; 9: `steps` of pa_adamw_step is one count per table record (float[ntensors]) instead of one per group, its `beta1` / `beta2` are doubles, and PaOptGroups loses `active`).  painter_amd/_lib.py refuses a library whose pa_abi_version() differs from the header it parsed. */
+ * rel-pos entry points; 4: `dxT_colsum` in pa_layernorm_bwd, `relpos_part` in pa_attn_bwd, `dx_colsum` in pa_linear_dgrad; 5: the bf16 GELU side output is gelu'(pre), pa_debug_set(9) is a test knob of the conv3x3 weight gradient, pa_attn4_trace is gone, pa_attn_bwd takes `out` / `ldo`, pa_debug_get / pa_attn_launch_counts are new; 6: the bf16 GELU side output is an 8-bit code (uint8, row pitch ldo bytes), pa_debug_set knobs 10 .. 15; 7: the *_skip entry points (DropPath skipping) and pa_debug_set knob 16 -- every earlier entry point keeps its argument list; 8: the pa_painter_* / pa_palette_argmin entry points of Painter task inference -- every earlier entry point keeps its argument list; 9: `steps` of pa_adamw_step is one count per table record (float[ntensors]) instead of one per group, its `beta1` / `beta2` are doubles, and PaOptGroups loses `active`; still 9 with the pa_pq_* and pa_ap_* entry points: they are purely additive, every earlier entry point keeps its argument list and its meaning).  painter_amd/_lib.py refuses a library whose pa_abi_version() differs from the header it parsed. */
 #define PA_ABI_VERSION 9
 int pa_abi_version(void);
 /* diagnostics only (tools/): which = 0 start-up stagger of alternate workgroup rows of the 256x256 GEMM in shader cycles,
@@ -713,6 +713,66 @@ int64_t pa_pq_workspace_bytes(int n_jobs, int g_cap, int p_cap, int n_classes);
  * misaligned buffers return hipErrorInvalidValue before anything is enqueued.  Two clears and three launches on `stream`. */
 int pa_pq_add(const pa_pq_job* jobs, int n_jobs, int64_t max_pixels, int g_cap, int p_cap, int n_classes, int bins, void* acc_tp_i64,
               void* acc_fp_i64, void* acc_fn_i64, void* acc_iou_f64, void* flags_u32, void* workspace, hipStream_t stream);
+
+/* COCO instance mask AP up to the per-detection match flags, csrc/painter_ap.hip: COCOeval.computeIoU and COCOeval.evaluateImg (iouType
+ * "segm") per picture, restated from pycocotools' published source and unverified against pycocotools; tests/painter_ap_host.py is the
+ * definition.  A DEVICE job table, one record per picture, pictures of any sizes in one call; the detections' bit masks, scores and count
+ * may be the ones pa_inst_decode wrote, their classes the ones pa_pano_decode wrote, and are read where those left them. */
+#define PA_AP_AGNOSTIC 1        /* bits of `modes`: useCats = 0, every detection against every ground truth */
+#define PA_AP_PER_CLASS 2       /* useCats = 1, a detection against the ground truths of its class */
+typedef struct pa_ap_gt {
+    int32_t category;    /* index 0 .. n_classes - 1 */
+    int32_t iscrowd;
+    double area;         /* the annotation's own number, which decides the area ranges; < 0 = the pixel count of the mask */
+} pa_ap_gt;
+typedef struct pa_ap_job {
+    const void* det_masks;      /* uint32 [d_cap][words] in pa_inst_decode's bit layout (pixel p = bit p % 32 of word p / 32), words = ceil(h w / 32) */
+    const void* det_scores;     /* float32 [d_cap] */
+    const void* det_classes;    /* int32 [d_cap], or NULL: every class is 0 (agnostic only) */
+    const void* det_count;      /* DEVICE int32 [1]: the number of detections D, clamped to 0 .. d_cap */
+    const void* gt_masks;       /* uint32 [n_gt][words] */
+    const void* gt_table;       /* pa_ap_gt [n_gt] */
+    int32_t h, w;               /* a job with h < 1, w < 1 or h * w >= 2^31 has neither detections nor ground truths */
+    int32_t n_gt;               /* G, clamped to 0 .. the call's g_cap */
+    int32_t d_cap;              /* rows the job's detection buffers hold; the call's d_cap bounds it once more */
+    int32_t empty_as_one;       /* != 0: with D == 0 the job emits the reference's single empty detection (score 0, area 0, class 0) */
+    int32_t reserved;
+} pa_ap_job;
+typedef struct pa_ap_record {
+    float score;
+    int32_t area;               /* the pixels of its mask */
+    int32_t category;
+    int32_t index;              /* its row in the job's detection buffers */
+    uint64_t matched[2];        /* [0] agnostic, [1] per class: bit a * n_thrs + t = matched in area range a at threshold t */
+    uint64_t ignored[2];        /* likewise: matched to an ignored ground truth, or unmatched with an area outside the range */
+} pa_ap_record;
+/* host only: bytes of pa_ap_add's workspace (per job a uint32 matrix d_cap x g_cap, 40 bytes per detection slot, 4 per ground-truth slot),
+ * -1 for n_jobs outside 1 .. 65535 or capacities outside 1 .. 128. */
+int64_t pa_ap_workspace_bytes(int n_jobs, int d_cap, int g_cap);
+/* host only: where a section of that workspace starts; which = 0 the intersections uint32 [n_jobs][d_cap][g_cap], 1 the detections' pixel
+ * counts uint32 [n_jobs][d_cap], 2 the ground truths' pixel counts uint32 [n_jobs][g_cap], 3 the sorted order int32 [n_jobs][d_cap]
+ * (rank -> row), 4 the bit words uint64 [n_jobs][4][d_cap] (matched agnostic, matched per class, ignored agnostic, ignored per class, by
+ * rank); -1 for bad arguments. */
+int64_t pa_ap_workspace_offset(int n_jobs, int d_cap, int g_cap, int which);
+/* Per job: detections in stable order of descending score (ties to the lower row).  I[d][g] = common pixels, area(d) and pixels(g) the
+ * pixel counts (padding bits of a last word never count).  iou[d][g] = 0.0 where I = 0, else (double)I / (double)U, U = area(d) for a crowd
+ * ground truth, else area(d) + pixels(g) - I.  For every area range a = (lo, hi) of area_ranges_f64 (DEVICE double [n_ranges][2]): a
+ * ground truth is ignored when it is crowd or its area (pa_ap_gt.area) is < lo or > hi; the ground truths are walked with the ignored
+ * ones last, otherwise in table order.  For every threshold t of iou_thrs_f64 (DEVICE double [n_thrs]) and every detection in order:
+ * best = min(t, 1 - 1e-10), m = none; a ground truth already matched at t that is not crowd is skipped; the walk ends when m is a
+ * non-ignored one and an ignored one comes up; one with iou < best is skipped; otherwise best = iou, m = it.  With m: matched, ignored =
+ * m's flag, m is taken.  Without: ignored = area(d) < lo or > hi.  PA_AP_PER_CLASS does the same among the detections and ground truths
+ * of each class.  records: pa_ap_record [n_jobs][d_cap], the first record_counts[j] (int32 [n_jobs], written) of job j are written, in
+ * sorted order; cutting to maxDets is the host's (a prefix of the order is matched as it would be alone).
+ * flags_u32: uint32 [n_jobs], written.  A job with a non-zero flag word emits nothing: bit 0 a NaN score, 1 a detection class outside
+ * [0, n_classes) while PA_AP_PER_CLASS is asked for, 2 a ground-truth class outside that range.
+ * max_words: the largest ceil(h w / 32) of the table, 1 .. 2^26 (it sizes the grid only).  1 <= d_cap, g_cap <= 128, n_ranges * n_thrs
+ * <= 64, 1 <= n_classes <= 1024, modes 1 .. 3.  workspace: pa_ap_workspace_bytes, 16-byte aligned; the job table, thresholds, ranges and
+ * records 8-byte aligned.  Null pointers, sizes outside the ranges named here or misaligned buffers return hipErrorInvalidValue before
+ * anything is enqueued.  One clear and three launches on `stream`; integer atomics only, so two runs give the same bytes. */
+int pa_ap_add(const pa_ap_job* jobs, int n_jobs, int64_t max_words, int d_cap, int g_cap, int n_classes, int modes, const double* iou_thrs_f64,
+              int n_thrs, const double* area_ranges_f64, int n_ranges, pa_ap_record* records, void* record_counts, void* flags_u32,
+              void* workspace, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,12 @@ of panopticapi's pq_compute_single_core, read from the panoptic decode's device-
 per category back for a whole data set (tests/painter_pq_host.py is the definition; restated from panopticapi's published source and
 unverified against panopticapi).
 
+`InstanceAP` and `run_instance_ap` score decoded instances against COCO instance annotations (csrc/painter_ap.hip): COCOeval's mask
+IoUs and its greedy matching per (mode, area range, threshold) on bit masks, read from the instance decode's device-resident masks,
+scores and count and the panoptic decode's classes -- 48 bytes per detection back; accumulate / summarize run on the host
+(`instance_ap_metrics`; tests/painter_ap_host.py is the definition; restated from pycocotools' published source and unverified against
+pycocotools).
+
 Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
 (`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
 `cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
@@ -54,7 +60,7 @@ evaluators what is left after the colour -> class decode (`class_map`), the conf
 (`instances`) and the panoptic merge (`panoptic`): the boundary-IoU branch (`_compute_boundary_iou`, cv2 erosion), `encode_json_sem_seg`
 and its RLE, the final ratios of `evaluate` (`SemsegScore.scores` restates them on the host); of the depth evaluation its KITTI branches
 (`do_kb_crop`, `garg_crop`) and the division of the sums;
-PNG encoding, RLE and COCOeval; of the pose route mmpose's OKS NMS, rescoring and COCOeval, and the 34 numbers per box of `to_image`.
+PNG encoding, RLE and COCOeval's box AP (mask AP: `InstanceAP`); of the pose route mmpose's OKS NMS, rescoring and COCOeval, and the 34 numbers per box of `to_image`.
 
 One host path serves the routes: `_device` / `_pictures` put the inputs of a call on one indexed CUDA device; INSTANCE_DEFAULTS,
 MERGE_DEFAULTS, POSE_DEFAULTS and DEPTH_DEFAULTS hold the keyword defaults and `_check_arguments` refuses the rest before a forward is enqueued; an output
@@ -1248,6 +1254,336 @@ def run_panoptic_quality(semseg_engine, inst_engine, pictures, gts, gt_segments,
 
     with _eval_mode(inst_engine.model):
         semseg_engine._run(list(zip(pictures, gts, gt_segments)), sizes, batch)
+    return score
+
+
+# ---- COCO instance mask AP (csrc/painter_ap.hip)
+class ApJob(ctypes.Structure):
+    """pa_ap_job of include/painter_hip.h."""
+    _fields_ = [("det_masks", ctypes.c_void_p), ("det_scores", ctypes.c_void_p), ("det_classes", ctypes.c_void_p),
+                ("det_count", ctypes.c_void_p), ("gt_masks", ctypes.c_void_p), ("gt_table", ctypes.c_void_p), ("h", ctypes.c_int32),
+                ("w", ctypes.c_int32), ("n_gt", ctypes.c_int32), ("d_cap", ctypes.c_int32), ("empty_as_one", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+AP_GT = np.dtype([("category", np.int32), ("iscrowd", np.int32), ("area", np.float64)])        # pa_ap_gt of include/painter_hip.h
+AP_RECORD = np.dtype([("score", np.float32), ("area", np.int32), ("category", np.int32), ("index", np.int32), ("matched", np.uint64, (2,)),
+                      ("ignored", np.uint64, (2,))])                                             # pa_ap_record
+AP_MODES = ("agnostic", "per_class")                                                             # COCOeval's useCats = 0 / 1; bit i of `modes`
+AP_MAX_DET = AP_MAX_GT = 128                                                                     # pa_ap_add's capacities
+AP_AREA_RANGES = ((0, 1e10), (0, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e10))                  # COCOeval's all / small / medium / large
+AP_FLAGS = ("a NaN score", "a detection class outside the %d classes", "a ground-truth class outside the %d classes")
+
+
+def _ap_mean(x):
+    x = x[x > -1]
+    return float(np.mean(x)) if x.size else -1.0
+
+
+def instance_ap_metrics(records, gt_annotations, n_classes=80, mode="agnostic", iou_thrs=None, rec_thrs=None, max_dets=(1, 10, 100),
+                        area_ranges=None):
+    """COCOeval.accumulate and .summarize (iouType "segm") on the records of `InstanceAP.records()`, on the host in float64.  records: per
+    picture its AP_RECORDs in sorted order; gt_annotations: per picture dicts(category_id = class index, iscrowd, area = a number) -- the
+    ground truths' ignore flags and their count depend on the annotations alone.  Per class (one pseudo-class in "agnostic" mode), area
+    range and m of max_dets: every picture's records (of the class) cut to the first m, concatenated in picture order, stable-sorted by
+    descending score; tp / fp = running counts of matched / unmatched records that are not ignored; recall = tp / npig, precision = tp /
+    (fp + tp + np.spacing(1)) made monotone from the right and read at the first position whose recall reaches each of rec_thrs.  ->
+    dict(AP, AP50, AP75, APs, APm, APl at max_dets[-1]; AR<m> per m; ARs, ARm, ARl; precision [T][R][K][A][M], recall [T][K][A][M], -1 where
+    no ground truth counts; `per_class` AP in "per_class" mode).  Means are over the entries > -1, -1.0 without any.  Restated from
+    pycocotools' published source; pycocotools is not available where this project is tested, so it is unverified against pycocotools."""
+    iou_thrs = np.linspace(.5, .95, 10) if iou_thrs is None else np.asarray(iou_thrs, np.float64)
+    rec_thrs = np.linspace(0, 1, 101) if rec_thrs is None else np.asarray(rec_thrs, np.float64)
+    area_ranges = AP_AREA_RANGES if area_ranges is None else area_ranges
+    mi = AP_MODES.index(mode)
+    T, R, A, M = len(iou_thrs), len(rec_thrs), len(area_ranges), len(max_dets)
+    K = int(n_classes) if mode == "per_class" else 1
+    precision, recall = -np.ones((T, R, K, A, M)), -np.ones((T, K, A, M))
+    gcls = [np.array([int(g["category_id"]) for g in anns], np.int64) for anns in gt_annotations]
+    crowd = [np.array([bool(g.get("iscrowd", 0)) for g in anns], bool) for anns in gt_annotations]
+    area = [np.array([float(g["area"]) for g in anns], np.float64) for anns in gt_annotations]
+    for k in range(K):
+        recs = [r[r["category"] == k] for r in records] if mode == "per_class" else list(records)
+        mine = [c == k for c in gcls] if mode == "per_class" else [np.ones(len(c), bool) for c in gcls]
+        for a, (lo, hi) in enumerate(area_ranges):
+            npig = sum(int((m & ~(c | (v < lo) | (v > hi))).sum()) for m, c, v in zip(mine, crowd, area))
+            if npig == 0:
+                continue
+            for m, max_det in enumerate(max_dets):
+                cut = [r[:max_det] for r in recs]
+                scores = np.concatenate([r["score"] for r in cut]) if cut else np.zeros(0, np.float32)
+                order = np.argsort(-scores, kind="mergesort")
+                shift = np.arange(a * T, a * T + T, dtype=np.uint64)[:, None]
+                word = lambda name: np.concatenate([r[name][:, mi] for r in cut])[order] if cut else np.zeros(0, np.uint64)
+                dtm, ign = (word("matched")[None] >> shift) & np.uint64(1) != 0, (word("ignored")[None] >> shift) & np.uint64(1) != 0
+                tp = np.cumsum(dtm & ~ign, axis=1).astype(np.float64)
+                fp = np.cumsum(~dtm & ~ign, axis=1).astype(np.float64)
+                nd = tp.shape[1]
+                for t in range(T):
+                    rc = tp[t] / npig
+                    pr = tp[t] / (fp[t] + tp[t] + np.spacing(1))
+                    recall[t, k, a, m] = rc[-1] if nd else 0
+                    pr = np.maximum.accumulate(pr[::-1])[::-1]
+                    at = np.searchsorted(rc, rec_thrs, side="left")
+                    q = np.zeros(R)
+                    q[at < nd] = pr[at[at < nd]]
+                    precision[t, :, k, a, m] = q
+    at = lambda v: np.flatnonzero(iou_thrs == v)
+    res = dict(AP=_ap_mean(precision[:, :, :, 0, -1]), AP50=_ap_mean(precision[at(.5), :, :, 0, -1]),
+               AP75=_ap_mean(precision[at(.75), :, :, 0, -1]))
+    for a, name in enumerate("sml", 1):
+        res["AP" + name] = _ap_mean(precision[:, :, :, a, -1]) if a < A else -1.0
+    for m, max_det in enumerate(max_dets):
+        res["AR%d" % max_det] = _ap_mean(recall[:, :, 0, m])
+    for a, name in enumerate("sml", 1):
+        res["AR" + name] = _ap_mean(recall[:, :, a, -1]) if a < A else -1.0
+    res.update(precision=precision, recall=recall)
+    if mode == "per_class":
+        res["per_class"] = [_ap_mean(precision[:, :, k, 0, -1]) for k in range(K)]
+    return res
+
+
+class InstanceAP:
+    """COCO instance mask AP of a data set (pa_ap_add, csrc/painter_ap.hip): COCOeval's computeIoU and evaluateImg per picture on the
+    device -- intersections of bit masks, the IoU doubles, the greedy matching per (mode, area range, threshold) -- and its accumulate /
+    summarize on the host (`instance_ap_metrics`).  Per `add` one clear and three launches for the whole list; nothing is copied back
+    before `records()` / `result()`: 48 bytes per detection slot, 4 per ground-truth slot and two words per picture.
+    tests/painter_ap_host.py is the definition; it is restated from pycocotools' published source and unverified against pycocotools.
+
+    modes: "agnostic" (useCats = 0, COCOCAInstSegEvaluatorCustom.py:404-414) and / or "per_class" (useCats = 1,
+    COCOInstSegEvaluatorCustom.py:315-329).  Classes are indices 0 .. n_classes - 1; categories = [ids] (or dicts with `id`) names the data
+    set's own ids instead: `category_id`s and classes handed to `add` are mapped through it on the host (an id it does not hold refuses
+    the picture), the classes of `add_decodes` come from the device and stay indices.  At most 128 detections and 128 ground truths per
+    picture, len(area_ranges) * len(iou_thrs) <= 64.  Polygon / RLE decoding, box AP, the class-wise re-NMS route and JSON I/O are not here."""
+
+    def __init__(self, n_classes=80, modes=("agnostic",), iou_thrs=None, area_ranges=None, max_dets=(1, 10, 100), categories=None,
+                 device="cuda"):
+        self.device = _device((), device)
+        self.index = None
+        if categories is not None:
+            labels = [c["id"] if isinstance(c, dict) else c for c in categories]
+            n_classes, self.index = len(labels), {label: i for i, label in enumerate(labels)}
+            assert len(self.index) == n_classes, "InstanceAP: a category id is listed twice"
+        self.labels = list(range(int(n_classes))) if categories is None else labels
+        self.k = int(n_classes)
+        self.modes = tuple(modes)
+        if not self.modes or any(m not in AP_MODES for m in self.modes):
+            raise ValueError("InstanceAP: modes %r (of %s)" % (modes, ", ".join(AP_MODES)))
+        self.iou_thrs = np.linspace(.5, .95, 10) if iou_thrs is None else np.array(iou_thrs, np.float64).ravel()
+        self.area_ranges = np.array(AP_AREA_RANGES if area_ranges is None else area_ranges, np.float64).reshape(-1, 2)
+        self.max_dets = tuple(int(m) for m in max_dets)
+        if not 1 <= self.k <= 1024 or not 1 <= len(self.iou_thrs) * len(self.area_ranges) <= 64 or not self.max_dets:
+            raise ValueError("InstanceAP: %d classes (1 .. 1024), %d thresholds x %d area ranges (at most 64 together)"
+                             % (self.k, len(self.iou_thrs), len(self.area_ranges)))
+        self.min_caps = (1, 1)                               # capacities (d_cap, g_cap) a call has at least (tests, measurements)
+        self.params = torch.from_numpy(np.concatenate([self.iou_thrs, self.area_ranges.ravel()])).to(self.device)
+        self.reset()
+
+    def reset(self):
+        self._outs, self._annotations, self._last, self._records = [], [], None, None
+
+    def _category(self, c):
+        return int(c) if self.index is None else self.index.get(c, -1)
+
+    def _add(self, dets, gt_masks, gt_annotations, keep):
+        """dets: per picture (h, w, capacity of its buffers, addresses of bit masks / scores / classes / count on the device or None,
+        host scores, host classes or None, empty_as_one).  Tables, host scores, counts and the job table go up in ONE pinned copy."""
+        n = len(dets)
+        if not (n == len(gt_masks) == len(gt_annotations)):
+            raise ValueError("InstanceAP: %d pictures of detections, %d of ground-truth masks, %d annotation lists" % (n, len(gt_masks), len(gt_annotations)))
+        if n == 0:
+            return self
+        if _device([list(gt_masks)], self.device) != self.device:
+            raise RuntimeError("painter_engine: this InstanceAP lives on %s" % self.device)
+        gbits, tables = [], []
+        for i, (d, g, anns) in enumerate(zip(dets, gt_masks, gt_annotations)):
+            if not torch.is_tensor(g):
+                g = np.asarray(g)
+            if g.ndim == 3 and len(g) and tuple(g.shape[1:]) != (d[0], d[1]):
+                raise ValueError("InstanceAP: the detections of picture %d are %s, its ground truth %s" % (i, (d[0], d[1]), tuple(g.shape[1:])))
+            if len(g) == 0:
+                g = np.zeros((0, d[0], d[1]), bool)
+            bits, n_gt = _bit_masks(g, d[0], d[1], self.device)
+            if n_gt != len(anns):
+                raise ValueError("InstanceAP: picture %d has %d ground-truth masks and %d annotations" % (i, n_gt, len(anns)))
+            t = np.zeros(n_gt, AP_GT)
+            for j, a in enumerate(anns):
+                t[j] = (self._category(a["category_id"]), int(bool(a.get("iscrowd", 0))), -1.0 if a.get("area") is None else float(a["area"]))
+            gbits.append(bits)
+            tables.append(t)
+        d_cap = max([self.min_caps[0]] + [d[2] for d in dets])
+        g_cap = max([self.min_caps[1]] + [len(t) for t in tables])
+        if d_cap > AP_MAX_DET or g_cap > AP_MAX_GT:
+            raise ValueError("InstanceAP: %d detections / %d ground truths in a picture (at most %d / %d)" % (d_cap, g_cap, AP_MAX_DET, AP_MAX_GT))
+        sections = [("jobs", np.uint8, ctypes.sizeof(ApJob) * n, 16)]
+        for i, (d, t) in enumerate(zip(dets, tables)):
+            own = d[3] is None                               # scores, classes and count come from the host
+            sections += [("gt%d" % i, AP_GT, len(t), 8), ("scores%d" % i, np.float32, d[2] if own else 0, 4),
+                         ("classes%d" % i, np.int32, d[2] if own and d[5] is not None else 0, 4), ("count%d" % i, np.int32, int(own), 4)]
+        at, size = _layout(sections)
+        host = torch.zeros(size, dtype=torch.uint8).pin_memory()
+        dev = torch.empty(size, dtype=torch.uint8, device=self.device)
+        a, base = host.numpy(), dev.data_ptr()
+        jobs = (ApJob * n)()
+        for i, (job, d, g, t) in enumerate(zip(jobs, dets, gbits, tables)):
+            _section(a, at, "gt%d" % i)[:] = t
+            job.h, job.w, job.d_cap, job.empty_as_one = d[0], d[1], d[2], int(d[6])
+            job.gt_masks, job.gt_table, job.n_gt = g.data_ptr(), base + at["gt%d" % i][0], len(t)
+            if d[3] is not None:
+                job.det_masks, job.det_scores, job.det_classes, job.det_count = d[3]
+            else:
+                count = len(d[4])
+                _section(a, at, "scores%d" % i)[:count] = d[4]
+                _section(a, at, "count%d" % i)[:] = count
+                job.det_masks, job.det_scores, job.det_count = d[7].data_ptr(), base + at["scores%d" % i][0], base + at["count%d" % i][0]
+                if d[5] is not None:
+                    _section(a, at, "classes%d" % i)[:count] = d[5]
+                    job.det_classes = base + at["classes%d" % i][0]
+        _section(a, at, "jobs")[:] = np.frombuffer(bytearray(jobs), np.uint8)
+        dev.copy_(host, non_blocking=True)
+        shape = (n, d_cap, g_cap)
+        nbytes = lib.pa_ap_workspace_bytes(*shape)
+        if nbytes < 0:
+            check(1, "pa_ap_add (sizes %s)" % (shape,))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        oat, osize = _layout([("records", AP_RECORD, n * d_cap, 8), ("counts", np.int32, n, 4), ("flags", np.uint32, n, 4),
+                              ("gpix", np.uint32, n * g_cap, 4)])
+        out = torch.zeros(osize, dtype=torch.uint8, device=self.device)
+        ptr = lambda name: out.data_ptr() + oat[name][0]
+        modes = sum(1 << AP_MODES.index(m) for m in set(self.modes))
+        T, A = len(self.iou_thrs), len(self.area_ranges)
+        check(lib.pa_ap_add(base + at["jobs"][0], n, max((d[0] * d[1] + 31) // 32 for d in dets), d_cap, g_cap, self.k, modes,
+                            self.params.data_ptr(), T, self.params.data_ptr() + 8 * T, A, ptr("records"), ptr("counts"), ptr("flags"),
+                            workspace.data_ptr(), _stream()), "pa_ap_add (sizes %s)" % (shape,))
+        off = lib.pa_ap_workspace_offset(*shape, 2)
+        out[oat["gpix"][0]:oat["gpix"][0] + 4 * n * g_cap].copy_(workspace[off:off + 4 * n * g_cap])       # the areas of `area: None`
+        self._outs.append((out, oat, shape))
+        self._annotations += [[dict(category_id=int(r["category"]), iscrowd=int(r["iscrowd"]), area=float(r["area"])) for r in t] for t in tables]
+        self._last = (keep, gbits, host, dev, workspace)     # what the enqueued launches read, until the next call
+        self._records = None
+        return self
+
+    def add(self, masks, scores, classes, gt_masks, gt_annotations, sizes=None):
+        """Lists with one entry per picture.  masks: bool / uint8 [n][H][W] (numpy or CUDA tensor) or uint32 bit masks [n][ceil(H W / 32)]
+        (then the size is that of the ground-truth masks, or sizes[i] = (H, W) where both sides are bit masks); scores: [n]; classes: [n] or None (class 0, "agnostic" only); classes may also
+        be None as a whole.  gt_masks: likewise [G][H][W]; gt_annotations: per picture dicts(category_id, iscrowd, area; area None = the
+        mask's pixel count).  Detections are taken as they are handed over: a picture without any has none (the reference's single empty
+        detection is what `instances` returns for such a picture).  Nothing is copied back.  -> self."""
+        masks, scores, gt_masks, gt_annotations = list(masks), list(scores), list(gt_masks), list(gt_annotations)
+        classes = [None] * len(masks) if classes is None else list(classes)
+        if not (len(masks) == len(scores) == len(classes)):
+            raise ValueError("InstanceAP.add: %d mask lists, %d score lists, %d class lists" % (len(masks), len(scores), len(classes)))
+        if len(masks) != len(gt_masks):
+            raise ValueError("InstanceAP.add: %d pictures of detections, %d of ground-truth masks" % (len(masks), len(gt_masks)))
+        if _device([masks], self.device) != self.device:
+            raise RuntimeError("painter_engine: this InstanceAP lives on %s" % self.device)
+        dets = []
+        for i, (m, s, c, g) in enumerate(zip(masks, scores, classes, gt_masks)):
+            if c is None and "per_class" in self.modes:
+                raise ValueError("InstanceAP.add: picture %d has no classes, which mode \"per_class\" needs" % i)
+            shape = next((tuple(int(v) for v in x.shape[1:]) for x in (m, g) if hasattr(x, "shape") and len(x.shape) == 3), None)
+            shape = shape if sizes is None else (int(sizes[i][0]), int(sizes[i][1]))
+            if shape is None:
+                raise ValueError("InstanceAP.add: picture %d gives bit masks on both sides, so its size is unknown" % i)
+            if not torch.is_tensor(m) and len(m) == 0:
+                m = np.zeros((0,) + shape, bool)
+            bits, count = _bit_masks(m, shape[0], shape[1], self.device)
+            s = _host_array(s, np.float32)
+            c = None if c is None else np.array([self._category(v) for v in _host_array(c, np.int64).tolist()], np.int32)
+            if len(s) != count or (c is not None and len(c) != count):
+                raise ValueError("InstanceAP.add: picture %d has %d masks, %d scores, %s classes" % (i, count, len(s), "no" if c is None else len(c)))
+            dets.append((shape[0], shape[1], int(bits.shape[0]), None, s, c, False, bits))
+        return self._add(dets, gt_masks, gt_annotations, [d[7] for d in dets])
+
+    def add_decodes(self, decodes, gt_masks, gt_annotations):
+        """decodes: launched InstanceDecodes (classes null: "agnostic" only) or PanopticDecodes built on one (`_launch_panoptic` with the
+        painted instance picture; the classes are those its vote wrote).  Bit masks, scores and count are read where the decode left them;
+        a decode whose count is 0 scores as the reference's single empty detection.  The decode's own `result()` is untouched.  -> self."""
+        dets, decodes = [], list(decodes)
+        for i, d in enumerate(decodes):
+            inst = d if isinstance(d, InstanceDecode) else getattr(d, "decode", None)
+            if inst is None:
+                raise TypeError("InstanceAP.add_decodes: entry %d is neither an InstanceDecode nor a PanopticDecode chained behind one" % i)
+            if inst.out.device != self.device:
+                raise RuntimeError("painter_engine: this InstanceAP lives on %s" % self.device)
+            if inst is d and "per_class" in self.modes:
+                raise ValueError("InstanceAP.add_decodes: an InstanceDecode has no classes, which mode \"per_class\" needs")
+            base = inst.out.data_ptr()
+            classes = None if inst is d else d.out.data_ptr() + d.at["classes"][0]
+            dets.append((inst.h, inst.w, inst.max_num, (base + inst.obits, base + inst.o32, classes, base + inst.at["count"][0]), None, None, True))
+        return self._add(dets, list(gt_masks), list(gt_annotations), decodes)
+
+    def records(self):
+        """The one copy back (and synchronisation) -> per picture its AP_RECORDs in sorted order (numpy).  ValueError names the first
+        refused picture (counted over all `add` calls since `reset`) and why."""
+        if self._records is None:
+            a = torch.cat([o for o, _, _ in self._outs]).cpu().numpy() if self._outs else np.zeros(0, np.uint8)
+            recs, flags, areas, base = [], [], [], 0
+            for out, oat, (n, d_cap, g_cap) in self._outs:
+                part = a[base:base + out.numel()]
+                base += out.numel()
+                table, counts = _section(part, oat, "records").reshape(n, d_cap), _section(part, oat, "counts")
+                recs += [table[i, :counts[i]].copy() for i in range(n)]
+                flags += _section(part, oat, "flags").tolist()
+                areas += [row for row in _section(part, oat, "gpix").reshape(n, g_cap)]
+            bad = np.flatnonzero(flags)
+            if len(bad):
+                word = int(flags[bad[0]])
+                bit = (word & -word).bit_length() - 1
+                why = AP_FLAGS[bit] % self.k if "%d" in AP_FLAGS[bit] else AP_FLAGS[bit]
+                raise ValueError("InstanceAP: picture %d is refused (flag bit %d, flags 0x%02x): %s; %d of %d pictures are refused and emit "
+                                 "nothing" % (bad[0], bit, word, why, len(bad), len(flags)))
+            anns = [[dict(g, area=float(pix[j])) if g["area"] < 0 else g for j, g in enumerate(p)] for p, pix in zip(self._annotations, areas)]
+            self._records = (recs, anns)
+        return self._records[0]
+
+    def result(self):
+        """`instance_ap_metrics` of `records()` per mode -> {mode: dict(AP, AP50, AP75, APs, APm, APl, AR<m>..., ARs, ARm, ARl, precision,
+        recall[, per_class])} -- accumulate and summarize on the host; COCOeval's formulas restated, unverified against pycocotools."""
+        recs = self.records()
+        return {mode: instance_ap_metrics(recs, self._records[1], self.k, mode, self.iou_thrs, None, self.max_dets,
+                                          [tuple(r) for r in self.area_ranges.tolist()]) for mode in self.modes}
+
+
+def run_instance_ap(inst_engine, pictures, gt_masks, gt_annotations, score, sizes=None, semseg_engine=None, **kw):
+    """`run_instances`' loop ending in `score.add_decodes` (an InstanceAP) instead of `result()`: forward, instance decode and scoring are
+    chained per batch, the masks are never copied back and nothing else is before `score.records()` / `score.result()`.  With
+    `semseg_engine` (task coco_pano_semseg) the loop is `run_panoptic`'s: every instance gets the class the panoptic decode's vote gives it
+    and "per_class" is allowed.  gt_masks, gt_annotations: per picture (see InstanceAP.add), of the painted picture's size (sizes[i],
+    default the query's own).  -> score."""
+    if inst_engine.task != "coco_pano_inst" or (semseg_engine is not None and semseg_engine.task != "coco_pano_semseg"):
+        raise ValueError("painter_engine: run_instance_ap takes a coco_pano_inst engine and, optionally, a coco_pano_semseg engine, not %r and %r"
+                         % (inst_engine.task, None if semseg_engine is None else semseg_engine.task))
+    if semseg_engine is None and "per_class" in score.modes:
+        raise ValueError("painter_engine: run_instance_ap scores mode \"per_class\" only with a semseg_engine, which gives the instances their classes")
+    kw = {k: v for k, v in kw.items() if k != "device"}
+    if semseg_engine is None:
+        _check_arguments("run_instance_ap", kw, INSTANCE_DEFAULTS)               # before the first forward is enqueued
+        args = dict(INSTANCE_DEFAULTS, **kw)
+    else:
+        _check_arguments("run_instance_ap", kw, INSTANCE_DEFAULTS, MERGE_DEFAULTS)
+        merge = {k: kw.pop(k, v) for k, v in MERGE_DEFAULTS.items()}             # kw keeps what belongs to the instance decode
+        palette, n_things = merge.pop("semseg_palette"), merge.pop("n_things")
+    pictures, gt_masks, gt_annotations = list(pictures), list(gt_masks), list(gt_annotations)
+    sizes = [(p.shape[1], p.shape[0]) for p in pictures] if sizes is None else [(int(w), int(h)) for w, h in sizes]
+    if not (len(pictures) == len(gt_masks) == len(gt_annotations) == len(sizes)):
+        raise ValueError("run_instance_ap: %d pictures, %d lists of ground-truth masks, %d annotation lists, %d sizes"
+                         % (len(pictures), len(gt_masks), len(gt_annotations), len(sizes)))
+
+    def batch(items, sizes):
+        pics, step = [p for p, _, _ in items], inst_engine.batch_size
+        sem = None if semseg_engine is None else semseg_engine._launch_batch(pics, sizes, False)
+        jobs = []
+        for j in range(0, len(pics), step):
+            inst = inst_engine._launch_batch(pics[j:j + step], sizes[j:j + step], False)
+            if sem is None:
+                jobs += [InstanceDecode(inst.picture(i), *args.values()) for i in range(inst.n_jobs)]
+            else:
+                jobs += [_launch_panoptic(sem.picture(j + i), inst.picture(i), None, palette, n_things, merge, kw) for i in range(inst.n_jobs)]
+        score.add_decodes(jobs, [g for _, g, _ in items], [a for _, _, a in items])
+
+    first = inst_engine if semseg_engine is None else semseg_engine
+    with _eval_mode(inst_engine.model):
+        first._run(list(zip(pictures, gt_masks, gt_annotations)), sizes, batch)
     return score
 
 
