@@ -774,6 +774,70 @@ int pa_ap_add(const pa_ap_job* jobs, int n_jobs, int64_t max_words, int d_cap, i
               int n_thrs, const double* area_ranges_f64, int n_ranges, pa_ap_record* records, void* record_counts, void* flags_u32,
               void* workspace, hipStream_t stream);
 
+/* COCO keypoint AP up to the per-detection match flags, csrc/painter_kpt.hip: what TopDownCocoDatasetCustom.evaluate
+ * (mmpose_custom/data/topdown_coco_dataset.py:194-315) does after the decode -- photo coordinates, rescoring, OKS NMS -- and COCOeval's
+ * computeOks and evaluateImg (iouType "keypoints") per photo.  mmpose's oks_iou / oks_nms and xtcocotools' COCOeval are restated from
+ * their published source and unverified against mmpose / xtcocotools; tests/painter_kpt_host.py is the definition and states every
+ * operation.  Both entry points are stream-ordered, allocate nothing and never synchronise; null, misaligned or out-of-range arguments
+ * return hipErrorInvalidValue before anything is enqueued. */
+typedef struct pa_kpt_gt {
+    double area;              /* the annotation's own number: the OKS denominator and the area ranges */
+    double bbox[4];           /* x, y, w, h: the box-distance branch of a ground truth without a labelled keypoint */
+    int32_t iscrowd;
+    int32_t num_keypoints;    /* 0: ignored */
+} pa_kpt_gt;
+typedef struct pa_kpt_job {
+    const void* rows;         /* int32 [n_box]: rows of the pose table, de-duplicated and in ascending bbox_id */
+    const void* gt_keypoints; /* double [n_gt][n_keypoints][3] = x, y, v */
+    const void* gt_table;     /* pa_kpt_gt [n_gt] */
+    int32_t n_box;            /* D, clamped to 0 .. the call's d_cap */
+    int32_t n_gt;             /* G, clamped to 0 .. the call's g_cap */
+} pa_kpt_job;
+typedef struct pa_kpt_record {
+    float score;              /* the rescored score */
+    int32_t row;              /* its row in the pose table */
+    double area;              /* (max x - min x) * (max y - min y) of its keypoints, float64: loadRes' area */
+    uint64_t matched;         /* bit a * n_thrs + t = matched in area range a at threshold t */
+    uint64_t ignored;         /* likewise: matched to an ignored ground truth, or unmatched with an area outside the range */
+} pa_kpt_record;
+/* Per box, chained behind pa_pose_keypoints: preds float32 [n][n_keypoints][2] (8-byte aligned) and maxvals float32 [n][n_keypoints] are
+ * read where the decode left them; boxes_f32: DEVICE float32 [n][5] = center x, y, scale x, y (box size / 200), box score.
+ * out_poses float32 [n][n_keypoints][3] = (x, y, maxval) with x = float32(((double)p * (full / heat_w) + (double)cx) - full * 0.5), full =
+ * (double)sx * 200 (painter_engine.to_image, bit for bit), y likewise; out_scores float32 [n]: the float32 running sum of the maxvals >
+ * vis_thr in joint order, one float32 division by their count (0 without any), one float32 multiply by the box score; out_areas float32
+ * [n] = float32(sx * 200) * float32(sy * 200).  1 <= n <= 2^24, 1 <= n_keypoints <= 32, heat_w, heat_h >= 1.  One launch, one wave per
+ * box. */
+int pa_kpt_poses(const float* preds, const float* maxvals, const float* boxes_f32, int n, int n_keypoints, int heat_w, int heat_h,
+                 float vis_thr, float* out_poses, float* out_scores, float* out_areas, hipStream_t stream);
+/* host only: bytes of pa_kpt_evaluate's workspace (8 bytes per job and box slot, 8 per job, evaluated detection and ground-truth slot), -1
+ * for n_jobs outside 1 .. 65535, d_cap outside 1 .. 1024, g_cap outside 1 .. 128 or max_det outside 1 .. 64. */
+int64_t pa_kpt_workspace_bytes(int n_jobs, int d_cap, int g_cap, int max_det);
+/* host only: where a section of that workspace starts; which = 0 the NMS order int32 [n_jobs][d_cap] (rank -> position in the job's
+ * rows), 1 the survivor flags int32 [n_jobs][d_cap] by rank, 2 the evaluation OKS doubles [n_jobs][max_det][g_cap]; only the entries of a
+ * job's own boxes / evaluated detections and ground truths are written.  -1 for bad arguments. */
+int64_t pa_kpt_workspace_offset(int n_jobs, int d_cap, int g_cap, int max_det, int which);
+/* One workgroup per job (photo) over a DEVICE job table; poses / scores / areas: the pose table pa_kpt_poses wrote, n_rows rows.  Per job:
+ * the boxes in descending score, equal scores to the higher position (argsort(kind="stable")[::-1]); greedy OKS NMS: a surviving box i
+ * suppresses a later box j when float32(oks) > oks_thr, oks = (sum_k exp(-e_k)) / K over all K keypoints in ascending k, e_k =
+ * (double)d2_k / (2 sigma_k)^2 / den / 2, d2_k = dx^2 + dy^2 in float32, den = (double)float32((a_i + a_j) / 2) + 2^-52.  oks_thr < 0: no
+ * NMS, the order is descending score with equal scores to the LOWER position.  The first max_det survivors are evaluated in that order:
+ * area = (max x - min x)(max y - min y) of its keypoints; against ground truth g with k1 = #(v > 0): k1 > 0: e_k = (dx^2 + dy^2) / (2
+ * sigma_k)^2 / (area_g + 2^-52) / 2 over the keypoints with v > 0, oks = sum exp(-e_k) / k1; k1 == 0: dx = max(0, x0 - xd) + max(0, xd -
+ * x1) with x0 = bx - bw, x1 = bx + 2 bw (y likewise) over all K, divided by K; float64 throughout, no fused multiply-add.  A ground truth
+ * is ignored when iscrowd or num_keypoints == 0, per area range (area_ranges_f64, DEVICE double [n_ranges][2]) also when its area is < lo
+ * or > hi.  Matching per range and threshold (iou_thrs_f64, DEVICE double [n_thrs]) is pa_ap_add's: best = min(t, 1 - 1e-10), ignored
+ * ground truths last, a matched ground truth stays open only when it is crowd, an unmatched detection is ignored when its area is outside
+ * the range.  records: pa_kpt_record [n_jobs][max_det], the first record_counts[j] of job j written; survivor_counts[j]: how many boxes
+ * the NMS kept (both int32 [n_jobs], written).  flags_u32: uint32 [n_jobs], written; a job with a non-zero word emits nothing: bit 0 a NaN
+ * among its poses, scores or areas, 1 a ground truth whose area + 2^-52 is not a positive finite number, 2 a row outside the pose table.
+ * 1 <= d_cap <= 1024, 1 <= g_cap <= 128, 1 <= n_keypoints <= 32 (sigmas_f64: DEVICE double [n_keypoints]), n_ranges * n_thrs <= 64, 1 <=
+ * max_det <= 64, 1 <= n_jobs <= 65535, 1 <= n_rows <= 2^24.  workspace: pa_kpt_workspace_bytes, 16-byte aligned; tables of doubles and
+ * records 8-byte aligned.  One launch; no floating-point atomics, so two runs give the same bytes. */
+int pa_kpt_evaluate(const pa_kpt_job* jobs, int n_jobs, const float* poses, const float* scores, const float* areas, int n_rows, int d_cap,
+                    int g_cap, int n_keypoints, const double* sigmas_f64, float oks_thr, int max_det, const double* iou_thrs_f64, int n_thrs,
+                    const double* area_ranges_f64, int n_ranges, pa_kpt_record* records, void* record_counts, void* survivor_counts,
+                    void* flags_u32, void* workspace, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

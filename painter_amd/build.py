@@ -30,11 +30,13 @@ FLAGS = FLAGS + os.environ.get("PA_EXTRA_FLAGS", "").split()
 # painter_restore.hip: the float64 window moments and S are stated operation by operation, and a perfect prediction must give exactly 1
 # (tests/painter_restore_host.py).  painter_pq.hip: two float64 divisions feed the comparisons with 0.5 that panopticapi makes in Python
 # floats (tests/painter_pq_host.py).  painter_ap.hip: one float64 division per (detection, ground truth) feeds the comparisons with the
-# IoU thresholds that COCOeval makes in float64 (tests/painter_ap_host.py).
+# IoU thresholds that COCOeval makes in float64 (tests/painter_ap_host.py).  painter_kpt.hip: the photo coordinates equal
+# painter_engine.to_image bit for bit, and the float32 / float64 steps that feed exp in the two OKS forms are stated operation by operation
+# (tests/painter_kpt_host.py).
 EXTRA = {"seggpt_io.hip": ["-ffp-contract=off"], "pair_io.hip": ["-ffp-contract=off"], "painter_io.hip": ["-ffp-contract=off"],
          "painter_inst.hip": ["-ffp-contract=off"], "painter_pano.hip": ["-ffp-contract=off"], "painter_pose.hip": ["-ffp-contract=off"],
          "painter_score.hip": ["-ffp-contract=off"], "painter_restore.hip": ["-ffp-contract=off"], "painter_pq.hip": ["-ffp-contract=off"],
-         "painter_ap.hip": ["-ffp-contract=off"]}
+         "painter_ap.hip": ["-ffp-contract=off"], "painter_kpt.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

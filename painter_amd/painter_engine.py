@@ -51,6 +51,12 @@ scores and count and the panoptic decode's classes -- 48 bytes per detection bac
 (`instance_ap_metrics`; tests/painter_ap_host.py is the definition; restated from pycocotools' published source and unverified against
 pycocotools).
 
+`KeypointAP` and `PainterEngine.run_pose_ap` carry the keypoint decode to COCO keypoint AP (csrc/painter_kpt.hip): photo coordinates,
+rescoring and OKS NMS of TopDownCocoDatasetCustom.evaluate (mmpose_custom/data/topdown_coco_dataset.py:194-315) and COCOeval's computeOks /
+evaluateImg per photo, read from the pose decode's device-resident preds and maxvals -- 32 bytes per evaluated detection back; accumulate /
+summarize run on the host (`keypoint_ap_metrics`; tests/painter_kpt_host.py is the definition; mmpose's oks_nms and xtcocotools' COCOeval
+are restated from their published source and unverified against mmpose / xtcocotools).
+
 Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
 (`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
 `cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
@@ -60,7 +66,7 @@ evaluators what is left after the colour -> class decode (`class_map`), the conf
 (`instances`) and the panoptic merge (`panoptic`): the boundary-IoU branch (`_compute_boundary_iou`, cv2 erosion), `encode_json_sem_seg`
 and its RLE, the final ratios of `evaluate` (`SemsegScore.scores` restates them on the host); of the depth evaluation its KITTI branches
 (`do_kb_crop`, `garg_crop`) and the division of the sums;
-PNG encoding, RLE and COCOeval's box AP (mask AP: `InstanceAP`); of the pose route mmpose's OKS NMS, rescoring and COCOeval, and the 34 numbers per box of `to_image`.
+PNG encoding, RLE and COCOeval's box AP (mask AP: `InstanceAP`); of the pose route soft_oks_nms, rle_score and the JSON file (keypoint AP: `KeypointAP`).
 
 One host path serves the routes: `_device` / `_pictures` put the inputs of a call on one indexed CUDA device; INSTANCE_DEFAULTS,
 MERGE_DEFAULTS, POSE_DEFAULTS and DEPTH_DEFAULTS hold the keyword defaults and `_check_arguments` refuses the rest before a forward is enqueued; an output
@@ -1587,6 +1593,310 @@ def run_instance_ap(inst_engine, pictures, gt_masks, gt_annotations, score, size
     return score
 
 
+# ---- COCO keypoint AP (csrc/painter_kpt.hip)
+class KptJob(ctypes.Structure):
+    """pa_kpt_job of include/painter_hip.h."""
+    _fields_ = [("rows", ctypes.c_void_p), ("gt_keypoints", ctypes.c_void_p), ("gt_table", ctypes.c_void_p), ("n_box", ctypes.c_int32),
+                ("n_gt", ctypes.c_int32)]
+
+
+KPT_GT = np.dtype([("area", np.float64), ("bbox", np.float64, (4,)), ("iscrowd", np.int32), ("num_keypoints", np.int32)])      # pa_kpt_gt
+KPT_RECORD = np.dtype([("score", np.float32), ("row", np.int32), ("area", np.float64), ("matched", np.uint64), ("ignored", np.uint64)])
+# configs/_base_/coco.py:178-181
+COCO_SIGMAS = (0.026, 0.025, 0.025, 0.035, 0.035, 0.079, 0.079, 0.072, 0.072, 0.062, 0.062, 0.107, 0.107, 0.087, 0.087, 0.089, 0.089)
+KPT_AREA_RANGES = ((0, 1e10), (32 ** 2, 96 ** 2), (96 ** 2, 1e10))                    # COCOeval's all / medium / large for keypoints
+KPT_MAX_BOX, KPT_MAX_GT, KPT_MAX_EVAL, KPT_MAX_JOBS = 1024, 128, 64, 65535               # pa_kpt_evaluate's capacities
+KPT_FLAGS = ("a NaN among its poses, scores or box areas", "a ground truth whose area + 2^-52 is not a positive finite number",
+             "a row outside the pose table")
+
+
+def _kpt_ignore(g):
+    return bool(g.get("iscrowd", 0)) or int(g["num_keypoints"]) == 0
+
+
+def keypoint_ap_metrics(records, ground_truth, iou_thrs=None, rec_thrs=None, area_ranges=None, max_dets=(20,)):
+    """COCOeval.accumulate and .summarize (iouType "keypoints", the one category `person`) on the records of `KeypointAP.records()`, on
+    the host in float64.  records: {image id: KPT_RECORDs in evaluation order}; ground_truth: {image id: annotation dicts} -- the ground
+    truths' ignore flags (iscrowd, num_keypoints == 0, area outside the range) and their count depend on the annotations alone.  Photos in
+    ascending image id; the rest is `instance_ap_metrics`' arithmetic.  -> dict(AP, AP50, AP75, APm, APl, AR, AR50, AR75, ARm, ARl at
+    max_dets[-1]; precision [T][R][1][A][M], recall [T][1][A][M], -1 where no ground truth counts).  Means are over the entries > -1, -1.0
+    without any.  Restated from xtcocotools' published source; xtcocotools is not available where this project is tested, so it is
+    unverified against xtcocotools."""
+    iou_thrs = np.linspace(.5, .95, 10) if iou_thrs is None else np.asarray(iou_thrs, np.float64)
+    rec_thrs = np.linspace(0, 1, 101) if rec_thrs is None else np.asarray(rec_thrs, np.float64)
+    area_ranges = KPT_AREA_RANGES if area_ranges is None else area_ranges
+    T, R, A, M = len(iou_thrs), len(rec_thrs), len(area_ranges), len(max_dets)
+    precision, recall = -np.ones((T, R, 1, A, M)), -np.ones((T, 1, A, M))
+    images = sorted(ground_truth)
+    skip = [np.array([_kpt_ignore(g) for g in ground_truth[i]], bool) for i in images]
+    area = [np.array([float(g["area"]) for g in ground_truth[i]], np.float64) for i in images]
+    recs = [records[i] for i in images]
+    for a, (lo, hi) in enumerate(area_ranges):
+        npig = sum(int((~(s | (v < lo) | (v > hi))).sum()) for s, v in zip(skip, area))
+        if npig == 0:
+            continue
+        for m, max_det in enumerate(max_dets):
+            cut = [r[:max_det] for r in recs]
+            scores = np.concatenate([r["score"] for r in cut]) if cut else np.zeros(0, np.float32)
+            order = np.argsort(-scores, kind="mergesort")
+            shift = np.arange(a * T, a * T + T, dtype=np.uint64)[:, None]
+            word = lambda name: np.concatenate([r[name] for r in cut])[order] if cut else np.zeros(0, np.uint64)
+            dtm, ign = (word("matched")[None] >> shift) & np.uint64(1) != 0, (word("ignored")[None] >> shift) & np.uint64(1) != 0
+            tp = np.cumsum(dtm & ~ign, axis=1).astype(np.float64)
+            fp = np.cumsum(~dtm & ~ign, axis=1).astype(np.float64)
+            nd = tp.shape[1]
+            for t in range(T):
+                rc = tp[t] / npig
+                pr = tp[t] / (fp[t] + tp[t] + np.spacing(1))
+                recall[t, 0, a, m] = rc[-1] if nd else 0
+                pr = np.maximum.accumulate(pr[::-1])[::-1]
+                at = np.searchsorted(rc, rec_thrs, side="left")
+                q = np.zeros(R)
+                q[at < nd] = pr[at[at < nd]]
+                precision[t, :, 0, a, m] = q
+    at = lambda v: np.flatnonzero(iou_thrs == v)
+    res = {}
+    for name, table in (("AP", precision), ("AR", recall)):
+        res[name] = _ap_mean(table[..., 0, -1])
+        res[name + "50"] = _ap_mean(table[at(.5)][..., 0, -1])
+        res[name + "75"] = _ap_mean(table[at(.75)][..., 0, -1])
+        for a, size in enumerate("ml", 1):
+            res[name + size] = _ap_mean(table[..., a, -1]) if a < A else -1.0
+    res.update(precision=precision, recall=recall)
+    return res
+
+
+class KeypointAP:
+    """COCO keypoint AP of a data set (pa_kpt_poses, pa_kpt_evaluate; csrc/painter_kpt.hip): what TopDownCocoDatasetCustom.evaluate
+    (mmpose_custom/data/topdown_coco_dataset.py:194-315) does with the decoded boxes -- photo coordinates, rescoring, de-duplication, OKS NMS
+    per photo (configs/coco_256x192_test_offline.py:100-106) -- and COCOeval's computeOks and evaluateImg per photo on the device, its
+    accumulate / summarize on the host (`keypoint_ap_metrics`).  `add` / `add_decodes` launch pa_kpt_poses per chunk and keep the poses on
+    the device; nothing is copied back before `records()` / `result()`: 32 bytes per evaluated detection and three words per photo.
+    tests/painter_kpt_host.py is the definition; mmpose's oks_nms and xtcocotools' COCOeval are restated there from their published source,
+    unverified against mmpose / xtcocotools.
+
+    ground_truth: {image id: [COCO annotation dicts with keypoints (K * 3), area, bbox, iscrowd, num_keypoints]}; every photo of the data
+    set is listed, also one without a person.  The NMS order is descending score with equal scores to the higher bbox_id
+    (argsort(kind="stable")[::-1]); the reference's `scores.argsort()[::-1]` agrees up to 16 boxes per photo, above that numpy's default
+    sort leaves ties unspecified.  At most 1024 boxes and 128 ground truths per photo, K <= 32, len(area_ranges) * len(iou_thrs) <= 64,
+    max(max_dets) <= 64.  soft_nms, rle_score and the JSON file are not here."""
+
+    def __init__(self, ground_truth, sigmas=COCO_SIGMAS, vis_thr=0.2, oks_thr=0.9, use_nms=True, iou_thrs=None, area_ranges=None,
+                 max_dets=(20,), heatmap_size=(192, 256), device="cuda"):
+        self.device = _device((), device)
+        self.sigmas = np.array(sigmas, np.float64).ravel()
+        self.k = len(self.sigmas)
+        self.vis_thr, self.oks_thr, self.use_nms = float(vis_thr), float(oks_thr), bool(use_nms)
+        self.iou_thrs = np.linspace(.5, .95, 10) if iou_thrs is None else np.array(iou_thrs, np.float64).ravel()
+        self.area_ranges = np.array(KPT_AREA_RANGES if area_ranges is None else area_ranges, np.float64).reshape(-1, 2)
+        self.max_dets = tuple(int(m) for m in max_dets)
+        self.heatmap_size = (int(heatmap_size[0]), int(heatmap_size[1]))
+        if not 1 <= self.k <= 32 or not 1 <= len(self.iou_thrs) * len(self.area_ranges) <= 64 or not self.max_dets or \
+                not 1 <= max(self.max_dets) <= KPT_MAX_EVAL or min(self.heatmap_size) < 1 or not self.oks_thr >= 0:
+            raise ValueError("KeypointAP: %d keypoints (1 .. 32), %d thresholds x %d area ranges (at most 64 together), max_dets %s (1 .. %d), "
+                             "heat map %s, oks_thr %s (>= 0)" % (self.k, len(self.iou_thrs), len(self.area_ranges), self.max_dets, KPT_MAX_EVAL,
+                                                                self.heatmap_size, oks_thr))
+        self.ground_truth = {image: list(anns) for image, anns in ground_truth.items()}
+        self._gt = {}
+        for image, anns in self.ground_truth.items():
+            kp = np.array([g["keypoints"] for g in anns], np.float64).reshape(len(anns), self.k, 3)
+            table = np.zeros(len(anns), KPT_GT)
+            for j, g in enumerate(anns):
+                table[j] = (float(g["area"]), tuple(float(v) for v in g["bbox"]), int(bool(g.get("iscrowd", 0))), int(g["num_keypoints"]))
+            if len(anns) > KPT_MAX_GT:
+                raise ValueError("KeypointAP: photo %r has %d ground truths (at most %d)" % (image, len(anns), KPT_MAX_GT))
+            self._gt[image] = (kp, table)
+        self.min_caps = (1, 1)                               # capacities (d_cap, g_cap) a call has at least (tests, measurements)
+        self.params = torch.from_numpy(np.concatenate([self.sigmas, self.iou_thrs, self.area_ranges.ravel()])).to(self.device)
+        self.reset()
+
+    def reset(self):
+        """Forgets every box added so far."""
+        self._chunks, self._images, self._bbox_ids, self._records, self._last = [], [], [], None, None
+        return self
+
+    def _ids(self, n, image_ids, bbox_ids):
+        image_ids = list(image_ids)
+        bbox_ids = list(range(len(self._images), len(self._images) + n)) if bbox_ids is None else [int(b) for b in bbox_ids]
+        if not (len(image_ids) == len(bbox_ids) == n):
+            raise ValueError("KeypointAP: %d boxes, %d image ids, %d bbox ids" % (n, len(image_ids), len(bbox_ids)))
+        return image_ids, bbox_ids
+
+    def _boxes(self, n, centers, scales, box_scores):
+        c, s, b = (_host_array(x, np.float32) for x in (centers, scales, box_scores))
+        if c.size != 2 * n or s.size != 2 * n or b.size != n:
+            raise ValueError("KeypointAP: %d boxes, %d center values, %d scale values, %d box scores" % (n, c.size, s.size, b.size))
+        return np.concatenate([c.reshape(n, 2), s.reshape(n, 2), b[:, None]], 1)
+
+    def _launch(self, parts, boxes, image_ids, bbox_ids, keep):
+        """parts: [(address of preds, address of maxvals, boxes)] in the order of `boxes` (float32 [n][5], host).  One upload of the box
+        table, one pa_kpt_poses per part into ONE chunk: poses [n][K][3] | scores [n] | areas [n]."""
+        n, k = len(boxes), self.k
+        table = torch.from_numpy(np.ascontiguousarray(boxes)).pin_memory().to(self.device, non_blocking=True)
+        chunk = torch.empty(n * (3 * k + 2), dtype=torch.float32, device=self.device)
+        base, first = chunk.data_ptr(), 0
+        for preds, maxvals, count in parts:
+            check(lib.pa_kpt_poses(preds, maxvals, table.data_ptr() + 20 * first, count, k, self.heatmap_size[0], self.heatmap_size[1],
+                                   self.vis_thr, base + 12 * k * first, base + 4 * (3 * k * n + first), base + 4 * ((3 * k + 1) * n + first),
+                                   _stream()), "pa_kpt_poses (%d boxes, %d keypoints)" % (count, k))
+            first += count
+        self._chunks.append((chunk, n))
+        self._images += image_ids
+        self._bbox_ids += bbox_ids
+        self._last = (keep, table)                           # what the enqueued launches read, until the next call
+        self._records = None
+        return self
+
+    def add(self, preds, maxvals, centers, scales, box_scores, image_ids, bbox_ids=None):
+        """n boxes: preds float32 [n][K][2] in heat-map pixels and maxvals float32 [n][K] as `keypoints` returns them (numpy arrays or CUDA
+        tensors); centers [n][2], scales [n][2] (box size / 200) and box_scores [n] as mmpose's img_metas carry them; image_ids: the photo
+        of every box; bbox_ids: its number among all boxes (default: the order of arrival).  A photo's boxes may arrive in different calls.
+        Nothing is copied back.  -> self."""
+        dev = _device([preds, maxvals], self.device)
+        if dev != self.device:
+            raise RuntimeError("painter_engine: this KeypointAP lives on %s" % self.device)
+        up = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)).contiguous()
+        p, m = up(preds), up(maxvals)
+        n = int(m.shape[0]) if m.dim() == 2 else -1
+        if p.dtype != torch.float32 or m.dtype != torch.float32 or n < 0 or tuple(m.shape) != (n, self.k) or tuple(p.shape) != (n, self.k, 2):
+            raise ValueError("KeypointAP.add: preds %s %s, maxvals %s %s for %d keypoints" % (p.dtype, tuple(p.shape), m.dtype, tuple(m.shape), self.k))
+        image_ids, bbox_ids = self._ids(n, image_ids, bbox_ids)
+        if n == 0:
+            return self
+        return self._launch([(p.data_ptr(), m.data_ptr(), n)], self._boxes(n, centers, scales, box_scores), image_ids, bbox_ids, (p, m))
+
+    def add_decodes(self, decodes, centers, scales, box_scores, image_ids, bbox_ids=None):
+        """decodes: launched PoseDecodes (`pa_pose_keypoints`); preds and maxvals are read where they left them, their own `result()` is
+        untouched.  centers, scales, box_scores, image_ids, bbox_ids: of all their boxes, in the order of the decodes.  -> self."""
+        decodes = list(decodes)
+        for i, d in enumerate(decodes):
+            if not isinstance(d, PoseDecode) or not hasattr(d, "workspace"):
+                raise TypeError("KeypointAP.add_decodes: entry %d is not a launched keypoint PoseDecode" % i)
+            if d.out.device != self.device:
+                raise RuntimeError("painter_engine: this KeypointAP lives on %s" % self.device)
+            if d.k != self.k or (d.w, d.h) != self.heatmap_size:
+                raise ValueError("KeypointAP.add_decodes: decode %d has %d keypoints on %d x %d pictures, this scorer %d on %d x %d"
+                                 % (i, d.k, d.w, d.h, self.k, *self.heatmap_size))
+        n = sum(d.n for d in decodes)
+        image_ids, bbox_ids = self._ids(n, image_ids, bbox_ids)
+        if n == 0:
+            return self
+        parts = [(d.out.data_ptr(), d.out.data_ptr() + 8 * d.n * d.k, d.n) for d in decodes if d.n]
+        return self._launch(parts, self._boxes(n, centers, scales, box_scores), image_ids, bbox_ids, decodes)
+
+    def poses(self):
+        """The pose table as it sits on the device, copied back -> (poses float32 [N][K][3], scores float32 [N], areas float32 [N]) of all
+        boxes in the order of arrival (tests, measurements)."""
+        k = self.k
+        if not self._chunks:
+            return np.zeros((0, k, 3), np.float32), np.zeros(0, np.float32), np.zeros(0, np.float32)
+        parts = [(c.cpu().numpy(), n) for c, n in self._chunks]
+        return (np.concatenate([a[:3 * k * n].reshape(n, k, 3) for a, n in parts]), np.concatenate([a[3 * k * n:3 * k * n + n] for a, n in parts]),
+                np.concatenate([a[3 * k * n + n:] for a, n in parts]))
+
+    def _groups(self):
+        """Host work on the ids only: per photo the positions of its boxes in ascending bbox_id, of equal ids the first handed over."""
+        groups = {}
+        for i, image in enumerate(self._images):
+            groups.setdefault(image, []).append(i)
+        for image in groups:
+            if image not in self._gt:
+                raise ValueError("KeypointAP: image id %r has boxes but is not in ground_truth" % (image,))
+        out = {}
+        for image, mine in groups.items():
+            mine = sorted(mine, key=lambda i: self._bbox_ids[i])          # stable
+            rows = [i for n, i in enumerate(mine) if n == 0 or self._bbox_ids[i] != self._bbox_ids[mine[n - 1]]]
+            if len(rows) > KPT_MAX_BOX:
+                raise ValueError("KeypointAP: photo %r has %d boxes (at most %d)" % (image, len(rows), KPT_MAX_BOX))
+            out[image] = np.array(rows, np.int32)
+        return out
+
+    def _evaluate(self, images, groups, tables):
+        """One pa_kpt_evaluate over the photos `images` -> (out, its layout, shape): enqueued, not copied back."""
+        poses, scores, areas, n_rows = tables
+        n, k = len(images), self.k
+        d_cap = max([self.min_caps[0]] + [len(groups[i]) for i in images])
+        g_cap = max([self.min_caps[1]] + [len(self._gt[i][1]) for i in images])
+        max_det = max(self.max_dets)
+        sections = [("jobs", np.uint8, ctypes.sizeof(KptJob) * n, 16)]
+        for j, image in enumerate(images):
+            sections += [("rows%d" % j, np.int32, len(groups[image]), 4), ("kp%d" % j, np.float64, self._gt[image][0].size, 8),
+                         ("gt%d" % j, KPT_GT, len(self._gt[image][1]), 8)]
+        at, size = _layout(sections)
+        host = torch.zeros(size, dtype=torch.uint8).pin_memory()
+        dev = torch.empty(size, dtype=torch.uint8, device=self.device)
+        a, base = host.numpy(), dev.data_ptr()
+        jobs = (KptJob * n)()
+        for j, (job, image) in enumerate(zip(jobs, images)):
+            kp, table = self._gt[image]
+            _section(a, at, "rows%d" % j)[:] = groups[image]
+            _section(a, at, "kp%d" % j)[:] = kp.ravel()
+            _section(a, at, "gt%d" % j)[:] = table
+            job.rows, job.n_box = base + at["rows%d" % j][0], len(groups[image])
+            if len(table):
+                job.gt_keypoints, job.gt_table, job.n_gt = base + at["kp%d" % j][0], base + at["gt%d" % j][0], len(table)
+        _section(a, at, "jobs")[:] = np.frombuffer(bytearray(jobs), np.uint8)
+        dev.copy_(host, non_blocking=True)
+        shape = (n, d_cap, g_cap, max_det)
+        nbytes = lib.pa_kpt_workspace_bytes(*shape)
+        if nbytes < 0:
+            check(1, "pa_kpt_evaluate (sizes %s)" % (shape,))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        oat, osize = _layout([("records", KPT_RECORD, n * max_det, 8), ("counts", np.int32, n, 4), ("survivors", np.int32, n, 4),
+                              ("flags", np.uint32, n, 4)])
+        out = torch.zeros(osize, dtype=torch.uint8, device=self.device)
+        ptr = lambda name: out.data_ptr() + oat[name][0]
+        T, A, par = len(self.iou_thrs), len(self.area_ranges), self.params.data_ptr()
+        check(lib.pa_kpt_evaluate(base + at["jobs"][0], n, poses.data_ptr(), scores.data_ptr(), areas.data_ptr(), n_rows, d_cap, g_cap, k, par,
+                                  self.oks_thr if self.use_nms else -1.0, max_det, par + 8 * k, T, par + 8 * (k + T), A, ptr("records"),
+                                  ptr("counts"), ptr("survivors"), ptr("flags"), workspace.data_ptr(), _stream()),
+              "pa_kpt_evaluate (sizes %s)" % (shape,))
+        self._last_eval = (host, dev, workspace, shape, images)          # the workspace is what the tests read
+        return out, oat, shape
+
+    def records(self):
+        """Groups and de-duplicates on the host (ids only), concatenates the pose chunks once, launches pa_kpt_evaluate and makes the one
+        copy back (and synchronisation) -> {image id: KPT_RECORDs in evaluation order}, for every photo of ground_truth; one without boxes
+        has none (its ground truths still count in `result()`); `survivors` then holds per photo how many boxes the NMS kept.  ValueError
+        for boxes of a photo that ground_truth does not list, and for a refused photo: it names the photo and the flag bit."""
+        if self._records is None:
+            groups = self._groups()
+            recs = {image: np.zeros(0, KPT_RECORD) for image in self.ground_truth}
+            self.survivors = {image: 0 for image in self.ground_truth}
+            images = list(groups)
+            if images:
+                k, total = self.k, len(self._images)
+                cat = lambda lo, hi: torch.cat([c[lo(n):hi(n)] for c, n in self._chunks])
+                tables = (cat(lambda n: 0, lambda n: 3 * k * n), cat(lambda n: 3 * k * n, lambda n: 3 * k * n + n),
+                          cat(lambda n: 3 * k * n + n, lambda n: 3 * k * n + 2 * n), total)
+                calls = [self._evaluate(images[i:i + KPT_MAX_JOBS], groups, tables) for i in range(0, len(images), KPT_MAX_JOBS)]
+                a = torch.cat([o for o, _, _ in calls]).cpu().numpy()
+                self._outs, base, first = calls, 0, 0                # kept for a caller that wants the words of a refused set
+                for out, oat, (n, _, _, max_det) in calls:
+                    part = a[base:base + out.numel()]
+                    base += out.numel()
+                    table, counts = _section(part, oat, "records").reshape(n, max_det), _section(part, oat, "counts")
+                    flags, surv = _section(part, oat, "flags"), _section(part, oat, "survivors")
+                    bad = np.flatnonzero(flags)
+                    if len(bad):
+                        word = int(flags[bad[0]])
+                        bit = (word & -word).bit_length() - 1
+                        raise ValueError("KeypointAP: photo %r is refused (flag bit %d, flags 0x%02x): %s; %d of %d photos of this call are "
+                                         "refused and emit nothing" % (images[first + bad[0]], bit, word, KPT_FLAGS[bit], len(bad), n))
+                    for j in range(n):
+                        recs[images[first + j]] = table[j, :counts[j]].copy()
+                        self.survivors[images[first + j]] = int(surv[j])
+                    first += n
+            self._records = recs
+        return self._records
+
+    def result(self):
+        """`keypoint_ap_metrics` of `records()` -> dict(AP, AP50, AP75, APm, APl, AR, AR50, AR75, ARm, ARl, precision, recall): accumulate
+        and summarize on the host; COCOeval's formulas restated, unverified against xtcocotools."""
+        return keypoint_ap_metrics(self.records(), self.ground_truth, self.iou_thrs, None, [tuple(r) for r in self.area_ranges.tolist()],
+                                   self.max_dets)
+
+
 class PainterEngine:
     """One prompt pair, one task, any number of query pictures.  prompt_img / prompt_tgt: RGB uint8 arrays of any size, resized once
     (`Image.resize((input_size, input_size))`, Pillow-exact) and kept on the device."""
@@ -1705,10 +2015,19 @@ class PainterEngine:
         flipped twins go through the same batched forwards.  sizes: (width, height) of the painted pictures, all equal within a call
         (default (192, 256) for every picture).  kw: palette, flip_pairs, shift_heatmap of `keypoints`.
         -> one dict(preds float32 [K][2], maxvals float32 [K]) per picture."""
+        def finish(decode, rows):
+            res = decode.result()
+            return [dict(preds=res["preds"][i], maxvals=res["maxvals"][i]) for i in range(len(rows))]
+        # called through the class: `self` needs only task, batch_size, _launch_batch and _run (the argument tests pass a stand-in)
+        return [o for b in PainterEngine._pose_decodes(self, "run_pose", pictures, flipped, sizes, kw, finish) for o in b]
+
+    def _pose_decodes(self, who, pictures, flipped, sizes, kw, finish):
+        """The batches of `run_pose`: per batch of boxes the forwards of the queries and their twins, one launched PoseDecode, then
+        finish(decode, positions of the batch's pictures in `pictures`) -> the list of what `finish` returned."""
         if self.task != "coco_pose":
-            raise ValueError("painter_engine: run_pose decodes the pictures of coco_pose, not of %r" % self.task)
+            raise ValueError("painter_engine: %s decodes the pictures of coco_pose, not of %r" % (who, self.task))
         kw.pop("device", None)
-        _check_arguments("run_pose", kw, POSE_DEFAULTS)                   # before the first forward is enqueued
+        _check_arguments(who, kw, POSE_DEFAULTS)                          # before the first forward is enqueued
         args = dict(POSE_DEFAULTS, **kw)
         pictures = list(pictures)
         sizes = [(192, 256)] * len(pictures) if sizes is None else [(int(w), int(h)) for w, h in sizes]
@@ -1734,9 +2053,39 @@ class PainterEngine:
             m, both = len(boxes), [b[0] for b in boxes] + ([b[1] for b in boxes] if flipped else [])
             plans = [self._launch_batch(both[j:j + self.batch_size], sizes[:1] * len(both[j:j + self.batch_size]), False)
                      for j in range(0, len(both), self.batch_size)]
-            res = PoseDecode(painted(plans, 0, m), painted(plans, m, m) if flipped else None, *args.values()).result()
-            return [dict(preds=res["preds"][i], maxvals=res["maxvals"][i]) for i in range(m)]
-        return [o for b in self._run(list(zip(pictures, flipped or pictures)), sizes, batch, step) for o in b]
+            decode = PoseDecode(painted(plans, 0, m), painted(plans, m, m) if flipped else None, *args.values())
+            return finish(decode, [b[2] for b in boxes])
+        return self._run(list(zip(pictures, flipped or pictures, range(len(pictures)))), sizes, batch, step)
+
+    def run_pose_ap(self, pictures, centers, scales, box_scores, image_ids, score, flipped=None, sizes=None, bbox_ids=None, **kw):
+        """coco_pose: `run_pose`'s batches ending in `score.add_decodes` (a KeypointAP) instead of the copy back: forward, keypoint decode
+        and pa_kpt_poses are chained per batch and nothing is copied back before `score.records()` / `score.result()`.  centers, scales,
+        box_scores, image_ids, bbox_ids: one per picture (see KeypointAP.add); flipped, sizes, kw: as `run_pose` takes them.  Everything
+        is checked before the first forward.  -> score."""
+        if self.task != "coco_pose":
+            raise ValueError("painter_engine: run_pose_ap scores the pictures of coco_pose, not of %r" % self.task)
+        pictures, image_ids = list(pictures), list(image_ids)
+        n = len(pictures)
+        sizes = [(192, 256)] * n if sizes is None else [(int(w), int(h)) for w, h in sizes]
+        bbox_ids = list(range(len(score._images), len(score._images) + n)) if bbox_ids is None else list(bbox_ids)
+        boxes = score._boxes(len(box_scores), centers, scales, box_scores)
+        if not (n == len(boxes) == len(image_ids) == len(bbox_ids) == len(sizes)):
+            raise ValueError("run_pose_ap: %d pictures, %d boxes, %d image ids, %d bbox ids, %d sizes"
+                             % (n, len(boxes), len(image_ids), len(bbox_ids), len(sizes)))
+        if len(set(sizes)) > 1 or (sizes and sizes[0] != score.heatmap_size):
+            raise ValueError("run_pose_ap: the painted pictures are %s, the scorer's heat map %s" % (sorted(set(sizes)), score.heatmap_size))
+        unknown = [i for i in image_ids if i not in score.ground_truth]
+        if unknown:
+            raise ValueError("run_pose_ap: image id %r is not in the scorer's ground_truth" % (unknown[0],))
+        if flipped is not None and not isinstance(flipped, str):
+            flipped = list(flipped)
+            if len(flipped) != n:
+                raise ValueError("run_pose_ap: %d pictures, %d flipped pictures" % (n, len(flipped)))
+
+        def finish(decode, idx):
+            score.add_decodes([decode], boxes[idx, :2], boxes[idx, 2:4], boxes[idx, 4], [image_ids[i] for i in idx], [bbox_ids[i] for i in idx])
+        PainterEngine._pose_decodes(self, "run_pose_ap", pictures, flipped, sizes, kw, finish)
+        return score
 
     def run_semseg_score(self, pictures, gts, score, sizes=None):
         """ade20k_semseg / coco_pano_semseg: forward and decode as `run`, then `score.add` (a SemsegScore) of every batch straight from
