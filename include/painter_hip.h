@@ -97,6 +97,8 @@ int pa_linear_dgrad(int dtype, const void* dy /*T [M,N]*/, int64_t lddy, const v
 int pa_linear_dgrad_skip(int dtype, const void* dy, int64_t lddy, const void* w, const void* gelu_aux, void* dx, int64_t lddx, float* dx_colsum,
                          void* workspace, int M, int N, int K, const float* rowskip /* of the rows of dy / dx */, int skip_rows_per_sample,
                          hipStream_t stream);
+/* pa_linear_wgrad_workspace_bytes: enough for every route pa_linear_wgrad can take at this shape (the maximum over the 256 x 256 kernel's and
+ * the generic engine's split-K slabs: the route also depends on the leading dimensions).  lddy and ldx are multiples of 4 elements. */
 int64_t pa_linear_wgrad_workspace_bytes(int dtype, int M, int N, int K);
 int pa_linear_wgrad(int dtype, const void* dy /*T [M,N]*/, int64_t lddy, const void* x /*T [M,K]*/, int64_t ldx,
                     float* dw /*f32 [N,K]*/, void* workspace, int M, int N, int K, hipStream_t stream);
@@ -155,7 +157,7 @@ int pa_attn_fwd_skip(int dtype, const void* qkv, int64_t ldq, const void* rcat, 
 
 /* autograd of pa_attn_fwd (no reference source: torch autograd of the lines above).
  *   delta  : f32 [batch*heads, L] = rowsum(dO o O)                      (pa_attn_bwd_delta)
- *   dqkv   : T, same layout as qkv (dq | dk | dv)
+ *   dqkv   : T, same layout as qkv (dq | dk | dv) -- the same leading dimension ldq too: a buffer of batch*L rows at that pitch
  *   dG     : T [batch*L, heads*NRP] r-space bias gradient, consumed by pa_attn_bwd_relpos (NULL when relpos_part is given)
  *   relpos_part : NULL, or pa_attn_bwd_relpos_partials_bytes() (> 0 only where the 28-token-wide bf16 kernels run and `tables` is
  *            given) of device scratch: the dQ kernel then contracts d rel_pos itself -- one fp32 [NRP, hd] partial per workgroup --

@@ -583,11 +583,13 @@ static int wgrad_splits(int M, int N, int K, int bk) {
     return s;
 }
 extern "C" int64_t pa_linear_wgrad_workspace_bytes(int dtype, int M, int N, int K) {
+    // the maximum over both routes: which one a call takes also depends on its leading dimensions (g256::ok in linear_wgrad_t), which the
+    // helper does not see -- a bf16 view with ld % 8 != 0 takes the generic engine and its wgrad_splits() slabs at a fast-route shape
+    int s = wgrad_splits(M, N, K, dtype == PA_BF16 ? 64 : 32);
     if (wgrad_fast(dtype, M, N, K)) {
-        const int s = wgrad_fast_splits(M, N, K);
-        return s > 1 ? (int64_t)s * N * K * sizeof(float) : 0;
+        const int f = wgrad_fast_splits(M, N, K);
+        if (f > s) s = f;
     }
-    const int s = wgrad_splits(M, N, K, dtype == PA_BF16 ? 64 : 32);
     return s > 1 ? (int64_t)s * N * K * sizeof(float) : 0;
 }
 template <typename T>
@@ -613,6 +615,7 @@ static int linear_wgrad_t(const T* dy, int64_t lddy, const T* x, int64_t ldx, fl
 extern "C" int pa_linear_wgrad(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw,
                                void* workspace, int M, int N, int K, hipStream_t st) {
     if (N % 4 || K % 4) return (int)hipErrorInvalidValue;
+    if (lddy % 4 || ldx % 4) return (int)hipErrorInvalidValue;      // (the generic loader reads 4 elements of a row at once: OpT::vec)
     if (dtype == PA_BF16) return linear_wgrad_t<bf16>((const bf16*)dy, lddy, (const bf16*)x, ldx, dw, (float*)workspace, M, N, K, st);
     return linear_wgrad_t<float>((const float*)dy, lddy, (const float*)x, ldx, dw, (float*)workspace, M, N, K, st);
 }

@@ -407,7 +407,9 @@ def attn_bwd_core(qkv, rcat, rcatT, out, dout, lse, batch, L, heads, Hp, Wp, sca
         delta = torch.empty((batch * heads, L), dtype=torch.float32, device=dev)
         check(lib.pa_attn_bwd_delta(code(T), p(out), out.stride(0), p(dout), dout.stride(0), p(delta), batch, L, heads, hd,
                                     stream()), "pa_attn_bwd_delta")
-    dqkv = torch.empty_like(qkv)
+    # the kernels write dqkv at qkv's row pitch (include/painter_hip.h: "same layout as qkv") -- empty_like of a column-slice view would be
+    # contiguous, and every row behind the first would land at the wrong place and the last ones behind the end
+    dqkv = torch.empty((qkv.shape[0], qkv.stride(0)), dtype=T, device=dev)[:, :qkv.shape[1]]
     nb = lib.pa_attn_bwd_relpos_partials_bytes(code(T), batch, L, heads, Hp, Wp, hd) if tables is not None else 0
     dG = part = None
     if nb > 0:
@@ -473,6 +475,7 @@ def patch_weight_pack(w, T, P, out=None):
     kp = (3 * P * P + 7) // 8 * 8
     if out is None:
         out = torch.empty((D, kp), dtype=T, device=w.device)
+    assert out.shape == (D, kp) and out.dtype == T and out.is_contiguous()          # (the entry point takes no leading dimension)
     check(lib.pa_patch_weight_pack(code(T), p(w), p(out), D, P, stream()), "pa_patch_weight_pack")
     return out
 

@@ -951,6 +951,8 @@ def test_c_abi_of_the_hot_path_rejects_bad_shapes_instead_of_reading_out_of_boun
     assert lib.pa_attn_fwd(PA_BF16, p_, 192, p_, p_, 64, p_, None, 1, 90, 1, 9, 10, 64, 0.125, s) != 0              # grid not a multiple of 4
     assert lib.pa_attn_fwd(PA_BF16, p_, 288, p_, p_, 96, p_, None, 1, 96, 1, 8, 12, 96, 0.125, s) != 0              # head_dim the kernels are not built for
     assert lib.pa_layernorm_fwd(PA_BF16, p_, 6, p_, p_, 1e-6, p_, 6, p_, p_, 4, 6, s) != 0                          # D % 4
+    assert lib.pa_linear_wgrad(PA_BF16, p_, 18, p_, 16, p_, p_, 64, 16, 16, s) != 0                                 # lddy % 4: the generic loader reads 4 elements at once
+    assert lib.pa_linear_wgrad(PA_F32, p_, 16, p_, 22, p_, p_, 64, 16, 16, s) != 0                                  # ldx % 4
     assert lib.pa_debug_set(99, 1) != 0
     assert lib.pa_attn_set_generation(7) != 0 and lib.pa_attn_set_generation(4) != 0        # the retired builds are gone
     with pytest.raises(RuntimeError):
