@@ -256,3 +256,5 @@ DEVI uint2 cvt4(float a, float b, float c, float d, bf16*) { return make_uint2(p
 
 typedef unsigned long long u64;                                                          // what atomicAdd's 64-bit overload takes
 inline int64_t up256(int64_t x) { return (x + 255) & ~(int64_t)255; }                    // workspace sections start on 256 bytes
+inline int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }                       // ... or, in the scorers' workspaces, on 16
+DEVI int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }

@@ -15,7 +15,8 @@
 //               ground truths "ignored ones last, stop at the first ignored one once a non-ignored one is held" is ONE pass in table
 //               order with two running bests (non-ignored, ignored; >= keeps the later of equals, as the walk does) and the ignored
 //               best counts only when there is no other: no order table, and the row of IoUs is read four at a time, every lane
-//               the same address.
+//               the same address.  That walk, the rank, the threshold cap and the ignore words are coco_match.h's, shared with
+//               painter_kpt.hip; the class filter of mode "per_class" goes in as the walk's skip predicate.
 //   emit      : per detection in sorted order one pa_ap_record, and the number of records per job.  A job with a flag word emits nothing.
 //
 // Caps: AP_MAX_D = AP_MAX_G = 128 detections / ground truths per picture (COCO val has at most 93 annotations per picture, the decode keeps
@@ -25,6 +26,7 @@
 #include <stdint.h>
 #include "../../include/painter_hip.h"
 #include "common.h"
+#include "coco_match.h"
 
 #pragma clang fp contract(off)
 
@@ -39,7 +41,6 @@ constexpr int64_t AP_MAX_WORDS = (int64_t)1 << 26;           // h * w < 2^31
 
 enum : uint32_t { FLAG_NAN = 1u, FLAG_DET_CLASS = 2u, FLAG_GT_CLASS = 4u };
 
-inline int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 inline bool caps_ok(int n_jobs, int d_cap, int g_cap) {
     return n_jobs >= 1 && n_jobs <= 65535 && d_cap >= 1 && d_cap <= AP_MAX_D && g_cap >= 1 && g_cap <= AP_MAX_G;
 }
@@ -60,7 +61,6 @@ inline Layout layout(int n_jobs, int d_cap, int g_cap) {
     return l;
 }
 
-DEVI int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 // Pixels of a job, 0 for one that counts nothing.
 DEVI int64_t job_pixels(const pa_ap_job& job) {
     if (job.h < 1 || job.w < 1) return 0;
@@ -216,12 +216,7 @@ __global__ __launch_bounds__(AP_THREADS) void ap_match_kernel(const pa_ap_job* _
         return;
     }
     // stable rank by descending score, ties to the lower index
-    if (tid < Dn) {
-        const float s = s_score[tid];
-        int rank = 0;
-        for (int o = 0; o < Dn; ++o) rank += (s_score[o] > s || (s_score[o] == s && o < tid)) ? 1 : 0;
-        s_order[rank] = tid;
-    }
+    if (tid < Dn) s_order[coco::rank_by_score(s_score, Dn, tid, false)] = tid;
     for (int i = tid; i < Dn * G; i += AP_THREADS) {
         const int d = i / G, g = i % G;
         const uint32_t c = lone ? 0u : inter[((int64_t)j * d_cap + d) * g_cap + g];
@@ -233,53 +228,22 @@ __global__ __launch_bounds__(AP_THREADS) void ap_match_kernel(const pa_ap_job* _
         ious[d * g_cap + g] = v;
     }
     // per range: the ignored ground truths
-    if (tid < A) {
-        const double lo = ranges[2 * tid], hi = ranges[2 * tid + 1];
-        u64 b[2] = {0ull, 0ull};
-        for (int g = 0; g < G; ++g)
-            if (s_gcrowd[g] || s_garea[g] < lo || s_garea[g] > hi) b[g >> 6] |= 1ull << (g & 63);
-        s_ign[tid][0] = b[0];
-        s_ign[tid][1] = b[1];
-    }
+    if (tid < A) coco::ignore_words(s_garea, G, ranges[2 * tid], ranges[2 * tid + 1], s_crowd[0], s_crowd[1], s_ign[tid]);
     __syncthreads();
     if (tid < 2 * A * T && ((modes >> (tid / (A * T))) & 1)) {
         const int mode = tid / (A * T), a = tid % (A * T) / T, t = tid % T;
-        const double thr = thrs[t], lo = ranges[2 * a], hi = ranges[2 * a + 1], cap = 1 - 1e-10;
-        const double thr0 = thr < cap ? thr : cap;
+        const double thr0 = coco::cap_threshold(thrs[t]), lo = ranges[2 * a], hi = ranges[2 * a + 1];
         const u64 bit = 1ull << (a * T + t);
         const u64 ign0 = s_ign[a][0], ign1 = s_ign[a][1], crowd0 = s_crowd[0], crowd1 = s_crowd[1];
         u64 taken0 = 0ull, taken1 = 0ull;                         // the ground truths matched at this threshold
         for (int r = 0; r < Dn; ++r) {
             const int d = s_order[r], dc = s_dcls[d];
-            const double* __restrict__ row = ious + d * g_cap;
-            const u64 free0 = ~taken0 | crowd0, free1 = ~taken1 | crowd1;          // a matched one stays open only when it is crowd
-            double best = thr0, best_ign = thr0;                  // of the non-ignored and of the ignored ground truths
-            int m = -1, m_ign = -1;
-            for (int g0 = 0; g0 < G; g0 += 4) {
-                double v[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = g0 + i < G ? row[g0 + i] : -INFINITY;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int g = g0 + i;
-                    if (v[i] < thr0) continue;
-                    if (!(((g < 64 ? free0 : free1) >> (g & 63)) & 1ull)) continue;
-                    if (mode == 1 && s_gcls[g] != dc) continue;
-                    if (((g < 64 ? ign0 : ign1) >> (g & 63)) & 1ull) {
-                        if (v[i] >= best_ign) { best_ign = v[i]; m_ign = g; }
-                    } else if (v[i] >= best) {
-                        best = v[i];
-                        m = g;
-                    }
-                }
-            }
+            const int m = coco::match_one(ious + d * g_cap, G, thr0, ign0, ign1, crowd0, crowd1, taken0, taken1,
+                                          [&](int g) { return mode == 1 && s_gcls[g] != dc; });
             bool ign;
-            if (m < 0) m = m_ign;
             if (m > -1) {
-                if (m < 64) taken0 |= 1ull << m;
-                else taken1 |= 1ull << (m - 64);
                 atomicOr(&s_bits[mode][r], bit);
-                ign = (((m < 64 ? ign0 : ign1) >> (m & 63)) & 1ull) != 0ull;
+                ign = coco::bit_of(ign0, ign1, m);
             } else {
                 ign = (double)s_darea[d] < lo || (double)s_darea[d] > hi;
             }

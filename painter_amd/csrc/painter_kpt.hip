@@ -20,7 +20,8 @@
 //              match   ONE THREAD per (range, threshold) runs evaluateImg's sequential greedy loop with the matched, crowd and ignored
 //                      ground truths as bits in registers: one pass in table order with two running bests (non-ignored, ignored; >=
 //                      keeps the later of equals, as the walk does) and the ignored best counts only when there is no other -- the walk
-//                      of painter_ap.hip's ap_match_kernel, restated here.
+//                      painter_ap.hip's ap_match_kernel runs, coco_match.h's match_one, with no class filter.  The
+//                      rank, the threshold cap and the per-range ignore words come from that header too.
 //              emit    one pa_kpt_record per evaluated survivor.  A photo with a flag word emits nothing.
 //
 // exp is HIP's double exp; everything that feeds it is stated operation by operation, no fused multiply-add.
@@ -29,6 +30,7 @@
 #include <stdint.h>
 #include "../../include/painter_hip.h"
 #include "common.h"
+#include "coco_match.h"
 
 #pragma clang fp contract(off)
 
@@ -42,7 +44,6 @@ constexpr int KP_NONE = 0x7fffffff;
 
 enum : uint32_t { FLAG_NAN = 1u, FLAG_GT_AREA = 2u, FLAG_ROW = 4u };
 
-inline int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 inline bool caps_ok(int n_jobs, int d_cap, int g_cap, int max_det) {
     return n_jobs >= 1 && n_jobs <= 65535 && d_cap >= 1 && d_cap <= KP_MAX_D && g_cap >= 1 && g_cap <= KP_MAX_G && max_det >= 1 &&
            max_det <= KP_MAX_E;
@@ -60,8 +61,6 @@ inline Layout layout(int n_jobs, int d_cap, int g_cap, int max_det) {
     l.end = l.oks + 8 * (int64_t)n_jobs * max_det * g_cap;
     return l;
 }
-
-DEVI int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One wave per box; boxes float32 [n][5] = center x, y, scale x, y, box score.
 __global__ __launch_bounds__(256) void kpt_poses_kernel(const float* __restrict__ preds, const float* __restrict__ maxvals,
@@ -174,15 +173,7 @@ __global__ __launch_bounds__(KP_MAX_D) void kpt_evaluate_kernel(const pa_kpt_job
         }
         return;
     }
-    if (tid < D) {
-        const float s = s_score[tid];
-        int rank = 0;
-        for (int o = 0; o < D; ++o) {
-            const float so = s_score[o];
-            rank += (so > s || (so == s && (nms ? o > tid : o < tid))) ? 1 : 0;
-        }
-        s_order[rank] = tid;
-    }
+    if (tid < D) s_order[coco::rank_by_score(s_score, D, tid, nms)] = tid;
     __syncthreads();
     // thread t takes the box of rank t
     float px[KP_MAX_K], py[KP_MAX_K];
@@ -317,51 +308,20 @@ __global__ __launch_bounds__(KP_MAX_D) void kpt_evaluate_kernel(const pa_kpt_job
         oks_out[((int64_t)j * max_det + e) * g_cap + g] = sum;
     }
     // per range: the ignored ground truths
-    if (tid < A) {
-        const double lo = ranges[2 * tid], hi = ranges[2 * tid + 1];
-        u64 b[2] = {s_skip[0], s_skip[1]};
-        for (int g = 0; g < G; ++g)
-            if (s_garea[g] < lo || s_garea[g] > hi) b[g >> 6] |= 1ull << (g & 63);
-        s_ign[tid][0] = b[0];
-        s_ign[tid][1] = b[1];
-    }
+    if (tid < A) coco::ignore_words(s_garea, G, ranges[2 * tid], ranges[2 * tid + 1], s_skip[0], s_skip[1], s_ign[tid]);
     __syncthreads();
     if (tid < A * T) {
         const int a = tid / T, t = tid % T;
-        const double thr = thrs[t], lo = ranges[2 * a], hi = ranges[2 * a + 1], cap = 1 - 1e-10;
-        const double thr0 = thr < cap ? thr : cap;
+        const double thr0 = coco::cap_threshold(thrs[t]), lo = ranges[2 * a], hi = ranges[2 * a + 1];
         const u64 bit = 1ull << (a * T + t);
         const u64 ign0 = s_ign[a][0], ign1 = s_ign[a][1], crowd0 = s_crowd[0], crowd1 = s_crowd[1];
         u64 taken0 = 0ull, taken1 = 0ull;                         // the ground truths matched at this threshold
         for (int r = 0; r < E; ++r) {
-            const double* __restrict__ orow = s_oks + r * g_cap;
-            const u64 free0 = ~taken0 | crowd0, free1 = ~taken1 | crowd1;          // a matched one stays open only when it is crowd
-            double best = thr0, best_ign = thr0;                  // of the non-ignored and of the ignored ground truths
-            int m = -1, m_ign = -1;
-            for (int g0 = 0; g0 < G; g0 += 4) {
-                double v[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = g0 + i < G ? orow[g0 + i] : -INFINITY;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int g = g0 + i;
-                    if (v[i] < thr0) continue;
-                    if (!(((g < 64 ? free0 : free1) >> (g & 63)) & 1ull)) continue;
-                    if (((g < 64 ? ign0 : ign1) >> (g & 63)) & 1ull) {
-                        if (v[i] >= best_ign) { best_ign = v[i]; m_ign = g; }
-                    } else if (v[i] >= best) {
-                        best = v[i];
-                        m = g;
-                    }
-                }
-            }
+            const int m = coco::match_one(s_oks + r * g_cap, G, thr0, ign0, ign1, crowd0, crowd1, taken0, taken1, [](int) { return false; });
             bool ign;
-            if (m < 0) m = m_ign;
             if (m > -1) {
-                if (m < 64) taken0 |= 1ull << m;
-                else taken1 |= 1ull << (m - 64);
                 atomicOr(&s_matched[r], bit);
-                ign = (((m < 64 ? ign0 : ign1) >> (m & 63)) & 1ull) != 0ull;
+                ign = coco::bit_of(ign0, ign1, m);
             } else {
                 ign = s_darea[r] < lo || s_darea[r] > hi;
             }

@@ -37,7 +37,6 @@ constexpr int64_t PQ_MAX_PIXELS = (int64_t)1 << 31;          // of a job: no 32-
 
 enum : uint32_t { FLAG_UNLISTED = 1u, FLAG_EMPTY = 2u, FLAG_CATEGORY = 4u, FLAG_UNION = 8u, FLAG_TWICE = 16u, FLAG_ORDER = 32u };
 
-inline int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 inline int64_t n_bins(int g_cap, int p_cap) { return (int64_t)(g_cap + 2) * (p_cap + 1); }
 inline bool caps_ok(int g_cap, int p_cap) { return g_cap >= 1 && g_cap <= PQ_MAX_G && p_cap >= 1 && p_cap <= PQ_MAX_P; }
 
@@ -55,7 +54,6 @@ inline Layout layout(int n_jobs, int g_cap, int p_cap, int K) {
     return l;
 }
 
-DEVI int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 DEVI int slot_of(int id) { return (int)(((uint32_t)id * 2654435761u) >> 23); }          // 9 bits
 
 // Entry `index` (1-based) of a table under its id.  Ids <= 0 are never listed (0 is the empty slot); of a repeated id one entry stays.

@@ -38,7 +38,6 @@ constexpr int DEPTH_THREADS = 256;
 constexpr int DEPTH_PARTS = 32;                   // partials per job: 8 jobs fill the chip
 constexpr int DEPTH_OUT = 10;                     // n, three counts, six sums
 
-inline int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 inline int64_t conf_lds_bytes(int K) { return up16(12 * (int64_t)K) + 4 * (int64_t)(K + 1) * (K + 1); }
 
 // Keys of a lane: >= 0 a bin, KEY_NONE no pixel, KEY_INVALID a ground-truth value >= K that is not the ignore label.

@@ -71,6 +71,9 @@ PNG encoding, RLE and COCOeval's box AP (mask AP: `InstanceAP`); of the pose rou
 One host path serves the routes: `_device` / `_pictures` put the inputs of a call on one indexed CUDA device; INSTANCE_DEFAULTS,
 MERGE_DEFAULTS, POSE_DEFAULTS and DEPTH_DEFAULTS hold the keyword defaults and `_check_arguments` refuses the rest before a forward is enqueued; an output
 buffer is one list of sections (`_layout`): its size, the pointers handed to the library and the slices of `result()` all come from it.
+The three scorers with job tables (`PanopticQuality`, `InstanceAP`, `KeypointAP`) stage their tables through one `_Upload` (sections, pinned
+host buffer, ONE asynchronous copy), size their workspace through `_workspace` and word a refused picture through `_refuse`; the two AP
+scorers parse COCOeval's parameters with `_coco_params`, and `instance_ap_metrics` / `keypoint_ap_metrics` share one `_coco_accumulate`.
 
 There is no CPU fallback: a CPU device or a missing libpainter_hip.so raises.
 """
@@ -210,6 +213,58 @@ def _section(host, at, name, count=None):
     """The first `count` elements (default: all) of a section of `_layout` in the buffer's host copy, in the section's dtype."""
     off, dtype, n = at[name]
     return host[off:off + dtype.itemsize * (n if count is None else count)].view(dtype)
+
+
+class _Upload:
+    """The tables of one scoring call, staged as sections (`_layout`; "jobs" is the job table) of a zeroed pinned host buffer with its twin
+    on the device: `up.put(name, values)` fills a section (its first len(values) elements) and returns its device address, `up.send(jobs)`
+    puts the job records in and enqueues the ONE asynchronous copy.  `host` and `dev` must outlive the launches that read them."""
+
+    def __init__(self, sections, device):
+        self.at, size = _layout(sections)
+        self.host = torch.zeros(size, dtype=torch.uint8).pin_memory()
+        self.dev = torch.empty(size, dtype=torch.uint8, device=device)
+        self._bytes, self._base = self.host.numpy(), self.dev.data_ptr()          # once: a data set has hundreds of sections
+
+    def put(self, name, values):
+        # one call per section and no call below it: KeypointAP stages three sections per photo, hundreds of photos per call
+        off, dtype, _ = self.at[name]
+        self._bytes[off:off + dtype.itemsize * len(values)].view(dtype)[:] = values
+        return self._base + off
+
+    def send(self, jobs):
+        at = self.put("jobs", np.frombuffer(bytearray(jobs), np.uint8))
+        self.dev.copy_(self.host, non_blocking=True)
+        return at
+
+
+def _workspace(size_of, shape, what, device):
+    """The workspace the library asks for at the capacities `shape`; sizes it refuses (-1) fail as `what` would."""
+    nbytes = size_of(*shape)
+    if nbytes < 0:
+        check(1, what)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _refuse(who, flags, reasons, k=None, name=lambda i: "picture %d" % i, rest="pictures are refused and emit nothing"):
+    """ValueError for the first non-zero word of `flags`, the flag words a scoring kernel left per picture: which picture, its lowest flag
+    bit, what that bit means (`reasons`; `k` fills a "%d classes") and how many are refused."""
+    bad = np.flatnonzero(flags)
+    if len(bad):
+        word = int(flags[bad[0]])
+        bit = (word & -word).bit_length() - 1
+        why = reasons[bit] % k if "%d" in reasons[bit] else reasons[bit]
+        raise ValueError("%s: %s is refused (flag bit %d, flags 0x%02x): %s; %d of %d %s"
+                         % (who, name(bad[0]), bit, word, why, len(bad), len(flags), rest))
+
+
+def _coco_params(iou_thrs, area_ranges, max_dets):
+    """COCOeval's Params as both AP scorers take them -> (iou_thrs float64 [T], area_ranges float64 [A][2], max_dets tuple, ok): a record's
+    words hold one bit per (range, threshold), so T * A <= 64."""
+    iou_thrs = np.linspace(.5, .95, 10) if iou_thrs is None else np.array(iou_thrs, np.float64).ravel()
+    area_ranges = np.array(area_ranges, np.float64).reshape(-1, 2)
+    max_dets = tuple(int(m) for m in max_dets)
+    return iou_thrs, area_ranges, max_dets, 1 <= len(iou_thrs) * len(area_ranges) <= 64 and bool(max_dets)
 
 
 def _forward(model, imgs, tgts):
@@ -1153,34 +1208,25 @@ class PanopticQuality:
         for i, (p, t) in enumerate(zip(preds, gtabs)):
             sections += [("gt%d" % i, GT_SEGMENT, len(t), 8), ("pred%d" % i, SEGMENT, 0 if p[4] is not None else len(p[3]), 8),
                          ("count%d" % i, np.int32, 0 if p[4] is not None else 1, 4)]
-        at, size = _layout(sections)
-        host = torch.zeros(max(size, 1), dtype=torch.uint8).pin_memory()
-        dev = torch.empty(max(size, 1), dtype=torch.uint8, device=self.device)
-        a, base = host.numpy(), dev.data_ptr()
+        up = _Upload(sections, self.device)
         jobs = (PqJob * n)()
         for i, (job, p, g, t) in enumerate(zip(jobs, preds, maps, gtabs)):
-            _section(a, at, "gt%d" % i)[:] = t
             job.pred, job.h, job.w, job.gt, job.gt_rgb = p[0], p[1], p[2], g.data_ptr(), int(g.dim() == 3)
-            job.gt_segments, job.n_gt, job.g_cap, job.p_cap = base + at["gt%d" % i][0], len(t), len(t), p[5]
+            job.gt_segments, job.n_gt, job.g_cap, job.p_cap = up.put("gt%d" % i, t), len(t), len(t), p[5]
             if p[4] is not None:
                 job.pred_segments, job.pred_count = p[3], p[4]
             else:
-                _section(a, at, "pred%d" % i)[:] = p[3]
-                _section(a, at, "count%d" % i)[:] = len(p[3])
-                job.pred_segments, job.pred_count = base + at["pred%d" % i][0], base + at["count%d" % i][0]
-        _section(a, at, "jobs")[:] = np.frombuffer(bytearray(jobs), np.uint8)
-        dev.copy_(host, non_blocking=True)
+                job.pred_segments, job.pred_count = up.put("pred%d" % i, p[3]), up.put("count%d" % i, [len(p[3])])
         shape = (n, g_cap, p_cap, self.k)
-        nbytes = lib.pa_pq_workspace_bytes(*shape)
-        if nbytes < 0:
-            check(1, "pa_pq_add (sizes %s)" % (shape,))
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        what = "pa_pq_add (sizes %s)" % (shape,)
+        sent = up.send(jobs)
+        workspace = _workspace(lib.pa_pq_workspace_bytes, shape, what, self.device)
         flags = torch.empty(n, dtype=torch.int32, device=self.device)
         ptr = lambda name: self.out.data_ptr() + self.at[name][0]
-        check(lib.pa_pq_add(base + at["jobs"][0], n, max(p[1] * p[2] for p in preds), g_cap, p_cap, self.k, self.bins, ptr("tp"), ptr("fp"),
-                            ptr("fn"), ptr("iou"), flags.data_ptr(), workspace.data_ptr(), _stream()), "pa_pq_add (sizes %s)" % (shape,))
+        check(lib.pa_pq_add(sent, n, max(p[1] * p[2] for p in preds), g_cap, p_cap, self.k, self.bins, ptr("tp"), ptr("fp"), ptr("fn"),
+                            ptr("iou"), flags.data_ptr(), workspace.data_ptr(), _stream()), what)
         self._flags.append(flags)
-        self._last = (keep, maps, host, dev, workspace)      # what the enqueued launches read, until the next call
+        self._last = (keep, maps, up.host, up.dev, workspace)      # what the enqueued launches read, until the next call
         return self
 
     def add(self, preds, pred_segments, gts, gt_segments):
@@ -1214,14 +1260,7 @@ class PanopticQuality:
         """The one copy back (and synchronisation), with the flag words -> tp, fp, fn int64 [n_classes], iou float64 [n_classes] (numpy).
         ValueError names the first refused picture (counted over all `add` calls since `reset`) and why."""
         a = torch.cat([self.out] + [f.view(torch.uint8) for f in self._flags]).cpu().numpy()
-        flags = a[self.out.numel():].view(np.uint32)
-        bad = np.flatnonzero(flags)
-        if len(bad):
-            word = int(flags[bad[0]])
-            bit = (word & -word).bit_length() - 1
-            why = PQ_FLAGS[bit] % self.k if "%d" in PQ_FLAGS[bit] else PQ_FLAGS[bit]
-            raise ValueError("PanopticQuality: picture %d is refused (flag bit %d, flags 0x%02x): %s; %d of %d pictures are refused and add "
-                             "nothing" % (bad[0], bit, word, why, len(bad), len(flags)))
+        _refuse("PanopticQuality", a[self.out.numel():].view(np.uint32), PQ_FLAGS, self.k, rest="pictures are refused and add nothing")
         return tuple(_section(a, self.at, name).copy() for name in ("tp", "fp", "fn", "iou"))
 
     def result(self):
@@ -1286,6 +1325,34 @@ def _ap_mean(x):
     return float(np.mean(x)) if x.size else -1.0
 
 
+def _coco_accumulate(pictures, npig, T, rec_thrs, max_dets, precision, recall):
+    """COCOeval.accumulate for one class (or pseudo-class).  pictures: per picture (scores, matched words, ignored words) of its records in
+    evaluation order, bit a * T + t of a word = area range a, threshold t; npig: per area range the ground truths that count.  Fills
+    precision [T][R][A][M] and recall [T][A][M] (views of the caller's tables) wherever npig > 0: the records cut to the first m of
+    max_dets, concatenated in picture order, stable-sorted by descending score; running tp / fp counts; precision made monotone from the
+    right and read at the first position whose recall reaches each of rec_thrs."""
+    for a, n_gt in enumerate(npig):
+        if n_gt == 0:
+            continue
+        shift = np.arange(a * T, a * T + T, dtype=np.uint64)[:, None]
+        for m, max_det in enumerate(max_dets):
+            cat = lambda i, dtype: np.concatenate([p[i][:max_det] for p in pictures]) if pictures else np.zeros(0, dtype)
+            order = np.argsort(-cat(0, np.float32), kind="mergesort")
+            dtm, ign = ((cat(i, np.uint64)[order][None] >> shift) & np.uint64(1) != 0 for i in (1, 2))
+            tp = np.cumsum(dtm & ~ign, axis=1).astype(np.float64)
+            fp = np.cumsum(~dtm & ~ign, axis=1).astype(np.float64)
+            nd = tp.shape[1]
+            for t in range(T):
+                rc = tp[t] / n_gt
+                pr = tp[t] / (fp[t] + tp[t] + np.spacing(1))
+                recall[t, a, m] = rc[-1] if nd else 0
+                pr = np.maximum.accumulate(pr[::-1])[::-1]
+                at = np.searchsorted(rc, rec_thrs, side="left")
+                q = np.zeros(len(rec_thrs))
+                q[at < nd] = pr[at[at < nd]]
+                precision[t, :, a, m] = q
+
+
 def instance_ap_metrics(records, gt_annotations, n_classes=80, mode="agnostic", iou_thrs=None, rec_thrs=None, max_dets=(1, 10, 100),
                         area_ranges=None):
     """COCOeval.accumulate and .summarize (iouType "segm") on the records of `InstanceAP.records()`, on the host in float64.  records: per
@@ -1310,29 +1377,9 @@ def instance_ap_metrics(records, gt_annotations, n_classes=80, mode="agnostic", 
     for k in range(K):
         recs = [r[r["category"] == k] for r in records] if mode == "per_class" else list(records)
         mine = [c == k for c in gcls] if mode == "per_class" else [np.ones(len(c), bool) for c in gcls]
-        for a, (lo, hi) in enumerate(area_ranges):
-            npig = sum(int((m & ~(c | (v < lo) | (v > hi))).sum()) for m, c, v in zip(mine, crowd, area))
-            if npig == 0:
-                continue
-            for m, max_det in enumerate(max_dets):
-                cut = [r[:max_det] for r in recs]
-                scores = np.concatenate([r["score"] for r in cut]) if cut else np.zeros(0, np.float32)
-                order = np.argsort(-scores, kind="mergesort")
-                shift = np.arange(a * T, a * T + T, dtype=np.uint64)[:, None]
-                word = lambda name: np.concatenate([r[name][:, mi] for r in cut])[order] if cut else np.zeros(0, np.uint64)
-                dtm, ign = (word("matched")[None] >> shift) & np.uint64(1) != 0, (word("ignored")[None] >> shift) & np.uint64(1) != 0
-                tp = np.cumsum(dtm & ~ign, axis=1).astype(np.float64)
-                fp = np.cumsum(~dtm & ~ign, axis=1).astype(np.float64)
-                nd = tp.shape[1]
-                for t in range(T):
-                    rc = tp[t] / npig
-                    pr = tp[t] / (fp[t] + tp[t] + np.spacing(1))
-                    recall[t, k, a, m] = rc[-1] if nd else 0
-                    pr = np.maximum.accumulate(pr[::-1])[::-1]
-                    at = np.searchsorted(rc, rec_thrs, side="left")
-                    q = np.zeros(R)
-                    q[at < nd] = pr[at[at < nd]]
-                    precision[t, :, k, a, m] = q
+        npig = [sum(int((m & ~(c | (v < lo) | (v > hi))).sum()) for m, c, v in zip(mine, crowd, area)) for lo, hi in area_ranges]
+        _coco_accumulate([(r["score"], r["matched"][:, mi], r["ignored"][:, mi]) for r in recs], npig, T, rec_thrs, max_dets,
+                         precision[:, :, k], recall[:, k])
     at = lambda v: np.flatnonzero(iou_thrs == v)
     res = dict(AP=_ap_mean(precision[:, :, :, 0, -1]), AP50=_ap_mean(precision[at(.5), :, :, 0, -1]),
                AP75=_ap_mean(precision[at(.75), :, :, 0, -1]))
@@ -1374,10 +1421,8 @@ class InstanceAP:
         self.modes = tuple(modes)
         if not self.modes or any(m not in AP_MODES for m in self.modes):
             raise ValueError("InstanceAP: modes %r (of %s)" % (modes, ", ".join(AP_MODES)))
-        self.iou_thrs = np.linspace(.5, .95, 10) if iou_thrs is None else np.array(iou_thrs, np.float64).ravel()
-        self.area_ranges = np.array(AP_AREA_RANGES if area_ranges is None else area_ranges, np.float64).reshape(-1, 2)
-        self.max_dets = tuple(int(m) for m in max_dets)
-        if not 1 <= self.k <= 1024 or not 1 <= len(self.iou_thrs) * len(self.area_ranges) <= 64 or not self.max_dets:
+        self.iou_thrs, self.area_ranges, self.max_dets, ok = _coco_params(iou_thrs, AP_AREA_RANGES if area_ranges is None else area_ranges, max_dets)
+        if not 1 <= self.k <= 1024 or not ok:
             raise ValueError("InstanceAP: %d classes (1 .. 1024), %d thresholds x %d area ranges (at most 64 together)"
                              % (self.k, len(self.iou_thrs), len(self.area_ranges)))
         self.min_caps = (1, 1)                               # capacities (d_cap, g_cap) a call has at least (tests, measurements)
@@ -1425,46 +1470,34 @@ class InstanceAP:
             own = d[3] is None                               # scores, classes and count come from the host
             sections += [("gt%d" % i, AP_GT, len(t), 8), ("scores%d" % i, np.float32, d[2] if own else 0, 4),
                          ("classes%d" % i, np.int32, d[2] if own and d[5] is not None else 0, 4), ("count%d" % i, np.int32, int(own), 4)]
-        at, size = _layout(sections)
-        host = torch.zeros(size, dtype=torch.uint8).pin_memory()
-        dev = torch.empty(size, dtype=torch.uint8, device=self.device)
-        a, base = host.numpy(), dev.data_ptr()
+        up = _Upload(sections, self.device)
         jobs = (ApJob * n)()
         for i, (job, d, g, t) in enumerate(zip(jobs, dets, gbits, tables)):
-            _section(a, at, "gt%d" % i)[:] = t
             job.h, job.w, job.d_cap, job.empty_as_one = d[0], d[1], d[2], int(d[6])
-            job.gt_masks, job.gt_table, job.n_gt = g.data_ptr(), base + at["gt%d" % i][0], len(t)
+            job.gt_masks, job.gt_table, job.n_gt = g.data_ptr(), up.put("gt%d" % i, t), len(t)
             if d[3] is not None:
                 job.det_masks, job.det_scores, job.det_classes, job.det_count = d[3]
             else:
-                count = len(d[4])
-                _section(a, at, "scores%d" % i)[:count] = d[4]
-                _section(a, at, "count%d" % i)[:] = count
-                job.det_masks, job.det_scores, job.det_count = d[7].data_ptr(), base + at["scores%d" % i][0], base + at["count%d" % i][0]
+                job.det_masks, job.det_scores, job.det_count = d[7].data_ptr(), up.put("scores%d" % i, d[4]), up.put("count%d" % i, [len(d[4])])
                 if d[5] is not None:
-                    _section(a, at, "classes%d" % i)[:count] = d[5]
-                    job.det_classes = base + at["classes%d" % i][0]
-        _section(a, at, "jobs")[:] = np.frombuffer(bytearray(jobs), np.uint8)
-        dev.copy_(host, non_blocking=True)
+                    job.det_classes = up.put("classes%d" % i, d[5])
         shape = (n, d_cap, g_cap)
-        nbytes = lib.pa_ap_workspace_bytes(*shape)
-        if nbytes < 0:
-            check(1, "pa_ap_add (sizes %s)" % (shape,))
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        what = "pa_ap_add (sizes %s)" % (shape,)
+        sent = up.send(jobs)
+        workspace = _workspace(lib.pa_ap_workspace_bytes, shape, what, self.device)
         oat, osize = _layout([("records", AP_RECORD, n * d_cap, 8), ("counts", np.int32, n, 4), ("flags", np.uint32, n, 4),
                               ("gpix", np.uint32, n * g_cap, 4)])
         out = torch.zeros(osize, dtype=torch.uint8, device=self.device)
         ptr = lambda name: out.data_ptr() + oat[name][0]
         modes = sum(1 << AP_MODES.index(m) for m in set(self.modes))
         T, A = len(self.iou_thrs), len(self.area_ranges)
-        check(lib.pa_ap_add(base + at["jobs"][0], n, max((d[0] * d[1] + 31) // 32 for d in dets), d_cap, g_cap, self.k, modes,
-                            self.params.data_ptr(), T, self.params.data_ptr() + 8 * T, A, ptr("records"), ptr("counts"), ptr("flags"),
-                            workspace.data_ptr(), _stream()), "pa_ap_add (sizes %s)" % (shape,))
+        check(lib.pa_ap_add(sent, n, max((d[0] * d[1] + 31) // 32 for d in dets), d_cap, g_cap, self.k, modes, self.params.data_ptr(), T,
+                            self.params.data_ptr() + 8 * T, A, ptr("records"), ptr("counts"), ptr("flags"), workspace.data_ptr(), _stream()), what)
         off = lib.pa_ap_workspace_offset(*shape, 2)
         out[oat["gpix"][0]:oat["gpix"][0] + 4 * n * g_cap].copy_(workspace[off:off + 4 * n * g_cap])       # the areas of `area: None`
         self._outs.append((out, oat, shape))
         self._annotations += [[dict(category_id=int(r["category"]), iscrowd=int(r["iscrowd"]), area=float(r["area"])) for r in t] for t in tables]
-        self._last = (keep, gbits, host, dev, workspace)     # what the enqueued launches read, until the next call
+        self._last = (keep, gbits, up.host, up.dev, workspace)     # what the enqueued launches read, until the next call
         self._records = None
         return self
 
@@ -1531,13 +1564,7 @@ class InstanceAP:
                 recs += [table[i, :counts[i]].copy() for i in range(n)]
                 flags += _section(part, oat, "flags").tolist()
                 areas += [row for row in _section(part, oat, "gpix").reshape(n, g_cap)]
-            bad = np.flatnonzero(flags)
-            if len(bad):
-                word = int(flags[bad[0]])
-                bit = (word & -word).bit_length() - 1
-                why = AP_FLAGS[bit] % self.k if "%d" in AP_FLAGS[bit] else AP_FLAGS[bit]
-                raise ValueError("InstanceAP: picture %d is refused (flag bit %d, flags 0x%02x): %s; %d of %d pictures are refused and emit "
-                                 "nothing" % (bad[0], bit, word, why, len(bad), len(flags)))
+            _refuse("InstanceAP", flags, AP_FLAGS, self.k)
             anns = [[dict(g, area=float(pix[j])) if g["area"] < 0 else g for j, g in enumerate(p)] for p, pix in zip(self._annotations, areas)]
             self._records = (recs, anns)
         return self._records[0]
@@ -1631,29 +1658,8 @@ def keypoint_ap_metrics(records, ground_truth, iou_thrs=None, rec_thrs=None, are
     skip = [np.array([_kpt_ignore(g) for g in ground_truth[i]], bool) for i in images]
     area = [np.array([float(g["area"]) for g in ground_truth[i]], np.float64) for i in images]
     recs = [records[i] for i in images]
-    for a, (lo, hi) in enumerate(area_ranges):
-        npig = sum(int((~(s | (v < lo) | (v > hi))).sum()) for s, v in zip(skip, area))
-        if npig == 0:
-            continue
-        for m, max_det in enumerate(max_dets):
-            cut = [r[:max_det] for r in recs]
-            scores = np.concatenate([r["score"] for r in cut]) if cut else np.zeros(0, np.float32)
-            order = np.argsort(-scores, kind="mergesort")
-            shift = np.arange(a * T, a * T + T, dtype=np.uint64)[:, None]
-            word = lambda name: np.concatenate([r[name] for r in cut])[order] if cut else np.zeros(0, np.uint64)
-            dtm, ign = (word("matched")[None] >> shift) & np.uint64(1) != 0, (word("ignored")[None] >> shift) & np.uint64(1) != 0
-            tp = np.cumsum(dtm & ~ign, axis=1).astype(np.float64)
-            fp = np.cumsum(~dtm & ~ign, axis=1).astype(np.float64)
-            nd = tp.shape[1]
-            for t in range(T):
-                rc = tp[t] / npig
-                pr = tp[t] / (fp[t] + tp[t] + np.spacing(1))
-                recall[t, 0, a, m] = rc[-1] if nd else 0
-                pr = np.maximum.accumulate(pr[::-1])[::-1]
-                at = np.searchsorted(rc, rec_thrs, side="left")
-                q = np.zeros(R)
-                q[at < nd] = pr[at[at < nd]]
-                precision[t, :, 0, a, m] = q
+    npig = [sum(int((~(s | (v < lo) | (v > hi))).sum()) for s, v in zip(skip, area)) for lo, hi in area_ranges]
+    _coco_accumulate([(r["score"], r["matched"], r["ignored"]) for r in recs], npig, T, rec_thrs, max_dets, precision[:, :, 0], recall[:, 0])
     at = lambda v: np.flatnonzero(iou_thrs == v)
     res = {}
     for name, table in (("AP", precision), ("AR", recall)):
@@ -1687,12 +1693,9 @@ class KeypointAP:
         self.sigmas = np.array(sigmas, np.float64).ravel()
         self.k = len(self.sigmas)
         self.vis_thr, self.oks_thr, self.use_nms = float(vis_thr), float(oks_thr), bool(use_nms)
-        self.iou_thrs = np.linspace(.5, .95, 10) if iou_thrs is None else np.array(iou_thrs, np.float64).ravel()
-        self.area_ranges = np.array(KPT_AREA_RANGES if area_ranges is None else area_ranges, np.float64).reshape(-1, 2)
-        self.max_dets = tuple(int(m) for m in max_dets)
+        self.iou_thrs, self.area_ranges, self.max_dets, ok = _coco_params(iou_thrs, KPT_AREA_RANGES if area_ranges is None else area_ranges, max_dets)
         self.heatmap_size = (int(heatmap_size[0]), int(heatmap_size[1]))
-        if not 1 <= self.k <= 32 or not 1 <= len(self.iou_thrs) * len(self.area_ranges) <= 64 or not self.max_dets or \
-                not 1 <= max(self.max_dets) <= KPT_MAX_EVAL or min(self.heatmap_size) < 1 or not self.oks_thr >= 0:
+        if not 1 <= self.k <= 32 or not ok or not 1 <= max(self.max_dets) <= KPT_MAX_EVAL or min(self.heatmap_size) < 1 or not self.oks_thr >= 0:
             raise ValueError("KeypointAP: %d keypoints (1 .. 32), %d thresholds x %d area ranges (at most 64 together), max_dets %s (1 .. %d), "
                              "heat map %s, oks_thr %s (>= 0)" % (self.k, len(self.iou_thrs), len(self.area_ranges), self.max_dets, KPT_MAX_EVAL,
                                                                 self.heatmap_size, oks_thr))
@@ -1822,36 +1825,26 @@ class KeypointAP:
         for j, image in enumerate(images):
             sections += [("rows%d" % j, np.int32, len(groups[image]), 4), ("kp%d" % j, np.float64, self._gt[image][0].size, 8),
                          ("gt%d" % j, KPT_GT, len(self._gt[image][1]), 8)]
-        at, size = _layout(sections)
-        host = torch.zeros(size, dtype=torch.uint8).pin_memory()
-        dev = torch.empty(size, dtype=torch.uint8, device=self.device)
-        a, base = host.numpy(), dev.data_ptr()
+        up = _Upload(sections, self.device)
         jobs = (KptJob * n)()
         for j, (job, image) in enumerate(zip(jobs, images)):
             kp, table = self._gt[image]
-            _section(a, at, "rows%d" % j)[:] = groups[image]
-            _section(a, at, "kp%d" % j)[:] = kp.ravel()
-            _section(a, at, "gt%d" % j)[:] = table
-            job.rows, job.n_box = base + at["rows%d" % j][0], len(groups[image])
+            job.rows, job.n_box = up.put("rows%d" % j, groups[image]), len(groups[image])
             if len(table):
-                job.gt_keypoints, job.gt_table, job.n_gt = base + at["kp%d" % j][0], base + at["gt%d" % j][0], len(table)
-        _section(a, at, "jobs")[:] = np.frombuffer(bytearray(jobs), np.uint8)
-        dev.copy_(host, non_blocking=True)
+                job.gt_keypoints, job.gt_table, job.n_gt = up.put("kp%d" % j, kp.ravel()), up.put("gt%d" % j, table), len(table)
         shape = (n, d_cap, g_cap, max_det)
-        nbytes = lib.pa_kpt_workspace_bytes(*shape)
-        if nbytes < 0:
-            check(1, "pa_kpt_evaluate (sizes %s)" % (shape,))
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        what = "pa_kpt_evaluate (sizes %s)" % (shape,)
+        sent = up.send(jobs)
+        workspace = _workspace(lib.pa_kpt_workspace_bytes, shape, what, self.device)
         oat, osize = _layout([("records", KPT_RECORD, n * max_det, 8), ("counts", np.int32, n, 4), ("survivors", np.int32, n, 4),
                               ("flags", np.uint32, n, 4)])
         out = torch.zeros(osize, dtype=torch.uint8, device=self.device)
         ptr = lambda name: out.data_ptr() + oat[name][0]
         T, A, par = len(self.iou_thrs), len(self.area_ranges), self.params.data_ptr()
-        check(lib.pa_kpt_evaluate(base + at["jobs"][0], n, poses.data_ptr(), scores.data_ptr(), areas.data_ptr(), n_rows, d_cap, g_cap, k, par,
+        check(lib.pa_kpt_evaluate(sent, n, poses.data_ptr(), scores.data_ptr(), areas.data_ptr(), n_rows, d_cap, g_cap, k, par,
                                   self.oks_thr if self.use_nms else -1.0, max_det, par + 8 * k, T, par + 8 * (k + T), A, ptr("records"),
-                                  ptr("counts"), ptr("survivors"), ptr("flags"), workspace.data_ptr(), _stream()),
-              "pa_kpt_evaluate (sizes %s)" % (shape,))
-        self._last_eval = (host, dev, workspace, shape, images)          # the workspace is what the tests read
+                                  ptr("counts"), ptr("survivors"), ptr("flags"), workspace.data_ptr(), _stream()), what)
+        self._last_eval = (up.host, up.dev, workspace, shape, images)          # the workspace is what the tests read
         return out, oat, shape
 
     def records(self):
@@ -1877,12 +1870,8 @@ class KeypointAP:
                     base += out.numel()
                     table, counts = _section(part, oat, "records").reshape(n, max_det), _section(part, oat, "counts")
                     flags, surv = _section(part, oat, "flags"), _section(part, oat, "survivors")
-                    bad = np.flatnonzero(flags)
-                    if len(bad):
-                        word = int(flags[bad[0]])
-                        bit = (word & -word).bit_length() - 1
-                        raise ValueError("KeypointAP: photo %r is refused (flag bit %d, flags 0x%02x): %s; %d of %d photos of this call are "
-                                         "refused and emit nothing" % (images[first + bad[0]], bit, word, KPT_FLAGS[bit], len(bad), n))
+                    _refuse("KeypointAP", flags, KPT_FLAGS, name=lambda i: "photo %r" % (images[first + i],),
+                            rest="photos of this call are refused and emit nothing")
                     for j in range(n):
                         recs[images[first + j]] = table[j, :counts[j]].copy()
                         self.survivors[images[first + j]] = int(surv[j])

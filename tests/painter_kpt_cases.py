@@ -231,6 +231,24 @@ def _mixed_check(case, ref):
         (matched & np.uint64(1) == 0).any()
 
 
+SECOND_WORD = [(93, 70)]           # 70 of the 93 boxes copy a ground truth each, so those of index 64 .. 69 have a box as well
+
+
+def second_word_facts(case, ref):
+    """What the case "second_word" is there for, read from the statement alone: the ground truths of index >= 64 are the second 64-bit
+    word of the kernel's free / ignored / taken bits.  -> (evaluated detections, those that take a ground truth of index >= 64 at range
+    `all`, threshold 0.5, those that take none there, ground truths of index >= 64 ignored in a range other than `all`)."""
+    out, gts = ref[100], case["ground_truth"][100]
+    matched, _, which = H._match(out["oks"], out["records"]["area"], gts, 0.5, *H.AREA_RANGES[0])
+    ignored = [g for g in range(64, len(gts)) if any(H.gt_ignore(gts[g]) or not lo <= float(gts[g]["area"]) <= hi for lo, hi in H.AREA_RANGES[1:])]
+    return len(out["records"]), int((which >= 64).sum()), int((~matched).sum()), len(ignored)
+
+
+def _second_word_check(case, ref):
+    evaluated, high, unmatched, ignored = second_word_facts(case, ref)
+    return evaluated == 64 and high >= 1 and unmatched >= 1 and ignored >= 1
+
+
 # name -> builder; everything the device tests and the measurement use.  EXACT names the cases exempt from the nudge condition.
 CASES = {
     "mixed": lambda: dataset(11, MIXED, check=_mixed_check),
@@ -246,6 +264,7 @@ CASES = {
     "split": lambda: dataset(16, [(7, 2), (5, 3)]),
     "chain": stable_chain,
     "flags": lambda: dataset(17, [(3, 2), (4, 2), (2, 1)]),
+    "second_word": lambda: dataset(18, SECOND_WORD, settings=dict(max_dets=(20, 64)), check=_second_word_check),
 }
 EXACT = ("identical",)                                           # OKS exactly 1.0 at a threshold of 1.0
 

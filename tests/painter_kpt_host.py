@@ -166,12 +166,13 @@ def gt_ignore(g):
 
 
 def _match(oks, dareas, gts, thr, lo, hi):
-    """evaluateImg's loop at one threshold and one range over the detections in order -> matched [E], ignored [E]."""
+    """evaluateImg's loop at one threshold and one range over the detections in order -> matched [E], ignored [E], and which [E]: the
+    ground truth each detection took, -1 for none."""
     ign = [gt_ignore(g) or float(g["area"]) < lo or float(g["area"]) > hi for g in gts]
     crowd = [bool(g.get("iscrowd", 0)) for g in gts]
     gorder = [g for g in range(len(gts)) if not ign[g]] + [g for g in range(len(gts)) if ign[g]]
     taken = set()
-    matched, ignored = np.zeros(len(dareas), bool), np.zeros(len(dareas), bool)
+    matched, ignored, which = np.zeros(len(dareas), bool), np.zeros(len(dareas), bool), -np.ones(len(dareas), np.int64)
     for d in range(len(dareas)):
         best, m = min(thr, 1 - 1e-10), -1
         for g in gorder:
@@ -183,11 +184,11 @@ def _match(oks, dareas, gts, thr, lo, hi):
                 continue
             best, m = oks[d, g], g
         if m > -1:
-            matched[d], ignored[d] = True, ign[m]
+            matched[d], ignored[d], which[d] = True, ign[m], m
             taken.add(m)
         else:
             ignored[d] = dareas[d] < lo or dareas[d] > hi
-    return matched, ignored
+    return matched, ignored, which
 
 
 def photo_flags(pose, scores, areas, gts):
@@ -223,7 +224,7 @@ def photo_records(pose, scores, areas, gts, rows=None, sigmas=SIGMAS, oks_thr=OK
     T = len(iou_thrs)
     for a, (lo, hi) in enumerate(area_ranges):
         for t, thr in enumerate(iou_thrs):
-            matched, ignored = _match(oks, rec["area"], gts, thr, lo, hi)
+            matched, ignored, _ = _match(oks, rec["area"], gts, thr, lo, hi)
             bit = np.uint64(1 << (a * T + t))
             rec["matched"][matched] |= bit
             rec["ignored"][ignored] |= bit

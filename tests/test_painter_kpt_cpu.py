@@ -234,6 +234,13 @@ def test_cases_hold_what_they_are_there_for():
     hand = C.case("hand_made")
     out = hand["statement"][1]
     assert abs(out["oks"][0, 0] - hand["oks"]) <= 1e-15 and out["records"]["matched"].tolist() == [1, 0] and out["alive"].all()
+    second = C.case("second_word")
+    assert [(len(r["order"]), len(second["ground_truth"][i])) for i, r in second["statement"].items()] == C.SECOND_WORD
+    evaluated, high, unmatched, ignored = C.second_word_facts(second, second["statement"])
+    assert evaluated == 64 and high >= 1 and unmatched >= 1 and ignored >= 1, (evaluated, high, unmatched, ignored)
+    # the same three facts in the records' own bits: bit 0 = (all, 0.5); a detection on a ground truth >= 64 has it set, an unmatched one not
+    rec = second["statement"][100]["records"]
+    assert int((rec["matched"] & np.uint64(1) != 0).sum()) == 64 - unmatched
 
 
 def test_a_cpu_device_is_refused():

@@ -123,6 +123,20 @@ def test_mixed_photos_in_one_call():
         assert np.array_equal(np.asarray(res[key]), np.asarray(v)), key
 
 
+def test_ground_truths_of_the_second_word():
+    """70 ground truths, 64 evaluated survivors: ground truths 64 .. 69 are the second 64-bit word of the walk's free / ignored / taken
+    bits.  tests/test_painter_kpt_cpu.py asserts on the statement that one of them is taken at (all, 0.5), one is ignored in another
+    range and one detection stays unmatched; here records, order and survivors are compared as bytes, the OKS within the bar."""
+    case = C.case("second_word")
+    ref = case["statement"]
+    ap = add(scorer(case), case)
+    got = ap.records()
+    same(got, ref)
+    assert len(got[100]) == 64 and ap._last_eval[3] == (1, 93, 70, 64)
+    assert ap.survivors[100] == int(ref[100]["alive"].sum())
+    check_workspace(ap, ref)
+
+
 def test_caps_and_max_det():
     crowded = C.case("crowded")
     ref = crowded["statement"]
