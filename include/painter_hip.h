@@ -593,7 +593,7 @@ int pa_pose_heatmaps(const void* pictures, const void* flipped, const void* pale
                      int n_keypoints, int shift, float* out_heatmaps, hipStream_t stream);
 
 /* Scoring of painted pictures against ground-truth maps, csrc/painter_score.hip: only the sums leave the device;
- * tests/painter_score_host.py is the definition.  Both entry points take a DEVICE job table, one record per picture, pictures of any
+ * tests/painter_score_host.py is the definition.  The entry points take a DEVICE job table, one record per picture, pictures of any
  * sizes in one launch; null pointers, n_jobs outside 1 .. 65535 or the ranges named below return hipErrorInvalidValue before anything is
  * launched. */
 typedef struct pa_score_job {
@@ -610,10 +610,38 @@ typedef struct pa_score_job {
  * grid; a workgroup counts into 32-bit bins in LDS, which a launch of at most 2^31 pixels cannot wrap).  1 <= n_colours <= 255 (gt is a
  * byte).  bins: 0 = the workgroups' private bins are in LDS whenever pa_semseg_lds_bins(n_colours) (n_colours <= 199: 12 n_colours
  * rounded up to 16, plus 4 (n_colours + 1)^2 bytes within 160 KB), else every run of equal neighbours adds to conf_i64 directly; 1 = the
- * direct form at any n_colours (measurements).  Integer atomics only: the result does not depend on their order. */
+ * direct form at any n_colours (measurements).  Integer atomics only: the result does not depend on their order.  The boundary branch
+ * is pa_semseg_boundary_confusion below, which counts this matrix and the boundary matrix in one call. */
 int pa_semseg_lds_bins(int n_colours);
 int pa_semseg_confusion(const pa_score_job* jobs, int n_jobs, int64_t total_pixels, const float* palette, int n_colours, int dist_type,
                         int ignore_label, int bins, void* conf_i64, void* invalid_i64, hipStream_t stream);
+typedef struct pa_boundary_job {
+    const void* picture;        /* uint8 [h][w][3], the painted picture */
+    const void* gt;             /* uint8 [h][w], the ground-truth labels */
+    int32_t h, w;               /* a job with h < 1 or w < 1 adds nothing */
+    int32_t d;                  /* the picture's dilation, >= 1: max(1, round(dilation_ratio * sqrt(h^2 + w^2))), computed by the caller */
+    int32_t reserved;
+} pa_boundary_job;
+/* SemSegEvaluatorCustom.process WITH its boundary branch (ADE20kSemSegEvaluatorCustom.py:103-110, COCOPanoSemSegEvaluatorCustom.py:97-104;
+ * detectron2's SemSegEvaluator._compute_boundary_iou, restated from detectron2's published source and unverified against detectron2 / cv2,
+ * neither of which is available where this project is tested; tests/painter_boundary_host.py is the definition).  conf_i64 and invalid_i64
+ * receive exactly what pa_semseg_confusion adds for the same pictures -- a pixel's class is evaluated once -- and for every pixel of every
+ * job bconf[(n_colours + 1) * boundary(pred) + boundary(gt')] += 1, where boundary(m) = m - eroded(m) and eroded(m)[y][x] = the minimum of
+ * the uint8 map m over rows y - d .. y + d and columns x - d .. x + d with every pixel outside the picture read as 0: cv2.erode by a 3 x 3
+ * square, d iterations, of the map behind a ring of one zero pixel.  The minimum is over label VALUES, as detectron2 erodes the label map
+ * itself.  Any d >= 1 (d >= w or d >= h: everything is boundary); a job with d < 1 enters conf_i64 only.  What a pixel counted in
+ * invalid_i64 adds to bconf is unspecified.  1 <= n_colours <= 254 (detectron2 switches the branch off from 255 classes); bconf_i64:
+ * int64 [(n_colours + 1)^2], 8-byte aligned, accumulated in place; bins as above, for both matrices.  workspace:
+ * pa_semseg_boundary_workspace_bytes(total_pixels) bytes = four byte maps (pred, gt', their row minima) of total_pixels rounded up to 16;
+ * total_pixels is the sum of h * w over the table, 1 .. 2^31, and jobs beyond it are counted in conf_i64 but not in bconf_i64.  Three
+ * launches, integer atomics only. */
+int64_t pa_semseg_boundary_workspace_bytes(int64_t total_pixels);          /* host only; -1 for bad arguments */
+int pa_semseg_boundary_confusion(const pa_boundary_job* jobs, int n_jobs, int64_t total_pixels, const float* palette, int n_colours,
+                                 int dist_type, int ignore_label, int bins, void* conf_i64, void* bconf_i64, void* invalid_i64,
+                                 void* workspace, hipStream_t stream);
+/* boundary(map) of one DEVICE uint8 map [h][w] as above -> out_u8 [h][w], through the scorer's own row and column passes.  h, w, d >= 1,
+ * h * w <= 2^31; workspace: pa_semseg_boundary_workspace_bytes(h * w) (one map of it is used). */
+int pa_label_boundary(const void* map_u8, int h, int w, int d, void* out_u8, void* workspace, hipStream_t stream);
 typedef struct pa_depth_job {
     const void* pred;           /* int32 [h][w], what pa_painter_decode_depth writes */
     const void* gt;             /* uint16 [h][w], the ground-truth depth PNG's values */

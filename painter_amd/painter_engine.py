@@ -31,7 +31,10 @@ from the bytes of the two pictures -- no heat map in memory, 51 floats per box b
 (csrc/painter_score.hip): the confusion matrix of SemSegEvaluatorCustom.process (ADE20kSemSegEvaluatorCustom.py:75-112,
 COCOPanoSemSegEvaluatorCustom.py:67-106) accumulated on the device over a whole data set -- one launch per batch, nothing copied back
 until `matrix()` -- and per picture the ten sums behind the nine numbers of nyuv2_depth/eval_with_pngs.py:50-71, 148-217
-(tests/painter_score_host.py is the definition).
+(tests/painter_score_host.py is the definition).  `SemsegBoundaryScore` adds the evaluators' boundary-IoU branch (:103-110 / :97-104,
+detectron2's `_compute_boundary_iou`): both label maps eroded on the device by a separable window minimum and a second joint histogram
+beside the first, from one evaluation of the classes; `label_boundary` is the erosion alone (tests/painter_boundary_host.py is the
+definition; restated from detectron2's published source and unverified against detectron2 / cv2).
 
 `restoration_scores`, `RestorationScores` and `PainterEngine.run_restoration_scores` score restored pictures (csrc/painter_restore.hip):
 PSNR and SSIM as painter_inference_lol.py:166-169 asks them of skimage (metric "skimage") or as derain's evaluate_PSNR_SSIM.m computes
@@ -63,8 +66,8 @@ Stays on the host, by design: file decode / encode; the depth script's one-off p
 canvases the script built, or pass an already resized 448 x 448 uint8 query to `run`) and its eval_sidd.m (MATLAB's built-in ssim /
 psnr); of the detectron2
 evaluators what is left after the colour -> class decode (`class_map`), the confusion count (`SemsegScore`), the instance decode
-(`instances`) and the panoptic merge (`panoptic`): the boundary-IoU branch (`_compute_boundary_iou`, cv2 erosion), `encode_json_sem_seg`
-and its RLE, the final ratios of `evaluate` (`SemsegScore.scores` restates them on the host); of the depth evaluation its KITTI branches
+(`instances`), the panoptic merge (`panoptic`) and the boundary-IoU branch (`SemsegBoundaryScore`): `encode_json_sem_seg`
+and its RLE, the final ratios of `evaluate` (`semseg_scores` restates them on the host); of the depth evaluation its KITTI branches
 (`do_kb_crop`, `garg_crop`) and the division of the sums;
 PNG encoding, RLE and COCOeval's box AP (mask AP: `InstanceAP`); of the pose route soft_oks_nms, rle_score and the JSON file (keypoint AP: `KeypointAP`).
 
@@ -80,6 +83,7 @@ There is no CPU fallback: a CPU device or a missing libpainter_hip.so raises.
 import contextlib
 import ctypes
 import functools
+import math
 
 import numpy as np
 import torch
@@ -562,6 +566,12 @@ class ScoreJob(ctypes.Structure):
     _fields_ = [("picture", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
 
 
+class BoundaryJob(ctypes.Structure):
+    """pa_boundary_job of include/painter_hip.h."""
+    _fields_ = [("picture", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("d", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class DepthJob(ctypes.Structure):
     """pa_depth_job of include/painter_hip.h."""
     _fields_ = [("pred", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("y0", ctypes.c_int32),
@@ -576,12 +586,47 @@ def _same_sizes(who, pictures, gts):
             raise ValueError("%s: picture %d is %s, its ground truth %s" % (who, i, tuple(p.shape[:2]), tuple(g.shape)))
 
 
-def semseg_scores(matrix):
+def _positive_ratio(who, dilation_ratio):
+    ratio = float(dilation_ratio)
+    if not (np.isfinite(ratio) and ratio > 0):
+        raise ValueError("%s: dilation_ratio is a finite number > 0, not %r" % (who, dilation_ratio))
+    return ratio
+
+
+def boundary_dilation(h, w, dilation_ratio=0.02):
+    """The erosion count of detectron2's SemSegEvaluator._mask_to_boundary for a picture of h x w: `int(round(dilation_ratio *
+    sqrt(h^2 + w^2)))` in float64 with Python's round (half to even), at least 1."""
+    h, w = int(h), int(w)
+    return max(1, int(round(_positive_ratio("boundary_dilation", dilation_ratio) * math.sqrt(h * h + w * w))))
+
+
+def label_boundary(label_map, dilation_ratio=0.02, device="cuda"):
+    """What the boundary branch makes of one label map, uint8 [H][W] (numpy or CUDA tensor) -> uint8 numpy [H][W]: the map minus its
+    erosion by a 3 x 3 square, `boundary_dilation(H, W, dilation_ratio)` times, behind a ring of zeros (pa_label_boundary: the row and
+    column passes of `SemsegBoundaryScore`).  The minimum is over label values, as detectron2 erodes the label map itself; restated from
+    detectron2's published source and unverified against detectron2 / cv2."""
+    ratio = _positive_ratio("label_boundary", dilation_ratio)
+    device = _device([label_map], device)
+    m = _maps(label_map, device, torch.uint8)
+    h, w = int(m.shape[0]), int(m.shape[1])
+    if h < 1 or w < 1:
+        return np.zeros((h, w), np.uint8)
+    what = "pa_label_boundary (%d x %d)" % (h, w)
+    workspace = _workspace(lib.pa_semseg_boundary_workspace_bytes, (h * w,), what, device)
+    out = torch.empty((h, w), dtype=torch.uint8, device=device)
+    check(lib.pa_label_boundary(m.data_ptr(), h, w, boundary_dilation(h, w, ratio), out.data_ptr(), workspace.data_ptr(), _stream()), what)
+    return out.cpu().numpy()
+
+
+def semseg_scores(matrix, boundary_matrix=None):
     """detectron2's SemSegEvaluator.evaluate (detectron2/evaluation/sem_seg_evaluation.py) from the confusion matrix int64
     [K + 1][K + 1] (rows = predictions, columns = ground truth, the last column = ignored pixels), in float64: -> dict(mIoU, fwIoU, mACC,
     pACC in percent, IoU and ACC float64 [K] in percent, NaN for a class without ground-truth pixels).  A class that the ground truth does
     not show is left out of every mean (the release with the boundary-IoU branch, which the reference's evaluators are written against);
-    the ignore column and the (empty) ignore row enter nothing.
+    the ignore column and the (empty) ignore row enter nothing.  With `boundary_matrix` (`SemsegBoundaryScore.boundary_matrix()`) two more
+    keys, float64 [K] in percent: BoundaryIoU = diagonal / union of the boundary matrix, NaN where the union is empty (no condition on the
+    ground truth here), and minIoU_BIoU, the evaluator's `min(IoU, B-Iou)` with Python's min -- the boundary IoU where it is smaller,
+    else the IoU, so a NaN IoU stays NaN and a NaN boundary IoU gives the IoU.
     Restated from detectron2's published source; detectron2 is not available where this project is tested, so the formulas are
     unverified against detectron2."""
     conf = np.asarray(matrix)
@@ -602,7 +647,17 @@ def semseg_scores(matrix):
     miou = iou[iou_valid].sum() / iou_valid.sum() if iou_valid.any() else np.nan
     fiou = (iou[iou_valid] * class_weight[iou_valid]).sum()
     pacc = tp.sum() / pos_gt.sum() if pos_gt.sum() else np.nan
-    return dict(mIoU=100 * miou, fwIoU=100 * fiou, mACC=100 * macc, pACC=100 * pacc, IoU=100 * iou, ACC=100 * acc)
+    res = dict(mIoU=100 * miou, fwIoU=100 * fiou, mACC=100 * macc, pACC=100 * pacc, IoU=100 * iou, ACC=100 * acc)
+    if boundary_matrix is not None:
+        b_conf = np.asarray(boundary_matrix)
+        assert b_conf.shape == conf.shape, (b_conf.shape, conf.shape)
+        b_tp = b_conf.diagonal()[:-1].astype(np.float64)
+        b_union = b_conf[:-1, :-1].sum(axis=0).astype(np.float64) + b_conf[:-1, :-1].sum(axis=1).astype(np.float64) - b_tp
+        b_iou = np.full(k, np.nan)
+        b_iou[b_union > 0] = b_tp[b_union > 0] / b_union[b_union > 0]
+        with np.errstate(invalid="ignore"):
+            res.update(BoundaryIoU=100 * b_iou, minIoU_BIoU=100 * np.where(b_iou < iou, b_iou, iou))
+    return res
 
 
 class SemsegScore:
@@ -617,9 +672,12 @@ class SemsegScore:
         self.k, self.dist_type, self.ignore_label = int(pal.shape[0]), dist_type, int(ignore_label)
         self.bins = 0                                        # pa_semseg_confusion's `bins`: 1 forces the direct form (tools/painter_score_bench.py)
         self.palette = torch.from_numpy(pal).to(self.device)
-        self.at, size = _layout([("conf", np.int64, (self.k + 1) ** 2, 8), ("invalid", np.int64, 1, 8)])
+        self.at, size = _layout(self._sections())
         self.out = torch.zeros(size, dtype=torch.uint8, device=self.device)
         self._last = None
+
+    def _sections(self):
+        return [("conf", np.int64, (self.k + 1) ** 2, 8), ("invalid", np.int64, 1, 8)]
 
     def reset(self):
         self.out.zero_()
@@ -635,32 +693,85 @@ class SemsegScore:
             return self
         pics = [_pictures(p, self.device) for p in pictures]
         maps = [_maps(g, self.device, torch.uint8) for g in gts]
+        self._last = (pics, maps) + tuple(self._launch(pics, maps))          # what the enqueued launches read, until the next call
+        return self
+
+    def _launch(self, pics, maps):
+        """The call of the library for one list -> what it reads besides the pictures and maps."""
         jobs = (ScoreJob * len(pics))()
         for job, p, g in zip(jobs, pics, maps):
             job.picture, job.gt, job.h, job.w = p.data_ptr(), g.data_ptr(), int(p.shape[0]), int(p.shape[1])
         total = sum(int(p.shape[0]) * int(p.shape[1]) for p in pics)
         host, table = _job_table(jobs, self.device)
-        ptr = lambda name: self.out.data_ptr() + self.at[name][0]
         check(lib.pa_semseg_confusion(table.data_ptr(), len(pics), total, self.palette.data_ptr(), self.k, DIST_TYPES[self.dist_type],
-                                      self.ignore_label, self.bins, ptr("conf"), ptr("invalid"), _stream()),
+                                      self.ignore_label, self.bins, self._ptr("conf"), self._ptr("invalid"), _stream()),
               "pa_semseg_confusion (%d jobs, %d pixels, %d colours)" % (len(pics), total, self.k))
-        self._last = (pics, maps, host, table)               # what the enqueued launch reads, until the next one
-        return self
+        return host, table
 
-    def matrix(self):
-        """The one copy back (and synchronisation) -> int64 numpy [K + 1][K + 1], rows = predicted class, columns = ground truth with
-        the ignored pixels in column K.  ValueError if a ground-truth value in [K, 255] other than the ignore label was met."""
+    def _ptr(self, name):
+        return self.out.data_ptr() + self.at[name][0]
+
+    def _matrix(self, name):
         a = self.out.cpu().numpy()
         invalid = int(_section(a, self.at, "invalid")[0])
         if invalid > 0:
             raise ValueError("SemsegScore: %d ground-truth pixels hold a label >= %d that is not the ignore label %d"
                              % (invalid, self.k, self.ignore_label))
-        return _section(a, self.at, "conf").reshape(self.k + 1, self.k + 1).copy()
+        return _section(a, self.at, name).reshape(self.k + 1, self.k + 1).copy()
+
+    def matrix(self):
+        """The one copy back (and synchronisation) -> int64 numpy [K + 1][K + 1], rows = predicted class, columns = ground truth with
+        the ignored pixels in column K.  ValueError if a ground-truth value in [K, 255] other than the ignore label was met."""
+        return self._matrix("conf")
 
     def scores(self):
         """`semseg_scores(self.matrix())`: mIoU, fwIoU, mACC, pACC, IoU and ACC per class, on the host in float64 -- detectron2's
         formulas restated, unverified against detectron2."""
         return semseg_scores(self.matrix())
+
+
+class SemsegBoundaryScore(SemsegScore):
+    """`SemsegScore` with the evaluators' boundary-IoU branch (ADE20kSemSegEvaluatorCustom.py:103-110, COCOPanoSemSegEvaluatorCustom.py:
+    97-104): besides the confusion matrix, the joint histogram of `label_boundary` of the class map and of the ground truth (its ignore
+    label replaced by K), both kept on the device (pa_semseg_boundary_confusion).  A pixel's class is evaluated once for both; the class
+    maps never leave the device.  A picture's erosion count is `boundary_dilation(H, W, dilation_ratio)`.  K <= 254: detectron2 switches
+    the branch off from 255 classes.  detectron2's _compute_boundary_iou restated from its published source, unverified against
+    detectron2 / cv2 (tests/painter_boundary_host.py is the definition)."""
+
+    def __init__(self, palette, dist_type="abs", ignore_label=255, dilation_ratio=0.02, device="cuda"):
+        if len(palette) > 254:
+            raise ValueError("SemsegBoundaryScore: %d classes -- detectron2 computes boundary IoU only for fewer than 255 classes (the "
+                             "ignore label becomes class K in a uint8 map); use SemsegScore" % len(palette))
+        self.dilation_ratio = _positive_ratio("SemsegBoundaryScore", dilation_ratio)
+        self.workspace = None
+        super().__init__(palette, dist_type, ignore_label, device)
+
+    def _sections(self):
+        return super()._sections() + [("bconf", np.int64, (self.k + 1) ** 2, 8)]
+
+    def _launch(self, pics, maps):
+        jobs = (BoundaryJob * len(pics))()
+        for job, p, g in zip(jobs, pics, maps):
+            job.picture, job.gt, job.h, job.w = p.data_ptr(), g.data_ptr(), int(p.shape[0]), int(p.shape[1])
+            job.d = boundary_dilation(job.h, job.w, self.dilation_ratio)
+        total = sum(int(p.shape[0]) * int(p.shape[1]) for p in pics)
+        what = "pa_semseg_boundary_confusion (%d jobs, %d pixels, %d colours)" % (len(pics), total, self.k)
+        if self.workspace is None or self.workspace.numel() < lib.pa_semseg_boundary_workspace_bytes(total):
+            self.workspace = _workspace(lib.pa_semseg_boundary_workspace_bytes, (total,), what, self.device)
+        host, table = _job_table(jobs, self.device)
+        check(lib.pa_semseg_boundary_confusion(table.data_ptr(), len(pics), total, self.palette.data_ptr(), self.k,
+                                               DIST_TYPES[self.dist_type], self.ignore_label, self.bins, self._ptr("conf"), self._ptr("bconf"),
+                                               self._ptr("invalid"), self.workspace.data_ptr(), _stream()), what)
+        return host, table
+
+    def boundary_matrix(self):
+        """As `matrix()`, of the boundary maps -> int64 numpy [K + 1][K + 1], rows = boundary value of the class map, columns = boundary
+        value of the ground truth (0 = not on a boundary).  The same ValueError."""
+        return self._matrix("bconf")
+
+    def scores(self):
+        """`semseg_scores(self.matrix(), self.boundary_matrix())`: the six numbers of `SemsegScore.scores`, BoundaryIoU and minIoU_BIoU."""
+        return semseg_scores(self.matrix(), self.boundary_matrix())
 
 
 def _crop_box(crop, h, w):
@@ -2077,8 +2188,8 @@ class PainterEngine:
         return score
 
     def run_semseg_score(self, pictures, gts, score, sizes=None):
-        """ade20k_semseg / coco_pano_semseg: forward and decode as `run`, then `score.add` (a SemsegScore) of every batch straight from
-        the decode plan's device-resident uint8 output -- the painted pictures are never copied back, and nothing else is before
+        """ade20k_semseg / coco_pano_semseg: forward and decode as `run`, then `score.add` (a SemsegScore or SemsegBoundaryScore) of every batch
+        straight from the decode plan's device-resident uint8 output -- the painted pictures are never copied back, and nothing else is before
         `score.matrix()`.  gts: one uint8 label map per picture, of the painted picture's size (sizes[i], default the query's own).
         -> score."""
         if self.task not in ("ade20k_semseg", "coco_pano_semseg"):
