@@ -9,11 +9,13 @@ kernels ran, Arena.check() asserts that every guard and row-gap byte is still 0x
 still hold the poison.  A plain module: no conftest, no pytest settings."""
 import contextlib
 import math
+import re
 
 import torch
 
 POISON = 0xFF
 GUARD_BYTES = 4 << 20          # each side; more than any overrun a helper of include/painter_hip.h could be short by at the shapes tested
+ALIGN = 256                    # bytes: the base of every payload (pa_inst_decode, pa_pano_decode refuse a workspace that is not 256-byte aligned)
 _INT_OF_SIZE = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
 
 
@@ -42,7 +44,7 @@ class _Alloc:
 
 class Arena:
     def __init__(self, device, guard_bytes=GUARD_BYTES):
-        assert guard_bytes >= 16 and guard_bytes % 16 == 0
+        assert guard_bytes >= ALIGN and guard_bytes % ALIGN == 0          # (so that the payload starts on the buffer's own alignment)
         self.device = torch.device(device)
         self.guard = guard_bytes
         self.allocs = []
@@ -65,8 +67,10 @@ class Arena:
             rows, pitch, off, row_bytes = shape[0], ld * es, col_off * es, shape[1] * es
         payload = rows * pitch
         tail = self.guard + (-payload) % 16                     # (the buffer stays a multiple of 16 bytes; the pad belongs to the guard)
-        buf = torch.full((self.guard + payload + tail,), POISON, dtype=torch.uint8, device=self.device)
-        assert buf.data_ptr() % 16 == 0
+        raw = torch.full((self.guard + payload + tail + ALIGN,), POISON, dtype=torch.uint8, device=self.device)
+        skip = -raw.data_ptr() % ALIGN                          # (0 from the device allocator; the host allocator aligns to 64 only)
+        buf = raw[skip:skip + self.guard + payload + tail]
+        assert (buf.data_ptr() + self.guard) % ALIGN == 0, "the payload of an arena allocation starts on a %d-byte boundary" % ALIGN
         flat = buf[self.guard:self.guard + payload].view(dtype)
         t = flat.view(shape) if ld is None else flat.view(rows, ld)[:, col_off:col_off + shape[1]]
         self.allocs.append(_Alloc(name or "#%d %s %s" % (len(self.allocs), tuple(shape), str(dtype).replace("torch.", "")), buf, self.guard, payload,
@@ -126,25 +130,73 @@ class TorchProxy:
     def empty_like(self, t, dtype=None, device=None, **kw):
         if not self._arena.owns(device if device is not None else t.device):
             return self._real.empty_like(t, dtype=dtype, device=device, **kw)
-        assert not kw, kw
+        fmt = kw.pop("memory_format", torch.preserve_format)               # (the arena's layout is contiguous: torch's own for every tensor met here)
+        assert not kw and fmt in (torch.preserve_format, torch.contiguous_format), (kw, fmt)
         return self._arena.empty(t.shape, dtype if dtype is not None else t.dtype)
+
+    # zeros / zeros_like / full: an arena allocation filled afterwards -- the payload holds the value, the guards stay 0xFF
+    def zeros(self, *size, dtype=None, device=None, **kw):
+        if not self._arena.owns(device):
+            return self._real.zeros(*size, dtype=dtype, device=device, **kw)
+        return self.empty(*size, dtype=dtype, device=device, **kw).zero_()
+
+    def zeros_like(self, t, dtype=None, device=None, **kw):
+        if not self._arena.owns(device if device is not None else t.device):
+            return self._real.zeros_like(t, dtype=dtype, device=device, **kw)
+        return self.empty_like(t, dtype=dtype, device=device, **kw).zero_()
+
+    def full(self, size, fill_value, dtype=None, device=None, **kw):
+        if not self._arena.owns(device):
+            return self._real.full(size, fill_value, dtype=dtype, device=device, **kw)
+        if dtype is None:                                          # torch.full's own rule
+            dtype = torch.bool if isinstance(fill_value, bool) else torch.int64 if isinstance(fill_value, int) else self._real.get_default_dtype()
+        return self.empty(size, dtype=dtype, device=device, **kw).fill_(fill_value)
+
+
+class CountingLib:
+    """Stands in for the module-level name `lib` of the module under test: counts the calls per pa_* symbol and forwards everything, so a
+    case can prove which C entry points it reached."""
+
+    def __init__(self, real):
+        self.__dict__["_real"] = real
+        self.__dict__["calls"] = {}
+
+    def __getattr__(self, name):
+        f = getattr(self._real, name)
+        if not name.startswith("pa_") or not callable(f):
+            return f
+
+        def counted(*a, **k):
+            self.calls[name] = self.calls.get(name, 0) + 1
+            return f(*a, **k)
+        return counted
+
+
+def abi_symbols(header_text):
+    """The pa_* function names declared in the text of include/painter_hip.h.  Comments are dropped first: they quote calls and older
+    declarations."""
+    src = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", header_text, flags=re.S))
+    return set(re.findall(r"\b(?:int64_t|int)\s+(pa_\w+)\s*\([^;{}]*\)\s*;", src))
 
 
 @contextlib.contextmanager
-def guarded_ops(monkeypatch, arena, ops=None):
+def guarded_ops(monkeypatch, arena, ops=None, exact_workspace=False):
     """For the duration of the block every tensor painter_amd.ops allocates -- outputs, side outputs, scratch -- is an exact-size, poisoned,
     guarded arena tensor: `torch` inside the module is a TorchProxy, and ops.workspace returns exactly the requested bytes (rounded up to
-    16, never less than 16).  -> the list of (requested bytes, tensor) of the workspace calls made."""
+    16, never less than 16).  `ops` may be any module that allocates through its name `torch`; one without a `workspace` attribute
+    (painter_engine, seggpt_engine, pair_pipeline) gets none.  exact_workspace: ops.workspace returns the requested bytes without the
+    rounding (a helper that returns 8 bytes gets 8).  -> the list of (requested bytes, tensor) of the workspace calls made."""
     if ops is None:
         from painter_amd import ops
     calls = []
 
     def workspace(nbytes, device, slot=0):
-        t = arena.empty((max(roundup(nbytes, 16), 16),), torch.uint8, name="workspace #%d (%d bytes asked, slot %d)" % (len(calls), nbytes, slot))
+        t = arena.empty((int(nbytes) if exact_workspace else max(roundup(nbytes, 16), 16),), torch.uint8, name="workspace #%d (%d bytes asked, slot %d)" % (len(calls), nbytes, slot))
         calls.append((int(nbytes), t))
         return t
 
     with monkeypatch.context() as m:
         m.setattr(ops, "torch", TorchProxy(torch, arena))
-        m.setattr(ops, "workspace", workspace)
+        if hasattr(ops, "workspace"):
+            m.setattr(ops, "workspace", workspace)
         yield calls
