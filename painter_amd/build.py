@@ -62,6 +62,7 @@ def sources():
 def headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_hip.h"))
+    hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_rle.h"))
     return sorted(hs)
 
 

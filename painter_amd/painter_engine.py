@@ -60,6 +60,13 @@ evaluateImg per photo, read from the pose decode's device-resident preds and max
 summarize run on the host (`keypoint_ap_metrics`; tests/painter_kpt_host.py is the definition; mmpose's oks_nms and xtcocotools' COCOeval
 are restated from their published source and unverified against mmpose / xtcocotools).
 
+`rle_encode`, `rle_decode`, `instance_results` and `run_instance_results` are COCO's run-length encoding on the device
+(csrc/painter_rle.hip, include/painter_rle.h): bit masks -> the `{"size", "counts"}` strings, areas and boxes of pycocotools.mask.encode, and
+strings or uncompressed counts -> bit masks.  The instance evaluators' whole output is coco_instances_results.json
+(COCOCAInstSegEvaluatorCustom.py:119, :147-170): `instance_results` chains the encode behind the instance decode, so scores and strings come
+back instead of the bool masks, and every `masks=` argument also takes a list of RLE dicts (a detections JSON, crowd ground truth)
+(tests/painter_rle_host.py is the definition; restated from pycocotools' published maskApi.c and unverified against pycocotools).
+
 Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
 (`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
 `cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
@@ -69,7 +76,7 @@ evaluators what is left after the colour -> class decode (`class_map`), the conf
 (`instances`), the panoptic merge (`panoptic`) and the boundary-IoU branch (`SemsegBoundaryScore`): `encode_json_sem_seg`
 and its RLE, the final ratios of `evaluate` (`semseg_scores` restates them on the host); of the depth evaluation its KITTI branches
 (`do_kb_crop`, `garg_crop`) and the division of the sums;
-PNG encoding, RLE and COCOeval's box AP (mask AP: `InstanceAP`); of the pose route soft_oks_nms, rle_score and the JSON file (keypoint AP: `KeypointAP`).
+PNG encoding and COCOeval's box AP (mask AP: `InstanceAP`; RLE: `rle_encode` / `rle_decode`); of the pose route soft_oks_nms, rle_score and the JSON file (keypoint AP: `KeypointAP`).
 
 One host path serves the routes: `_device` / `_pictures` put the inputs of a call on one indexed CUDA device; INSTANCE_DEFAULTS,
 MERGE_DEFAULTS, POSE_DEFAULTS and DEPTH_DEFAULTS hold the keyword defaults and `_check_arguments` refuses the rest before a forward is enqueued; an output
@@ -1005,10 +1012,15 @@ def _host_array(values, dtype):
 
 
 def _bit_masks(masks, h, w, device):
-    """bool / uint8 [n][H][W] (numpy or CUDA tensor), or bit masks uint32 [n][ceil(H W / 32)] (the `bits` of an InstanceDecode) -> int32
-    CUDA tensor [max(n, 1)][words] in pa_inst_decode's bit layout, n.  device: what `_device` returned for the call; a mask tensor
-    anywhere else is refused."""
+    """bool / uint8 [n][H][W] (numpy or CUDA tensor), bit masks uint32 [n][ceil(H W / 32)] (the `bits` of an InstanceDecode), or a list of
+    COCO RLE dicts (size, counts; a detections JSON's segmentations, crowd ground truth: `rle_decode`) -> int32 CUDA tensor
+    [max(n, 1)][words] in pa_inst_decode's bit layout, n.  device: what `_device` returned for the call; a mask tensor anywhere else is
+    refused."""
     words = (h * w + 31) // 32
+    if _is_rles(masks):
+        if _rle_size(masks) != (h, w):
+            raise ValueError("painter_engine: the RLE masks are %s, the picture %s" % (_rle_size(masks), (h, w)))
+        return rle_decode(masks, device), len(masks)
     if torch.is_tensor(masks):
         if _device([masks]) != device:                               # a host or foreign address must never reach a kernel
             raise RuntimeError("painter_engine: the masks are on %s, the picture on %s" % (masks.device, device))
@@ -1153,7 +1165,8 @@ def panoptic(semseg_picture, inst_picture=None, *, instances=None, semseg_palett
 
     inst_picture: the painted `coco_pano_inst` picture; it is decoded as `instances(inst_picture, **instances_kw)` does and the merge is
     chained behind that decode on the device -- one output buffer, one copy back, one synchronisation.  Or instances = dict(masks= bool /
-    uint8 [n][H][W] (numpy or a CUDA tensor on the picture's device), scores= [n], classes= [n] or None (lists, numpy or tensors; they
+    uint8 [n][H][W] (numpy or a CUDA tensor on the picture's device) or a list of COCO RLE dicts (a detections JSON's segmentations,
+    decoded on the device: `rle_decode`), scores= [n], classes= [n] or None (lists, numpy or tensors; they
     are read on the host)) for pre-computed instances (:229-248); given classes skip the vote.
 
     -> dict(panoptic int32 [H][W] (0 = unassigned), segments = list of dicts as the reference builds them (things: id, isthing, score,
@@ -1517,7 +1530,7 @@ class InstanceAP:
     COCOInstSegEvaluatorCustom.py:315-329).  Classes are indices 0 .. n_classes - 1; categories = [ids] (or dicts with `id`) names the data
     set's own ids instead: `category_id`s and classes handed to `add` are mapped through it on the host (an id it does not hold refuses
     the picture), the classes of `add_decodes` come from the device and stay indices.  At most 128 detections and 128 ground truths per
-    picture, len(area_ranges) * len(iou_thrs) <= 64.  Polygon / RLE decoding, box AP, the class-wise re-NMS route and JSON I/O are not here."""
+    picture, len(area_ranges) * len(iou_thrs) <= 64.  Masks may be lists of COCO RLE dicts (`rle_decode`).  Polygon decoding, box AP, the class-wise re-NMS route and JSON I/O are not here."""
 
     def __init__(self, n_classes=80, modes=("agnostic",), iou_thrs=None, area_ranges=None, max_dets=(1, 10, 100), categories=None,
                  device="cuda"):
@@ -1558,12 +1571,16 @@ class InstanceAP:
             raise RuntimeError("painter_engine: this InstanceAP lives on %s" % self.device)
         gbits, tables = [], []
         for i, (d, g, anns) in enumerate(zip(dets, gt_masks, gt_annotations)):
-            if not torch.is_tensor(g):
-                g = np.asarray(g)
-            if g.ndim == 3 and len(g) and tuple(g.shape[1:]) != (d[0], d[1]):
-                raise ValueError("InstanceAP: the detections of picture %d are %s, its ground truth %s" % (i, (d[0], d[1]), tuple(g.shape[1:])))
-            if len(g) == 0:
-                g = np.zeros((0, d[0], d[1]), bool)
+            if _is_rles(g):                                  # RLE ground truth (crowd annotations): decoded on the device by _bit_masks
+                if _rle_size(g) != (d[0], d[1]):
+                    raise ValueError("InstanceAP: the detections of picture %d are %s, its ground truth %s" % (i, (d[0], d[1]), _rle_size(g)))
+            else:
+                if not torch.is_tensor(g):
+                    g = np.asarray(g)
+                if g.ndim == 3 and len(g) and tuple(g.shape[1:]) != (d[0], d[1]):
+                    raise ValueError("InstanceAP: the detections of picture %d are %s, its ground truth %s" % (i, (d[0], d[1]), tuple(g.shape[1:])))
+                if len(g) == 0:
+                    g = np.zeros((0, d[0], d[1]), bool)
             bits, n_gt = _bit_masks(g, d[0], d[1], self.device)
             if n_gt != len(anns):
                 raise ValueError("InstanceAP: picture %d has %d ground-truth masks and %d annotations" % (i, n_gt, len(anns)))
@@ -1615,7 +1632,8 @@ class InstanceAP:
     def add(self, masks, scores, classes, gt_masks, gt_annotations, sizes=None):
         """Lists with one entry per picture.  masks: bool / uint8 [n][H][W] (numpy or CUDA tensor) or uint32 bit masks [n][ceil(H W / 32)]
         (then the size is that of the ground-truth masks, or sizes[i] = (H, W) where both sides are bit masks); scores: [n]; classes: [n] or None (class 0, "agnostic" only); classes may also
-        be None as a whole.  gt_masks: likewise [G][H][W]; gt_annotations: per picture dicts(category_id, iscrowd, area; area None = the
+        be None as a whole.  gt_masks: likewise [G][H][W], or per picture a list of RLE dicts (size, counts: crowd ground truth as COCO
+        stores it; also accepted for `masks`); gt_annotations: per picture dicts(category_id, iscrowd, area; area None = the
         mask's pixel count).  Detections are taken as they are handed over: a picture without any has none (the reference's single empty
         detection is what `instances` returns for such a picture).  Nothing is copied back.  -> self."""
         masks, scores, gt_masks, gt_annotations = list(masks), list(scores), list(gt_masks), list(gt_annotations)
@@ -1631,6 +1649,7 @@ class InstanceAP:
             if c is None and "per_class" in self.modes:
                 raise ValueError("InstanceAP.add: picture %d has no classes, which mode \"per_class\" needs" % i)
             shape = next((tuple(int(v) for v in x.shape[1:]) for x in (m, g) if hasattr(x, "shape") and len(x.shape) == 3), None)
+            shape = next((_rle_size(x) for x in (m, g) if _is_rles(x)), None) if shape is None else shape
             shape = shape if sizes is None else (int(sizes[i][0]), int(sizes[i][1]))
             if shape is None:
                 raise ValueError("InstanceAP.add: picture %d gives bit masks on both sides, so its size is unknown" % i)
@@ -1732,6 +1751,238 @@ def run_instance_ap(inst_engine, pictures, gt_masks, gt_annotations, score, size
 
 
 # ---- COCO keypoint AP (csrc/painter_kpt.hip)
+# ---- COCO RLE (csrc/painter_rle.hip, include/painter_rle.h)
+RLE_HEADER = np.dtype([("runs", np.int64), ("chars", np.int64), ("overflow", np.int64), ("count", np.int64)])       # pa_rle_header
+RLE_RECORD = np.dtype([("char_offset", np.int64), ("char_count", np.int64), ("runs", np.uint32), ("area", np.uint32),
+                       ("bbox", np.int32, (4,))])                                                                   # pa_rle_record
+RLE_FLAGS = ("", "the counts do not sum to h * w", "a count is negative after the delta", "the string ends inside a value",
+             "a value has more than 7 groups", "more runs than the workspace was sized for", "the span lies outside the pool",
+             "a byte outside '0' .. 'o'")                                                        # pa_rle_decode's flag values 1 .. 7
+RLE_CHARS_PER_COLUMN = 16          # default pool: 16 characters per column and mask slot (+ 64) -- about five runs of two or three
+                                   # characters per column; an instance blob has two.  More than that takes the second launch.
+
+
+def rle_default_chars(w, n_cap):
+    return int(n_cap) * (RLE_CHARS_PER_COLUMN * int(w) + 64)
+
+
+def _address(x):
+    return x.data_ptr() if torch.is_tensor(x) else int(x)
+
+
+class RleEncode:
+    """One launched pa_rle_encode: bit masks in pa_inst_decode's layout -> COCO RLE strings, areas and boxes (maskApi.c's rleEncode,
+    rleToString, rleArea, rleToBbox; tests/painter_rle_host.py is the definition, restated from pycocotools' published source and
+    unverified against pycocotools).  bits, count: CUDA tensors, or device addresses inside a buffer `keep` holds (the `bits` and
+    `count` sections of an InstanceDecode: the encode then chains behind the decode with no synchronisation).  `result()` copies back
+    header + records and then pool[:total]; if the header reports that the strings did not fit the pool (default:
+    `rle_default_chars`), it launches once more with the exact total it just read -- there is no failure mode and no host encode."""
+
+    def __init__(self, bits, count, h, w, n_cap, char_cap=None, device=None, keep=None):
+        self.keep = (bits, count, keep)
+        self.device = _device([bits, count], device if device is not None else "cuda")
+        self.bits, self.count = _address(bits), _address(count)
+        self.h, self.w, self.n_cap = int(h), int(w), int(n_cap)
+        self.char_cap = rle_default_chars(self.w, self.n_cap) if char_cap is None else int(char_cap)
+        self.launches = 0
+        self.workspace = _workspace(lib.pa_rle_encode_workspace_bytes, (self.h, self.w, self.n_cap),
+                                    "pa_rle_encode (sizes %s)" % ((self.h, self.w, self.n_cap),), self.device)
+        self._launch()
+
+    def _launch(self):
+        # ONE byte buffer: header, records, pool (at least one byte, so that its address is never null)
+        self.at, size = _layout([("header", RLE_HEADER, 1, 8), ("records", RLE_RECORD, self.n_cap, 8), ("pool", np.uint8, max(self.char_cap, 1), 16)])
+        self.out = torch.empty(size, dtype=torch.uint8, device=self.device)
+        ptr = lambda name: self.out.data_ptr() + self.at[name][0]
+        check(lib.pa_rle_encode(self.bits, self.count, self.h, self.w, self.n_cap, self.workspace.data_ptr(), self.char_cap, ptr("header"),
+                                ptr("records"), ptr("pool"), _stream()), "pa_rle_encode")
+        self.launches += 1
+
+    def _head(self):
+        end = self.at["records"][0] + RLE_RECORD.itemsize * self.n_cap
+        a = self.out[:end].cpu().numpy()
+        return a, _section(a, self.at, "header")[0]
+
+    def result(self):
+        """-> dict(header, records RLE_RECORD [count], pool uint8 [total characters], strings: one str per mask)."""
+        a, header = self._head()
+        if header["overflow"]:
+            self.char_cap = int(header["chars"])
+            self._launch()
+            a, header = self._head()
+            assert not header["overflow"]
+        n, total = int(header["count"]), int(header["chars"])
+        records = _section(a, self.at, "records", n)
+        o = self.at["pool"][0]
+        pool = self.out[o:o + total].cpu().numpy()
+        text = pool.tobytes().decode("ascii")
+        strings = [text[int(r["char_offset"]):int(r["char_offset"] + r["char_count"])] for r in records]
+        return dict(header=header, records=records, pool=pool, strings=strings)
+
+
+def _is_rles(x):
+    """A non-empty list of COCO RLE dicts (size, counts)?"""
+    return isinstance(x, (list, tuple)) and len(x) > 0 and all(isinstance(r, dict) and "counts" in r and "size" in r for r in x)
+
+
+def _rle_size(rles):
+    sizes = {(int(r["size"][0]), int(r["size"][1])) for r in rles}
+    if len(sizes) != 1:
+        raise ValueError("painter_engine: the RLE masks of one call have one size, not %s" % sorted(sizes))
+    return sizes.pop()
+
+
+def rle_encode(masks, size=None, device="cuda"):
+    """pycocotools.mask.encode on the device.  masks: bool / uint8 [n][H][W] (numpy or CUDA tensor), or bit masks uint32 / int32
+    [n][ceil(H W / 32)] with size = (H, W) -> (rles, areas, bboxes): a list of {"size": [h, w], "counts": str}, int64 [n], float64 [n][4]
+    (x, y, w, h; zeros for an empty mask)."""
+    device = _device([masks], device)
+    masks = masks if torch.is_tensor(masks) else np.asarray(masks)
+    if size is None:
+        assert len(masks.shape) == 3, "rle_encode: bit masks need size=(H, W)"
+        size = masks.shape[1:]
+    h, w = int(size[0]), int(size[1])
+    bits, n = _bit_masks(masks, h, w, device)
+    count = torch.tensor([n], dtype=torch.int32, device=device)
+    res = RleEncode(bits, count, h, w, int(bits.shape[0])).result()
+    rles = [{"size": [h, w], "counts": s} for s in res["strings"]]
+    return rles, res["records"]["area"].astype(np.int64), res["records"]["bbox"].astype(np.float64).reshape(n, 4)
+
+
+def _launch_rle_decode(rles, h, w, compressed, device):
+    n = len(rles)
+    if compressed:
+        parts = [r["counts"].encode("ascii") if isinstance(r["counts"], str) else bytes(r["counts"]) for r in rles]
+        pool = np.frombuffer(b"".join(parts), np.uint8)
+    else:
+        parts = [np.asarray(r["counts"], dtype=np.int64).ravel() for r in rles]
+        if any(len(p) and (p.min() < 0 or p.max() >= 1 << 32) for p in parts):
+            raise ValueError("rle_decode: uncompressed counts are integers 0 .. 2^32 - 1")
+        pool = np.concatenate(parts + [np.zeros(0, np.int64)]).astype(np.uint32)
+    lengths = np.array([len(p) for p in parts], np.int64)
+    spans = np.stack([np.cumsum(lengths) - lengths, lengths], 1)
+    total = int(lengths.sum())
+    dpool = torch.zeros(max(total, 1), dtype=torch.uint8 if compressed else torch.int32, device=device)
+    if total:
+        dpool[:total].copy_(torch.from_numpy(pool.copy() if compressed else pool.view(np.int32)))
+    dspans = torch.from_numpy(np.ascontiguousarray(spans)).to(device)
+    shape = (n, h, w, total)
+    what = "pa_rle_decode (sizes %s)" % (shape,)
+    workspace = _workspace(lib.pa_rle_decode_workspace_bytes, shape, what, device)
+    bits = torch.empty((n, (h * w + 31) // 32), dtype=torch.int32, device=device)
+    flags = torch.empty(n, dtype=torch.int32, device=device)
+    check(lib.pa_rle_decode(dpool.data_ptr(), int(compressed), dspans.data_ptr(), n, h, w, total, total, workspace.data_ptr(), bits.data_ptr(),
+                            flags.data_ptr(), _stream()), what)
+    return bits, flags, (dpool, dspans, workspace)
+
+
+def rle_decode(rles, device="cuda"):
+    """pycocotools.mask.decode on the device, into bit masks.  rles: dicts {"size": [h, w], "counts": ...} of one size, counts a str /
+    bytes (compressed) or a list of ints (uncompressed, COCO's crowd annotations) -> int32 CUDA tensor [n][ceil(h w / 32)] in
+    pa_inst_decode's bit layout.  A malformed mask raises ValueError naming the mask and its flag (include/painter_rle.h)."""
+    device = _device((), device)
+    rles = list(rles)
+    if not _is_rles(rles):
+        raise ValueError("rle_decode: a non-empty list of dicts with `size` and `counts`")
+    h, w = _rle_size(rles)
+    kinds = np.array([isinstance(r["counts"], (str, bytes, bytearray)) for r in rles])
+    if kinds.all() or not kinds.any():
+        bits, flags, _ = _launch_rle_decode(rles, h, w, bool(kinds[0]), device)
+        flags = flags.cpu().numpy()
+    else:                                                                   # both kinds in one list: one launch each
+        bits = torch.empty((len(rles), (h * w + 31) // 32), dtype=torch.int32, device=device)
+        flags = np.zeros(len(rles), np.int32)
+        for kind in (True, False):
+            idx = np.flatnonzero(kinds == kind)
+            part, f, _ = _launch_rle_decode([rles[i] for i in idx], h, w, kind, device)
+            bits[torch.from_numpy(idx).to(device)] = part
+            flags[idx] = f.cpu().numpy()
+    _refuse("rle_decode", (1 << flags.astype(np.int64)) * (flags != 0), RLE_FLAGS, name=lambda i: "mask %d" % i,
+            rest="masks are refused and decode to nothing")
+    return bits
+
+
+class InstanceResults:
+    """The entries `instances_to_coco_json` builds for one picture (detectron2's function, restated from its published source and
+    unverified), behind a launched InstanceDecode or a PanopticDecode chained behind one: the RLE encode reads bit masks and count where
+    the decode left them; `result()` copies back the prefix of the decode's buffer before its `bits` section (count, scores), the classes
+    of a PanopticDecode and the RLE buffer -- never `masks`."""
+
+    def __init__(self, decode, image_id):
+        inst = decode if isinstance(decode, InstanceDecode) else getattr(decode, "decode", None)
+        if inst is None:
+            raise TypeError("instance_results: neither an InstanceDecode nor a PanopticDecode chained behind one")
+        self.decode, self.inst, self.image_id = decode, inst, image_id
+        base = inst.out.data_ptr()
+        self.encode = RleEncode(base + inst.obits, base + inst.at["count"][0], inst.h, inst.w, inst.max_num, device=inst.out.device, keep=inst.out)
+
+    def result(self):
+        inst = self.inst
+        a = inst.out[:inst.obits].cpu().numpy()
+        n = int(_section(a, inst.at, "count")[0])
+        if n == 0:            # :302-310: one all-zero mask, score 0, label 0.  Slot 0 of the decode's bits is zero then: encode it as one mask
+            one = torch.ones(1, dtype=torch.int32, device=inst.out.device)
+            strings = RleEncode(inst.out.data_ptr() + inst.obits, one, inst.h, inst.w, 1, device=inst.out.device, keep=inst.out).result()["strings"]
+            scores, classes = [0.0], [0]
+        else:
+            strings = self.encode.result()["strings"]
+            scores = [float(s) for s in _section(a, inst.at, "scores", n)]
+            if inst is self.decode:
+                classes = [1] * n
+            else:
+                off = self.decode.at["classes"][0]
+                classes = self.decode.out[off:off + 4 * n].cpu().numpy().view(np.int32).tolist()
+        return [dict(image_id=self.image_id, category_id=int(c), bbox=[0.0, 0.0, 0.0, 0.0], score=s,
+                     segmentation={"size": [inst.h, inst.w], "counts": t}) for c, s, t in zip(classes, scores, strings)]
+
+
+def instance_results(decode, image_id):
+    """The list `instances_to_coco_json` builds from the evaluators' Instances (COCOCAInstSegEvaluatorCustom.py:147; detectron2's
+    function is restated from its published source and unverified), one entry per instance of a launched InstanceDecode or of a
+    PanopticDecode chained behind one: image_id; category_id = the voted class behind a PanopticDecode, otherwise the label 1, and 0 for
+    the empty-prediction mask; bbox = [0.0] * 4, for the evaluators set zero boxes (:246, :350); score = the Python float of the float32;
+    segmentation = {"size": [h, w], "counts": str}, pycocotools.mask.encode's RLE computed on the device (`RleEncode`).  A decode without
+    candidates gives the reference's single entry (:302-310): score 0, category 0, the all-zero mask (counts of [h w])."""
+    return InstanceResults(decode, image_id).result()
+
+
+def run_instance_results(inst_engine, pictures, image_ids, sizes=None, semseg_engine=None, **kw):
+    """`run_instance_ap`'s loop ending in `instance_results`: forwards, decodes and RLE encodes of a batch are all enqueued before the
+    first copy back, and no mask is copied back.  With `semseg_engine` (task coco_pano_semseg) every instance carries the class the
+    panoptic decode's vote gives it.  -> the flat list the evaluator `json.dumps` into coco_instances_results.json."""
+    if inst_engine.task != "coco_pano_inst" or (semseg_engine is not None and semseg_engine.task != "coco_pano_semseg"):
+        raise ValueError("painter_engine: run_instance_results takes a coco_pano_inst engine and, optionally, a coco_pano_semseg engine, not %r and %r"
+                         % (inst_engine.task, None if semseg_engine is None else semseg_engine.task))
+    kw = {k: v for k, v in kw.items() if k != "device"}
+    if semseg_engine is None:
+        _check_arguments("run_instance_results", kw, INSTANCE_DEFAULTS)         # before the first forward is enqueued
+        args = dict(INSTANCE_DEFAULTS, **kw)
+    else:
+        _check_arguments("run_instance_results", kw, INSTANCE_DEFAULTS, MERGE_DEFAULTS)
+        merge = {k: kw.pop(k, v) for k, v in MERGE_DEFAULTS.items()}             # kw keeps what belongs to the instance decode
+        palette, n_things = merge.pop("semseg_palette"), merge.pop("n_things")
+    pictures, image_ids = list(pictures), list(image_ids)
+    sizes = [(p.shape[1], p.shape[0]) for p in pictures] if sizes is None else [(int(w), int(h)) for w, h in sizes]
+    if not (len(pictures) == len(image_ids) == len(sizes)):
+        raise ValueError("run_instance_results: %d pictures, %d image ids, %d sizes" % (len(pictures), len(image_ids), len(sizes)))
+
+    def batch(items, sizes):
+        pics, step = [p for p, _ in items], inst_engine.batch_size
+        sem = None if semseg_engine is None else semseg_engine._launch_batch(pics, sizes, False)
+        jobs = []
+        for j in range(0, len(pics), step):
+            inst = inst_engine._launch_batch(pics[j:j + step], sizes[j:j + step], False)
+            for i in range(inst.n_jobs):
+                dec = InstanceDecode(inst.picture(i), *args.values()) if sem is None else \
+                    _launch_panoptic(sem.picture(j + i), inst.picture(i), None, palette, n_things, merge, kw)
+                jobs.append(InstanceResults(dec, items[j + i][1]))
+        return [e for job in jobs for e in job.result()]
+
+    first = inst_engine if semseg_engine is None else semseg_engine
+    with _eval_mode(inst_engine.model):
+        return [e for b in first._run(list(zip(pictures, image_ids)), sizes, batch) for e in b]
+
+
 class KptJob(ctypes.Structure):
     """pa_kpt_job of include/painter_hip.h."""
     _fields_ = [("rows", ctypes.c_void_p), ("gt_keypoints", ctypes.c_void_p), ("gt_table", ctypes.c_void_p), ("n_box", ctypes.c_int32),
