@@ -1,6 +1,6 @@
 // bf16 MFMA GEMM for the big nn.Linear contractions of the ViT blocks:
 //     D[i][j] = sum_k A(i,k) * B(j,k),   fp32 accumulate
-// 256 x 256 output tile per workgroup of 8 waves (2 along i x 4 along j, 128 x 64 per wave, 32x32x16 MFMA), contraction
+// 256 x 256 output tile per workgroup of 8 waves (2 along i x 4 along j, 128 x 64 per wave, 16x16x32 or 32x32x16 MFMA per family), contraction
 // tiles of 64, operands staged HBM -> LDS by LDS-DMA (global_load_lds_dwordx4), never through VGPRs.
 //
 // Each operand may be stored contraction-contiguous ("K-major": X and W of y = x.W^T) or row-contiguous ("M-major":
@@ -36,8 +36,30 @@ DEVI constexpr int unit_off(bool isB, int sub, int stage) { return (isB ? 65536 
 template <int N> DEVI void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 DEVI void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// source byte offset (from the operand's tile-0 base) of the 16-byte chunk that lane `tid` moves with DMA `j` of a unit
-template <bool MM, bool IS_A>
+// MFMA shape of the main loop, one per GEMM family (SH = 32: v_mfma_f32_32x32x16_bf16, SH = 16: v_mfma_f32_16x16x32_bf16).  Both shapes
+// take the same 24 fragment reads, 64 fragment registers, 128 accumulator registers and MFMA cycles per K tile and wave, and both add the
+// products of an output element in ascending k; what differs is the power the matrix pipe draws, i.e. the clock the board holds under a
+// whole-chip launch.  -DG256_MFMA16_MASK=<bits>: 1 = forward (K-major x K-major), 2 = data gradient (K-major x
+// M-major), 4 = weight gradient (M-major x M-major) run on 16x16x32; EVERY instantiation of a family (full, 224-row, mixed, SKIP, LIVE)
+// takes the family's shape, so the tile plans and the skipping / dense routes of one family stay bit-identical to each other.
+// Measured (MI355X; figures and logs: DESIGN.md sections 4.1 and 5): under a whole-chip launch the board holds a higher clock on 16x16x32
+// at the same power, and the training step gains with each family that takes it (bench.py, alternating processes: forward + data gradient
+// alone, mask 3, and all three, mask 7, each below the one before in every run), so every family takes 16x16x32.  On a quarter of the
+// chip, at the clock ceiling, the same loop is SLOWER on 16x16x32: it costs more cycles and wins on the clock alone.
+#ifndef G256_MFMA16_MASK
+#define G256_MFMA16_MASK 7
+#endif
+constexpr int family_shape(bool amm, bool bmm) {
+    return ((G256_MFMA16_MASK >> (amm ? 2 : bmm ? 1 : 0)) & 1) ? 16 : 32;
+}
+
+// source byte offset (from the operand's tile-0 base) of the 16-byte chunk that lane `tid` moves with DMA `j` of a unit.
+// M-major image: [64 k][16 chunks of 8 rows], chunk c of k row k at position c ^ 4 (k & 3).  SH = 16 adds the term 2 ((k >> 3) & 1):
+// a 32-lane half of a transposing read there takes the k rows 8 q .. 8 q + 3 and 8 (q + 1) .. 8 (q + 1) + 3 of the SAME 16 operand
+// rows -- 256-byte rows, so the same banks (2-way) without it; with it the second group sits 32 bytes further: 8 k rows x 32 bytes
+// = all 64 banks once.  The term moves whole 32-byte chunk pairs, never the two chunks of a pair against each other (the pair is what
+// one group of a transposing read takes from a k row), and is the same for k and k + 4 (one base register for both halves of a k-step).
+template <bool MM, bool IS_A, int SH>
 DEVI uint32_t src_off(int tid, int j, int sub, int tile0, int rows, uint32_t ld) {
     const int cidx = j * NT + tid;
     if constexpr (!MM) {
@@ -48,7 +70,7 @@ DEVI uint32_t src_off(int tid, int j, int sub, int tile0, int rows, uint32_t ld)
         return ((uint32_t)row * ld + kc * 8) * 2u;
     } else {
         const int k = cidx >> 4, cp = cidx & 15;
-        const int c = cp ^ (4 * (k & 3));
+        const int c = cp ^ (4 * (k & 3)) ^ (SH == 16 ? 2 * ((k >> 3) & 1) : 0);
         int n = IS_A ? ((c >> 3) * 128 + sub * 64 + (c & 7) * 8) : ((c >> 2) * 64 + sub * 32 + (c & 3) * 8);
         n = min(tile0 + n, rows - 8);
         return ((uint32_t)k * ld + n) * 2u;
@@ -73,10 +95,14 @@ template <int OFF> DEVI void lds_read64_tr(uint2& d, uint32_t addr) {
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
 }
 
-// one operand sub-tile of 32 rows x 64 k held by a wave: 4 k-steps of 8 contraction values per lane.  K-major: one
+// one operand sub-tile of 32 rows x 64 k held by a wave.  SH = 32: 4 k-steps of 8 contraction values per lane.  K-major: one
 // ds_read_b128 per k-step; M-major: two transposing 64-bit reads (k 0-3 | k 4-7 of the lane's 8) per k-step.
-template <bool MM> struct Frag4;
-template <> struct Frag4<false> {
+// SH = 16: two 16-row blocks x two k-steps of 32; register 2 rb + ks holds row 16 rb + (lane & 15), k = 32 ks + 8 (lane >> 4) .. + 7.
+// K-major: the same four ds_read_b128 from the same image (base 2 rb + ks; a 16-lane service group of the read covers 8 chunk
+// positions x 2 row parities = 64 banks: conflict-free); M-major: the same eight transposing reads, k-steps 8 KB apart, bases per
+// 16-row block (the image's term 2 ((k >> 3) & 1) meets the block's chunk bit, so the block is no immediate offset).
+template <bool MM, int SH> struct Frag4;
+template <int SH> struct Frag4<false, SH> {
     uint4 q0, q1, q2, q3;
     template <int IMM> DEVI void read(const uint32_t (&base)[4], int) {
         lds_read128<IMM>(q0, base[0]);
@@ -87,19 +113,32 @@ template <> struct Frag4<false> {
     template <int KS> DEVI bf16x8 k() const {
         return __builtin_bit_cast(bf16x8, KS == 0 ? q0 : KS == 1 ? q1 : KS == 2 ? q2 : q3);
     }
+    template <int RB, int KS> DEVI bf16x8 r() const { return k<2 * RB + KS>(); }
 };
-template <> struct Frag4<true> {
+template <int SH> struct Frag4<true, SH> {
     uint2 l0, h0, l1, h1, l2, h2, l3, h3;
     template <int IMM> DEVI void read(const uint32_t (&base)[4], int which_mb) {
-        const uint32_t b = base[which_mb];
-        lds_read64_tr<IMM + 0 * 4096>(l0, b);
-        lds_read64_tr<IMM + 0 * 4096 + 1024>(h0, b);
-        lds_read64_tr<IMM + 1 * 4096>(l1, b);
-        lds_read64_tr<IMM + 1 * 4096 + 1024>(h1, b);
-        lds_read64_tr<IMM + 2 * 4096>(l2, b);
-        lds_read64_tr<IMM + 2 * 4096 + 1024>(h2, b);
-        lds_read64_tr<IMM + 3 * 4096>(l3, b);
-        lds_read64_tr<IMM + 3 * 4096 + 1024>(h3, b);
+        if constexpr (SH == 32) {
+            const uint32_t b = base[which_mb];
+            lds_read64_tr<IMM + 0 * 4096>(l0, b);
+            lds_read64_tr<IMM + 0 * 4096 + 1024>(h0, b);
+            lds_read64_tr<IMM + 1 * 4096>(l1, b);
+            lds_read64_tr<IMM + 1 * 4096 + 1024>(h1, b);
+            lds_read64_tr<IMM + 2 * 4096>(l2, b);
+            lds_read64_tr<IMM + 2 * 4096 + 1024>(h2, b);
+            lds_read64_tr<IMM + 3 * 4096>(l3, b);
+            lds_read64_tr<IMM + 3 * 4096 + 1024>(h3, b);
+        } else {
+            const uint32_t b0 = base[2 * which_mb], b1 = base[2 * which_mb + 1];
+            lds_read64_tr<IMM>(l0, b0);
+            lds_read64_tr<IMM + 1024>(h0, b0);
+            lds_read64_tr<IMM + 8192>(l1, b0);
+            lds_read64_tr<IMM + 8192 + 1024>(h1, b0);
+            lds_read64_tr<IMM>(l2, b1);
+            lds_read64_tr<IMM + 1024>(h2, b1);
+            lds_read64_tr<IMM + 8192>(l3, b1);
+            lds_read64_tr<IMM + 8192 + 1024>(h3, b1);
+        }
     }
     template <int KS> DEVI bf16x8 k() const {
         typedef __attribute__((ext_vector_type(2))) uint32_t u2;
@@ -109,6 +148,7 @@ template <> struct Frag4<true> {
         u2 lv = {l.x, l.y}, hv = {h.x, h.y};
         return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lv, hv, 0, 1, 2, 3));
     }
+    template <int RB, int KS> DEVI bf16x8 r() const { return k<2 * RB + KS>(); }
 };
 
 // Epilogue contract (j a multiple of 8; N % 8 == 0 is required by ok(); the functor bounds-checks):
@@ -174,11 +214,13 @@ constexpr int BM_HALF = 128;
 //   M-major A (weight gradient over compact rows, no K split): the contraction runs over roundup(*live_count, 128) rows = an even number of K
 //     tiles; the rows between the count and that bound must be zero in BOTH operands.  A count of 0 runs no K loop and stores the zero accumulator.
 // Nothing changes inside the K loop, and LIVE = false compiles to the kernel it was before.
-template <bool AMM, bool BMM, int ILV, class Epi, bool SHORT = false, bool MIXED = false, bool SKIP = false, bool LIVE = false>
+template <bool AMM, bool BMM, int ILV, class Epi, bool SHORT = false, bool MIXED = false, bool SKIP = false, bool LIVE = false,
+          int SH = family_shape(AMM, BMM)>
 __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag, uint32_t lda, const bf16* __restrict__ Bg,
                                                       uint32_t ldb, Epi epi, int M, int N, int ktiles, int ktiles_per_split,
                                                       int tiles_n, int stagger, int order, int nfull, int patch,
                                                       const float* __restrict__ rowskip, int rps, const int* __restrict__ live_count) {
+    static_assert(SH == 32 || SH == 16, "MFMA shape: 32x32x16 or 16x16x32");
     static_assert(!(LIVE && (SHORT || MIXED || SKIP)), "a device-side count goes with uniform 256-row tiles");
     static_assert(!(SHORT && AMM), "the 224-row tile is built for a K-major A operand");
     static_assert(!(SKIP && AMM), "row tiles are skipped only for a K-major A operand");
@@ -310,8 +352,8 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
     for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            oa[sub][j] = src_off<AMM, true>(tid, j, sub, i0, M, lda);
-            ob[sub][j] = src_off<BMM, false>(tid, j, sub, j0, N, ldb);
+            oa[sub][j] = src_off<AMM, true, SH>(tid, j, sub, i0, M, lda);
+            ob[sub][j] = src_off<BMM, false, SH>(tid, j, sub, j0, N, ldb);
         }
     const size_t a_step = AMM ? (size_t)BK * lda * 2 : (size_t)BK * 2;
     const size_t b_step = BMM ? (size_t)BK * ldb * 2 : (size_t)BK * 2;
@@ -333,7 +375,7 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
 
     // ---- fragment read bases (per lane)
     uint32_t ra[4], rb[4];
-    {
+    if constexpr (SH == 32) {
         const int lr = lane & 31, g = lane >> 5;
         const int t = ((lr >> 1) & 7) ^ g;
         const int i = lane & 15, half = (lane >> 4) & 1;
@@ -356,32 +398,89 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
             rb[0] = (uint32_t)(65536 + (g * 8 + (i >> 2)) * 256 + ((c ^ (4 * (i >> 2))) << 4) + (i & 1) * 8);
             rb[1] = rb[2] = rb[3] = 0;
         }
-    }
-
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
+    } else {
+        // 16x16x32: lane = 16 kq + i.  K-major, base 2 rb + ks: row 16 rb + i of the 32-row block, k chunk 4 ks + kq (its position: src_off).
+        // M-major, base 2 mb + rb (A) / rb (B): lane 4 q + p of a 16-lane group addresses k row 8 kq + q (k-steps and the upper four k by
+        // immediates), chunk pair 2 rb of the 32-row block, chunk p >> 1 of the pair, 8-byte half p & 1 -- through the image's XOR.
+        const int i = lane & 15, kq = lane >> 4, q = i >> 2, p = i & 3;
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+            for (int ks = 0; ks < 2; ++ks) {
+                const int r16 = b * 16 + i, pos = ((i >> 1) ^ kq ^ (4 * ks)) << 4;
+                if constexpr (!AMM) ra[2 * b + ks] = (uint32_t)((htile ? wr * 32768 + r16 * 128 : (wr * 64 + r16) * 128) + pos);
+                if constexpr (!BMM) rb[2 * b + ks] = (uint32_t)(65536 + (wc * 32 + r16) * 128 + pos);
+            }
+        const int krow = 8 * kq + q, x = (4 * (krow & 3)) ^ (2 * ((krow >> 3) & 1));
+        if constexpr (AMM) {
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const int c = wr * 8 + mb * 4 + b * 2 + (p >> 1);
+                    ra[2 * mb + b] = (uint32_t)(krow * 256 + ((c ^ x) << 4) + (p & 1) * 8);
+                }
+        }
+        if constexpr (BMM) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int c = wc * 4 + b * 2 + (p >> 1);
+                rb[b] = (uint32_t)(65536 + krow * 256 + ((c ^ x) << 4) + (p & 1) * 8);
+            }
+            rb[2] = rb[3] = 0;
+        }
+    }
 
-    Frag4<AMM> fa0, fa1;
-    Frag4<BMM> fb0, fb1;
+    // 32 x 32 accumulator block [mb][nb]: one 16-register MFMA result (SH = 32), or the four 16 x 16 results [ih][jh] of its quarters
+    typedef __attribute__((ext_vector_type(4))) float f32x4;
+    struct AccBlk {
+        typename std::conditional<SH == 32, f32x16, f32x4[2][2]>::type v;
+    };
+    AccBlk acc[4][2];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            if constexpr (SH == 32) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[a][b].v[r] = 0.f;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[a][b].v[r >> 3][(r >> 2) & 1][r & 3] = 0.f;
+            }
+        }
+
+    Frag4<AMM, SH> fa0, fa1;
+    Frag4<BMM, SH> fb0, fb1;
 
     // the MFMA takes the B fragment first so that a lane ends up with ONE output row and 4-column runs (wide stores)
+    // one 32 x 32 block x one k-step: SH = 32: k-step KS (of 4) in one MFMA; SH = 16: k-step KS (of 2) in four, one per 16 x 16 quarter
+#define G256_BLK32(ACC, BF, AF, KS) ACC.v = __builtin_amdgcn_mfma_f32_32x32x16_bf16((BF).template k<KS>(), (AF).template k<KS>(), ACC.v, 0, 0, 0);
+#define G256_Q16(ACC, BF, AF, KS, IH, JH) \
+    ACC.v[IH][JH] = __builtin_amdgcn_mfma_f32_16x16x32_bf16((BF).template r<JH, KS>(), (AF).template r<IH, KS>(), ACC.v[IH][JH], 0, 0, 0);
+#define G256_BLK16(ACC, BF, AF, KS) G256_Q16(ACC, BF, AF, KS, 0, 0) G256_Q16(ACC, BF, AF, KS, 0, 1) G256_Q16(ACC, BF, AF, KS, 1, 0) G256_Q16(ACC, BF, AF, KS, 1, 1)
 #define G256_MMA(KS)                                                                                                     \
-    acc[mrow * 2 + 0][ncol] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr.template k<KS>(), fa0.template k<KS>(), acc[mrow * 2 + 0][ncol], 0, 0, 0); \
-    if (!SHORT || mrow == 0 || blk3)                                                                                     \
-        acc[mrow * 2 + 1][ncol] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr.template k<KS>(), fa1.template k<KS>(), acc[mrow * 2 + 1][ncol], 0, 0, 0);
-    // d0 / d1: this phase's DMA pieces; issued between the MFMAs (order pinned) as far as ILV says, otherwise by the caller
-    auto mma_quad = [&](int mrow, int ncol, const Frag4<BMM>& bfr, auto&& d0, auto&& d1) {
+    G256_BLK32(acc[mrow * 2 + 0][ncol], bfr, fa0, KS)                                                                    \
+    if (!SHORT || mrow == 0 || blk3) { G256_BLK32(acc[mrow * 2 + 1][ncol], bfr, fa1, KS) }
+    // d0 / d1: this phase's DMA pieces; issued between the MFMAs (order pinned) as far as ILV says, otherwise by the caller.
+    // Either shape: d0 after the first quarter of the segment's MFMA time, d1 after the third; k ascending per output element.
+    auto mma_quad = [&](int mrow, int ncol, const Frag4<BMM, SH>& bfr, auto&& d0, auto&& d1) {
         __builtin_amdgcn_s_setprio(1);
-        G256_MMA(0)
-        if constexpr (ILV >= 2) { __builtin_amdgcn_sched_barrier(0); d0(); __builtin_amdgcn_sched_barrier(0); }
-        G256_MMA(1) G256_MMA(2)
-        if constexpr (ILV >= 1) { __builtin_amdgcn_sched_barrier(0); d1(); __builtin_amdgcn_sched_barrier(0); }
-        G256_MMA(3)
+        if constexpr (SH == 32) {
+            G256_MMA(0)
+            if constexpr (ILV >= 2) { __builtin_amdgcn_sched_barrier(0); d0(); __builtin_amdgcn_sched_barrier(0); }
+            G256_MMA(1) G256_MMA(2)
+            if constexpr (ILV >= 1) { __builtin_amdgcn_sched_barrier(0); d1(); __builtin_amdgcn_sched_barrier(0); }
+            G256_MMA(3)
+        } else {
+            const bool two = !SHORT || mrow == 0 || blk3;      // (224-row tile: the lower wave row's fourth 32-row block = two 16-row blocks)
+            G256_BLK16(acc[mrow * 2 + 0][ncol], bfr, fa0, 0)
+            if constexpr (ILV >= 2) { __builtin_amdgcn_sched_barrier(0); d0(); __builtin_amdgcn_sched_barrier(0); }
+            if (two) { G256_BLK16(acc[mrow * 2 + 1][ncol], bfr, fa1, 0) }
+            G256_BLK16(acc[mrow * 2 + 0][ncol], bfr, fa0, 1)
+            if constexpr (ILV >= 1) { __builtin_amdgcn_sched_barrier(0); d1(); __builtin_amdgcn_sched_barrier(0); }
+            if (two) { G256_BLK16(acc[mrow * 2 + 1][ncol], bfr, fa1, 1) }
+        }
         __builtin_amdgcn_s_setprio(0);
     };
 #undef G256_MMA
@@ -464,20 +563,28 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
     auto half_body = [&](auto stage_c, int T) {
         constexpr int S = decltype(stage_c)::value;
         const int t1 = min(T + 1, nt - 1);
-#define G256_HMMA(KS, NC) \
-        acc[0][NC] = __builtin_amdgcn_mfma_f32_32x32x16_bf16((NC ? fb1 : fb0).template k<KS>(), fa0.template k<KS>(), acc[0][NC], 0, 0, 0); \
-        acc[1][NC] = __builtin_amdgcn_mfma_f32_32x32x16_bf16((NC ? fb1 : fb0).template k<KS>(), fa1.template k<KS>(), acc[1][NC], 0, 0, 0);
 #define G256_HDMA(X) __builtin_amdgcn_sched_barrier(0); X; __builtin_amdgcn_sched_barrier(0);
+        // (SH = 32: G256_HMMA = k-step KS of 4 on both blocks; SH = 16: G256_HM16 = k-step KS of 2 on block MB -- the same MFMA time between
+        // two DMA pieces either way)
+#define G256_HMMA(KS, NC) G256_BLK32(acc[0][NC], (NC ? fb1 : fb0), fa0, KS) G256_BLK32(acc[1][NC], (NC ? fb1 : fb0), fa1, KS)
+#define G256_HM16(KS, MB, NC) G256_BLK16(acc[MB][NC], (NC ? fb1 : fb0), (MB ? fa1 : fa0), KS)
         // ---- phase 0: a_wr, b0 of stage S; stage the next tile's a0, a1 (upper halves), b0 into stage S ^ 1
         fa0.template read<unit_off(false, 0, S)>(ra, 0);
         fa1.template read<unit_off(false, 0, S) + 4096>(ra, 1);
         fb0.template read<unit_off(true, 0, S) - 65536>(rb, 0);
         lwait();
         __builtin_amdgcn_s_setprio(1);
-        G256_HMMA(0, 0) G256_HDMA(piece_a(0, S ^ 1, t1, 0))
-        G256_HMMA(1, 0) G256_HDMA(piece_a(1, S ^ 1, t1, 0))
-        G256_HMMA(2, 0) G256_HDMA(piece_b(0, S ^ 1, t1, 0))
-        G256_HMMA(3, 0) G256_HDMA(piece_b(0, S ^ 1, t1, 1))
+        if constexpr (SH == 32) {
+            G256_HMMA(0, 0) G256_HDMA(piece_a(0, S ^ 1, t1, 0))
+            G256_HMMA(1, 0) G256_HDMA(piece_a(1, S ^ 1, t1, 0))
+            G256_HMMA(2, 0) G256_HDMA(piece_b(0, S ^ 1, t1, 0))
+            G256_HMMA(3, 0) G256_HDMA(piece_b(0, S ^ 1, t1, 1))
+        } else {
+            G256_HM16(0, 0, 0) G256_HDMA(piece_a(0, S ^ 1, t1, 0))
+            G256_HM16(0, 1, 0) G256_HDMA(piece_a(1, S ^ 1, t1, 0))
+            G256_HM16(1, 0, 0) G256_HDMA(piece_b(0, S ^ 1, t1, 0))
+            G256_HM16(1, 1, 0) G256_HDMA(piece_b(0, S ^ 1, t1, 1))
+        }
         __builtin_amdgcn_s_setprio(0);
         wait_vm<4>();
         bar();
@@ -485,15 +592,25 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
         fb1.template read<unit_off(true, 1, S) - 65536>(rb, 0);
         lwait();
         __builtin_amdgcn_s_setprio(1);
-        G256_HMMA(0, 1) G256_HDMA(piece_b(1, S ^ 1, t1, 0))
-        G256_HMMA(1, 1) G256_HMMA(2, 1) G256_HDMA(piece_b(1, S ^ 1, t1, 1))
-        G256_HMMA(3, 1)
+        if constexpr (SH == 32) {
+            G256_HMMA(0, 1) G256_HDMA(piece_b(1, S ^ 1, t1, 0))
+            G256_HMMA(1, 1) G256_HMMA(2, 1) G256_HDMA(piece_b(1, S ^ 1, t1, 1))
+            G256_HMMA(3, 1)
+        } else {
+            G256_HM16(0, 0, 1) G256_HDMA(piece_b(1, S ^ 1, t1, 0))
+            G256_HM16(0, 1, 1) G256_HM16(1, 0, 1) G256_HDMA(piece_b(1, S ^ 1, t1, 1))
+            G256_HM16(1, 1, 1)
+        }
         __builtin_amdgcn_s_setprio(0);
         wait_vm<2>();
         bar();
+#undef G256_HM16
 #undef G256_HMMA
 #undef G256_HDMA
     };
+#undef G256_BLK16
+#undef G256_Q16
+#undef G256_BLK32
 
     bool ran_half = false;
     if constexpr (MIXED) {
@@ -568,9 +685,15 @@ __global__ __launch_bounds__(NT) void gemm256_kernel(const bf16* __restrict__ Ag
                 for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const f32x16& c = acc[mb][nb];
-                        *reinterpret_cast<float4*>(stg + lr * 68 + nb * 32 + q * 8 + g * 4) =
-                            make_float4(c[q * 4 + 0], c[q * 4 + 1], c[q * 4 + 2], c[q * 4 + 3]);
+                        if constexpr (SH == 32) {
+                            const f32x16& c = acc[mb][nb].v;
+                            *reinterpret_cast<float4*>(stg + lr * 68 + nb * 32 + q * 8 + g * 4) =
+                                make_float4(c[q * 4 + 0], c[q * 4 + 1], c[q * 4 + 2], c[q * 4 + 3]);
+                        } else {      // quarter (ih, jh) = (q >> 1, q & 1): the lane holds row lane & 15, columns 4 (lane >> 4) .. + 3 of it
+                            const f32x4& c = acc[mb][nb].v[q >> 1][q & 1];
+                            *reinterpret_cast<float4*>(stg + ((q >> 1) * 16 + (lane & 15)) * 68 + nb * 32 + (q & 1) * 16 + (lane >> 4) * 4) =
+                                make_float4(c[0], c[1], c[2], c[3]);
+                        }
                     }
                 const int ib = rbase + (mb >> 1) * 64 + (mb & 1) * 32;
 #pragma unroll
