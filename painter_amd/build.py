@@ -32,11 +32,12 @@ FLAGS = FLAGS + os.environ.get("PA_EXTRA_FLAGS", "").split()
 # floats (tests/painter_pq_host.py).  painter_ap.hip: one float64 division per (detection, ground truth) feeds the comparisons with the
 # IoU thresholds that COCOeval makes in float64 (tests/painter_ap_host.py).  painter_kpt.hip: the photo coordinates equal
 # painter_engine.to_image bit for bit, and the float32 / float64 steps that feed exp in the two OKS forms are stated operation by operation
-# (tests/painter_kpt_host.py).
+# (tests/painter_kpt_host.py).  painter_paint.hip: the float64 divisions and the product with 79 decide the cell, and with it the colour, of
+# an instance target exactly as the reference's Python floats do (tests/painter_paint_host.py).
 EXTRA = {"seggpt_io.hip": ["-ffp-contract=off"], "pair_io.hip": ["-ffp-contract=off"], "painter_io.hip": ["-ffp-contract=off"],
          "painter_inst.hip": ["-ffp-contract=off"], "painter_pano.hip": ["-ffp-contract=off"], "painter_pose.hip": ["-ffp-contract=off"],
          "painter_score.hip": ["-ffp-contract=off"], "painter_restore.hip": ["-ffp-contract=off"], "painter_pq.hip": ["-ffp-contract=off"],
-         "painter_ap.hip": ["-ffp-contract=off"], "painter_kpt.hip": ["-ffp-contract=off"]}
+         "painter_ap.hip": ["-ffp-contract=off"], "painter_kpt.hip": ["-ffp-contract=off"], "painter_paint.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():
@@ -63,6 +64,7 @@ def headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_hip.h"))
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_rle.h"))
+    hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_paint.h"))
     return sorted(hs)
 
 

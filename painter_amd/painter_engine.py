@@ -67,6 +67,13 @@ strings or uncompressed counts -> bit masks.  The instance evaluators' whole out
 back instead of the bool masks, and every `masks=` argument also takes a list of RLE dicts (a detections JSON, crowd ground truth)
 (tests/painter_rle_host.py is the definition; restated from pycocotools' published maskApi.c and unverified against pycocotools).
 
+`paint_semantic`, `paint_panoptic_semantic`, `paint_instances` and `paint_pose` go the other way (csrc/painter_paint.hip,
+include/painter_paint.h): annotations -- label maps, panoptic id maps, instance masks, keypoints -- become the painted TARGET pictures the
+reference's offline generators write as PNG files (gen_color_ade20k_sem.py, gen_color_coco_panoptic_segm.py, SaveDataPairCustom,
+encode_target_to_image), byte for byte, as uint8 CUDA tensors that `PainterEngine(prompt_tgt=...)`, `PairSpec.target` and every decoder
+take (tests/painter_paint_host.py is the definition; mmpose's MSRA rule is restated from its published source and unverified against
+mmpose).
+
 Stays on the host, by design: file decode / encode; the depth script's one-off prompt-target preparation
 (`Image.fromarray(float array).convert("RGB")`, painter_inference_depth.py:134-145: pass its result as `prompt_tgt`); SIDD's
 `cv2.resize` of the float query (painter_inference_sidd.py:136: OpenCV's resize is not restated -- use `run_one_image` with the
@@ -2248,8 +2255,265 @@ class KeypointAP:
                                    self.max_dets)
 
 
+# ---- painting targets from annotations (csrc/painter_paint.hip, include/painter_paint.h)
+PAINT_MAX_COLOURS, PAINT_MAX_SEGMENTS, PAINT_MAX_MASKS, PAINT_CELLS, PAINT_MAX_JOINTS, PAINT_MAX_TABLE = 1024, 1024, 4096, 6400, 32, 1024
+PAINT_LABELS_U8, PAINT_LABELS_I32, PAINT_IDS_I32, PAINT_IDS_RGB = range(4)
+
+
+class PaintJob(ctypes.Structure):
+    """pa_paint_job of include/painter_paint.h."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("table", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("kind", ctypes.c_int32), ("n_table", ctypes.c_int32)]
+
+
+def _u8_palette(who, palette, default, rows=None, channels=3):
+    """[K][channels] integer colours 0 .. 255, or None for `default()` -> uint8 numpy, a copy."""
+    pal = np.array(default() if palette is None else palette)
+    if pal.ndim != 2 or pal.shape[1] != channels or pal.shape[0] < 1 or (rows is not None and pal.shape[0] != rows) or \
+            not ((pal == np.floor(pal)).all() and pal.min() >= 0 and pal.max() <= 255):
+        raise ValueError("%s: the palette holds integer colours 0..255 as [%s][%d], got %s" % (who, rows or "K", channels, pal.shape))
+    return np.ascontiguousarray(pal.astype(np.uint8))
+
+
+def _paint_sources(who, maps, kinds):
+    """The maps of a semantic call, checked on the host before anything touches the device: {accepted dtype / trailing shape: kind}."""
+    out = []
+    for i, m in enumerate(maps):
+        m = m if torch.is_tensor(m) else np.asarray(m)
+        key = (str(m.dtype).replace("torch.", ""), tuple(m.shape[2:]))
+        if len(m.shape) < 2 or key not in kinds or m.shape[0] < 1 or m.shape[1] < 1:
+            raise ValueError("%s: picture %d is %s %s; accepted: %s" % (who, i, key[0], tuple(m.shape), ", ".join(
+                "%s [H][W]%s" % (d, "".join("[%d]" % s for s in t)) for d, t in kinds)))
+        out.append((m, kinds[key]))
+    if not out:
+        raise ValueError("%s: no pictures" % who)
+    return out
+
+
+def _paint_launch(who, sources, tables, pal, device):
+    """One pa_paint_semantic over a job table -> (the pictures, uint8 CUDA [H][W][3] each; int32 CUDA [n] = labels above the palette)."""
+    srcs = [m.contiguous() if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m)).to(device) for m, _ in sources]
+    for s in srcs:
+        if s.device != device:
+            raise RuntimeError("%s: the maps are on %s, expected %s" % (who, s.device, device))
+    flat = np.concatenate([t.reshape(-1, 2) for t in tables] + [np.zeros((1, 2), np.int32)]).astype(np.int32)
+    tab_d = torch.from_numpy(flat).to(device, non_blocking=True)
+    pal_d = torch.from_numpy(pal).to(device, non_blocking=True)
+    outs = [torch.empty((int(s.shape[0]), int(s.shape[1]), 3), dtype=torch.uint8, device=device) for s in srcs]
+    jobs, row = (PaintJob * len(srcs))(), 0
+    for k, (s, o, (_, kind), t) in enumerate(zip(srcs, outs, sources, tables)):
+        jobs[k] = PaintJob(s.data_ptr(), o.data_ptr(), tab_d.data_ptr() + 8 * row, int(s.shape[0]), int(s.shape[1]), kind, len(t))
+        row += len(t)
+    host, jobs_d = _job_table(jobs, device)
+    bad = torch.empty(len(srcs), dtype=torch.int32, device=device)
+    check(lib.pa_paint_semantic(jobs_d.data_ptr(), len(srcs), max(int(s.shape[0]) * int(s.shape[1]) for s in srcs), pal_d.data_ptr(),
+                                int(pal.shape[0]), bad.data_ptr(), _stream()), "%s (pa_paint_semantic, %d pictures)" % (who, len(srcs)))
+    return outs, bad
+
+
+def paint_semantic(label_maps, palette=None, device="cuda"):
+    """`colorEncode` of Painter/data/ade20k/gen_color_ade20k_sem.py:66-82 on the device: a label map uint8 / int32 [H][W] (numpy or CUDA
+    tensor) or a list of them, of any sizes, in ONE launch over a job table -> the painted target, a contiguous uint8 CUDA tensor
+    [H][W][3] (a list for a list).  label <= 0 paints black, label l paints palette[l - 1]; palette: [K][3], K <= 1024, default
+    `semantic_palette(150, 6)`, that file's PALETTE.  A label above K is an IndexError in the reference: here the pixel paints black, is
+    counted on the device, and the call raises ValueError naming the first such picture.  Only the counts come back."""
+    single = not isinstance(label_maps, (list, tuple))
+    sources = _paint_sources("paint_semantic", [label_maps] if single else list(label_maps),
+                             {("uint8", ()): PAINT_LABELS_U8, ("int32", ()): PAINT_LABELS_I32})
+    pal = _u8_palette("paint_semantic", palette, lambda: semantic_palette(150, 6))
+    if pal.shape[0] > PAINT_MAX_COLOURS:
+        raise ValueError("paint_semantic: %d colours, at most %d" % (pal.shape[0], PAINT_MAX_COLOURS))
+    device = _device([m for m, _ in sources], device)
+    outs, bad = _paint_launch("paint_semantic", sources, [np.zeros((0, 2), np.int32)] * len(sources), pal, device)
+    bad = bad.cpu().numpy()
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError("paint_semantic: picture %d has %d pixel(s) with a label above the palette's %d colours; %d of %d pictures do"
+                         % (i, int(bad[i]), pal.shape[0], int((bad != 0).sum()), len(bad)))
+    return outs[0] if single else outs
+
+
+def paint_panoptic_semantic(id_maps, segments_info, category_index, palette=None, device="cuda"):
+    """The paint loop of Painter/data/coco_semseg/gen_color_coco_panoptic_segm.py:122-138 on the device.  id_maps: a segment-id map
+    int32 [H][W], or the RGB annotation PNG uint8 [H][W][3] whose ids are formed on the device as r + 256 g + 65536 b (numpy or CUDA
+    tensors), or a list of them; segments_info: per picture the annotation's segments, (segment id, category id) pairs or dicts with
+    "id" and "category_id"; category_index: category id -> colour index (the script's catid2colorid); palette [K][3], default
+    `semantic_palette()`.  An id no segment lists paints black; where two segments share an id the later one wins, as the script's
+    sequential overwrite does.  -> uint8 CUDA [H][W][3] (a list for a list).  A category without a colour index is a KeyError, a colour
+    index outside the palette a ValueError, both before anything is launched.  (The script skips an annotation without segments; here
+    it paints black.)"""
+    single = not isinstance(id_maps, (list, tuple))
+    sources = _paint_sources("paint_panoptic_semantic", [id_maps] if single else list(id_maps),
+                             {("int32", ()): PAINT_IDS_I32, ("uint8", (3,)): PAINT_IDS_RGB})
+    infos = [segments_info] if single else list(segments_info)
+    if len(infos) != len(sources):
+        raise ValueError("paint_panoptic_semantic: %d pictures, %d segment lists" % (len(sources), len(infos)))
+    pal = _u8_palette("paint_panoptic_semantic", palette, semantic_palette)
+    if pal.shape[0] > PAINT_MAX_COLOURS:
+        raise ValueError("paint_panoptic_semantic: %d colours, at most %d" % (pal.shape[0], PAINT_MAX_COLOURS))
+    tables = []
+    for i, info in enumerate(infos):
+        rows = [(s["id"], s["category_id"]) if isinstance(s, dict) else tuple(s) for s in info]
+        if len(rows) > PAINT_MAX_SEGMENTS:
+            raise ValueError("paint_panoptic_semantic: picture %d has %d segments, at most %d" % (i, len(rows), PAINT_MAX_SEGMENTS))
+        t = np.zeros((len(rows), 2), np.int32)
+        for k, (sid, cat) in enumerate(rows):
+            colour = int(category_index[cat])
+            if not 0 <= colour < pal.shape[0]:
+                raise ValueError("paint_panoptic_semantic: picture %d, category %r has colour index %d outside the palette's %d colours"
+                                 % (i, cat, colour, pal.shape[0]))
+            if not 0 <= int(sid) < 1 << 31:
+                raise ValueError("paint_panoptic_semantic: picture %d, segment id %r" % (i, sid))
+            t[k] = int(sid), colour
+        tables.append(t)
+    device = _device([m for m, _ in sources], device)
+    outs, _ = _paint_launch("paint_panoptic_semantic", sources, tables, pal, device)
+    return outs[0] if single else outs
+
+
+def _geo_cells(boxes, n, h, w):
+    """method="geo_center" of SaveDataPairCustom.__call__ (:115-118, :124-125) with its own expressions, on the host."""
+    boxes = np.asarray(boxes)
+    if boxes.shape != (n, 4):
+        raise ValueError("paint_instances: boxes are [n][4] = x1, y1, x2, y2 for the %d masks, got %s" % (n, boxes.shape))
+    cells = np.zeros((n, 2), np.int32)
+    for idx in range(n):
+        box = boxes[idx]
+        center_x, center_y = (box[:2] + box[2:]) / 2
+        cells[idx] = int(center_x / w * 79), int(center_y / h * 79)
+    if n and (cells.min() < 0 or cells.max() > 79):
+        raise ValueError("paint_instances: the centre of box %d lies outside the picture" % int(np.flatnonzero(((cells < 0) | (cells > 79)).any(1))[0]))
+    return cells
+
+
+def paint_instances(masks, size=None, palette=None, method="mass_center", boxes=None, device="cuda"):
+    """SaveDataPairCustom.__call__ of Painter/data/mmdet_custom/data/pipelines/transforms.py:93-131 (center_of_mass :153-172) on the
+    device: the class-agnostic instance target.  masks: whatever `_bit_masks` takes -- bool / uint8 [n][H][W], bit masks uint32 / int32
+    [n][ceil(H W / 32)] with size = (H, W), or a list of COCO RLE dicts; palette [6400][3] in `location_palette()`'s order (the default);
+    method "mass_center", or "geo_center" with boxes [n][4] = x1, y1, x2, y2 (the centre is then computed on the host).
+
+    Every mask is painted in the colour of the cell its centre falls in: the integers n, sum x, sum y over its bits, then the
+    reference's float64 operations in its order (norm = n or 1e-6, cx = sum x / norm, ax = int(cx / W * 79)).  The reference asserts
+    disjoint masks; where masks overlap, the HIGHEST index wins, which is what its sequential overwrite does.  Up to 4096 masks.
+
+    -> (picture uint8 CUDA [H][W][3], cells int32 numpy [n][2] = (ax, ay), empty bool = the reference's "pure black label" that it does
+    not save).  The picture stays on the device; 8 n + 4 bytes come back."""
+    if method not in ("mass_center", "geo_center"):
+        raise NotImplementedError(method)
+    if (method == "geo_center") != (boxes is not None):
+        raise ValueError("paint_instances: boxes go with method=\"geo_center\", and only with it")
+    pal = _u8_palette("paint_instances", palette, location_palette, rows=PAINT_CELLS)
+    if _is_rles(masks):
+        size = _rle_size(masks) if size is None else size
+    else:
+        masks = masks if torch.is_tensor(masks) else np.asarray(masks)
+        if size is None:
+            if len(masks.shape) != 3:
+                raise ValueError("paint_instances: bit masks need size=(H, W)")
+            size = masks.shape[1:]
+    h, w = int(size[0]), int(size[1])
+    if h < 1 or w < 1 or h * w >= 1 << 31 or len(masks) > PAINT_MAX_MASKS:
+        raise ValueError("paint_instances: %d masks of %d x %d; at most %d masks, 1 <= H W < 2^31" % (len(masks), h, w, PAINT_MAX_MASKS))
+    cells_in = _geo_cells(boxes, len(masks), h, w) if method == "geo_center" else None
+    device = _device([masks], device)
+    bits, n = _bit_masks(masks, h, w, device)
+    pal_d = torch.from_numpy(pal).to(device, non_blocking=True)
+    cells_d = None if cells_in is None else torch.from_numpy(np.concatenate([cells_in, np.zeros((1, 2), np.int32)])).to(device, non_blocking=True)
+    ws = _workspace(lib.pa_paint_instances_workspace_bytes, (n,), "pa_paint_instances (%d masks)" % n, device)
+    picture = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
+    small = torch.empty(2 * max(n, 1) + 1, dtype=torch.int32, device=device)            # cells [n][2] | empty
+    check(lib.pa_paint_instances(bits.data_ptr(), n, h, w, pal_d.data_ptr(), None if cells_d is None else cells_d.data_ptr(), ws.data_ptr(),
+                                 picture.data_ptr(), small.data_ptr(), small.data_ptr() + 8 * max(n, 1), _stream()),
+          "pa_paint_instances (%d masks of %d x %d)" % (n, h, w))
+    back = small.cpu().numpy()
+    return picture, back[:2 * n].reshape(n, 2).copy(), bool(back[2 * max(n, 1)])
+
+
+def msra_rectangles(joints, visible, heatmap_size, sigma, image_size=None):
+    """mmpose 0.x `TopDownGenerateTarget._msra_generate_target` up to its rectangles, with its own Python expressions (restated from
+    mmpose's published source; mmpose is not available where this project is tested, so the rule is UNVERIFIED against it): per joint
+    mu = int(joint / feat_stride + 0.5), ul = int(mu - 3 sigma), br = int(mu + 3 sigma + 1), weight = visible, and 0 where
+    ul_x >= W or ul_y >= H or br_x < 0 or br_y < 0.  `int()` truncates toward zero, so for sigma = 1.5 and mu < 5 the patch is 9 wide and
+    its centre, ul + 5, is not mu.  joints [B][K][>= 2], visible [B][K] or [B][K][>= 1]
+    -> (rects int32 [B][K][4] = ul_x, ul_y, br_x, br_y, zeros for weight 0; weights float32 [B][K])."""
+    W, H = int(heatmap_size[0]), int(heatmap_size[1])
+    joints, visible = np.asarray(joints), np.asarray(visible)
+    B, K = joints.shape[:2]
+    feat_stride = np.array(image_size if image_size is not None else (W, H)) / [W, H]
+    tmp_size = sigma * 3
+    rects, weights = np.zeros((B, K, 4), np.int32), np.zeros((B, K), np.float32)
+    for b in range(B):
+        for k in range(K):
+            weight = visible[b, k, 0] if visible.ndim == 3 else visible[b, k]
+            mu_x = int(joints[b][k][0] / feat_stride[0] + 0.5)
+            mu_y = int(joints[b][k][1] / feat_stride[1] + 0.5)
+            ul = [int(mu_x - tmp_size), int(mu_y - tmp_size)]
+            br = [int(mu_x + tmp_size + 1), int(mu_y + tmp_size + 1)]
+            if ul[0] >= W or ul[1] >= H or br[0] < 0 or br[1] < 0:
+                weight = 0
+            weights[b, k] = weight
+            if weights[b, k] > 0.5:
+                rects[b, k] = ul[0], ul[1], br[0], br[1]
+    return rects, weights
+
+
+def msra_table(sigma):
+    """R by squared distance from the patch centre for one sigma, with the reference's own numpy expression (the patch of
+    _msra_generate_target, `* 255.` and `.astype(np.uint8)` of encode_rgb_target_to_image) -> (uint8 [2 r^2 + 1] with r the patch's
+    largest offset, the float32 values before rounding, the centre size // 2)."""
+    size = 2 * (sigma * 3) + 1
+    c = int(size // 2)
+    r = max(c, int(np.ceil(size)) - 1 - c)
+    d2 = np.arange(2 * r * r + 1, dtype=np.float32)
+    g = np.exp(-d2 / (2 * sigma ** 2))
+    return (g * 255.).astype(np.uint8), g, c
+
+
+def paint_pose(joints, visible, heatmap_size=(192, 256), sigmas=(1.5, 3), palette=None, image_size=None, device="cuda"):
+    """The `coco_pose` target: mmpose's MSRA heat maps for both sigmas followed by `encode_rgb_target_to_image` of
+    Painter/data/mmpose_custom/data/pipelines/custom_transform.py:64-112, without a heat map in memory.  joints [B][K][>= 2] in pixels
+    of `image_size` (default: the heat map's own size, as in the reference's configuration), visible [B][K] or [B][K][>= 1], K <= 32;
+    heatmap_size (W, H); sigmas (class sigma -> G, B; kernel sigma -> R); palette [K][2] = (G, B) per joint, default `pose_palette()`.
+
+    Host: `msra_rectangles` for both sigmas and `msra_table` -- a few integers per joint.  Device, integers only: R = table[min d^2] over
+    the kernel rectangles that hold the pixel (the table is strictly decreasing, so the smallest d^2 is the reference's max and the
+    lowest joint among equals its argmax); (G, B) = black without a class rectangle, the joint's colour with one, and with several the
+    colour of the kernel argmax joint.  The MSRA rule is mmpose's, restated from its published source and UNVERIFIED against mmpose;
+    the encoding is the reference's own and pinned by tests/golden/painter_paint.npz.  Not built: the TopDownAffine crop of the photo,
+    Megvii / UDP encodings, use_different_joint_weights.
+
+    -> (pictures uint8 CUDA [B][H][W][3], weights float32 numpy [B][K]: the target_weight of the kernel sigma)."""
+    joints, visible = np.asarray(joints), np.asarray(visible)
+    if joints.ndim != 3 or joints.shape[2] < 2 or joints.shape[0] < 1 or not 1 <= joints.shape[1] <= PAINT_MAX_JOINTS or \
+            visible.shape[:2] != joints.shape[:2] or visible.ndim not in (2, 3):
+        raise ValueError("paint_pose: joints [B][K][>= 2] with 1 <= K <= %d and visible [B][K], got %s and %s"
+                         % (PAINT_MAX_JOINTS, joints.shape, visible.shape))
+    B, K = joints.shape[:2]
+    W, H = int(heatmap_size[0]), int(heatmap_size[1])
+    if len(sigmas) != 2 or W < 1 or H < 1 or H * W >= 1 << 31:
+        raise ValueError("paint_pose: sigmas = (class sigma, kernel sigma), heatmap_size = (W, H)")
+    pal = _u8_palette("paint_pose", palette, lambda: pose_palette()[:-1], channels=2)
+    if pal.shape[0] < K:
+        raise ValueError("paint_pose: %d joints, the palette has %d colours" % (K, pal.shape[0]))
+    table, g, c = msra_table(sigmas[1])
+    if len(table) > PAINT_MAX_TABLE or not (np.diff(g) < 0).all():
+        raise ValueError("paint_pose: for sigma %r the float32 heat values are not strictly decreasing in d^2 (or the patch is too large):"
+                         " the device rule does not hold" % (sigmas[1],))
+    rects_c, _ = msra_rectangles(joints, visible, (W, H), sigmas[0], image_size)
+    rects_k, weights = msra_rectangles(joints, visible, (W, H), sigmas[1], image_size)
+    device = _device((), device)
+    tables = np.concatenate([np.stack([rects_c, rects_k], 1).astype(np.int32).view(np.uint8).ravel(), pal[:K].ravel(), table])
+    tab_d = torch.from_numpy(tables).to(device, non_blocking=True)
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=device)
+    o_pal = 32 * B * K
+    check(lib.pa_paint_pose(tab_d.data_ptr(), B, K, H, W, c, tab_d.data_ptr() + o_pal, tab_d.data_ptr() + o_pal + 2 * K, len(table),
+                            out.data_ptr(), _stream()), "pa_paint_pose (%d boxes of %d joints, %d x %d)" % (B, K, H, W))
+    return out, weights
+
+
 class PainterEngine:
-    """One prompt pair, one task, any number of query pictures.  prompt_img / prompt_tgt: RGB uint8 arrays of any size, resized once
+    """One prompt pair, one task, any number of query pictures.  prompt_img / prompt_tgt: RGB uint8 arrays of any size, or contiguous
+    uint8 CUDA tensors [H][W][3] on the engine's device (what the `paint_*` encoders return), resized once
     (`Image.resize((input_size, input_size))`, Pillow-exact) and kept on the device."""
 
     def __init__(self, model, device, task, prompt_img, prompt_tgt, input_size=448, batch_size=8):
@@ -2260,8 +2524,9 @@ class PainterEngine:
         self.batch_size = int(batch_size)
         assert self.batch_size >= 1
         self.io = DeviceIO(self.device, res=self.res, hres=self.res, patch=int(self.model.patch_size))
-        self.prompt = self.io.resize(self.io.upload(prompt_img), (self.res, self.res))
-        self.prompt_tgt = self.io.resize(self.io.upload(prompt_tgt), (self.res, self.res))
+        on_device = lambda x: _pictures(x, self.device) if torch.is_tensor(x) else self.io.upload(x)
+        self.prompt = self.io.resize(on_device(prompt_img), (self.res, self.res))
+        self.prompt_tgt = self.io.resize(on_device(prompt_tgt), (self.res, self.res))
 
     def stitch(self, queries):
         """queries: uint8 CUDA [N][res][res][3] -> (imgs, tgts) float32 [N][3][2*res][res]."""

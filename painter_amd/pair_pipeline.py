@@ -34,8 +34,8 @@ STD = (0.229, 0.224, 0.225)
 @dataclass
 class PairSpec:
     """One (image, target) pair of a sample and the random decisions of its transform stack."""
-    image: np.ndarray                                   # decoded RGB uint8 [H][W][3]
-    target: np.ndarray                                  # decoded RGB uint8 [H][W][3], same size
+    image: np.ndarray                                   # decoded RGB uint8 [H][W][3], or a contiguous uint8 CUDA tensor of that shape
+    target: np.ndarray                                  # decoded RGB uint8 [H][W][3], same size (e.g. what painter_engine.paint_* returns)
     crop: Tuple[int, int, int, int]                     # RandomResizedCrop.get_params -> (top, left, height, width)
     jitter_ops: Sequence[int] = ()                      # ColorJitter: ops in applied order (BRIGHTNESS ...), empty = not applied
     jitter_factors: Sequence[float] = ()                # factor per op; for HUE the hue_factor in [-0.5, 0.5]
@@ -261,7 +261,8 @@ class DevicePairPipeline:
                      ("mid_row0", "<i4")])          # include/painter_hip.h: pa_crop_job
 
     def resized_crop_batch(self, pictures, boxes, nearest, out):
-        """pictures: decoded uint8 [H][W][3] numpy arrays; boxes: (top, left, h, w) each; nearest: bool each; out: uint8
+        """pictures: decoded uint8 [H][W][3] numpy arrays, or contiguous uint8 CUDA tensors (a job then reads its crop box straight from
+        the tensor: `src` points at the box's first pixel and `src_row_bytes` is the tensor's row pitch, nothing is packed); boxes: (top, left, h, w) each; nearest: bool each; out: uint8
         [n][side][side][3] CUDA tensor written in place.  The crop boxes travel to the device packed in one pinned buffer, the job table in
         one more copy; resize tables for (in, out) size pairs not seen recently are built and uploaded by _table() (2-4 small copies each)."""
         n = len(pictures)
@@ -270,9 +271,13 @@ class DevicePairPipeline:
         sizes = []
         for pic, (i, j, h, w) in zip(pictures, boxes):
             H, W = pic.shape[:2]
-            assert pic.dtype == np.uint8 and pic.ndim == 3 and pic.shape[2] == 3
+            if torch.is_tensor(pic):
+                assert pic.dtype == torch.uint8 and pic.dim() == 3 and pic.shape[2] == 3 and pic.is_contiguous() and pic.is_cuda and \
+                    self.device.index in (None, pic.device.index), (pic.dtype, tuple(pic.shape), pic.device)
+            else:
+                assert pic.dtype == np.uint8 and pic.ndim == 3 and pic.shape[2] == 3
             assert 0 <= i and 0 <= j and h >= 1 and w >= 1 and i + h <= H and j + w <= W, ((i, j, h, w), (H, W))
-            sizes.append((h * w * 3 + 15) & ~15)
+            sizes.append(0 if torch.is_tensor(pic) else (h * w * 3 + 15) & ~15)
         total = sum(sizes)
         if self._pin_event is not None:
             self._pin_event.synchronize()               # the previous step's upload has left the staging buffer
@@ -282,7 +287,8 @@ class DevicePairPipeline:
         off = 0
         offs = []
         for pic, (i, j, h, w), sz in zip(pictures, boxes, sizes):
-            pin[off:off + h * w * 3].reshape(h, w, 3)[...] = pic[i:i + h, j:j + w]
+            if not torch.is_tensor(pic):
+                pin[off:off + h * w * 3].reshape(h, w, 3)[...] = pic[i:i + h, j:j + w]
             offs.append(off)
             off += sz
         dev = torch.empty(total, dtype=torch.uint8, device=self.device)
@@ -293,8 +299,12 @@ class DevicePairPipeline:
         mid_rows = 0
         keep = []
         for k, ((i, j, h, w), near) in enumerate(zip(boxes, nearest)):
-            jobs["src"][k], jobs["dst"][k] = dev.data_ptr() + offs[k], out[k].data_ptr()
-            jobs["src_row_bytes"][k], jobs["h"][k], jobs["w"][k], jobs["nearest"][k] = w * 3, h, w, 1 if near else 0
+            pic = pictures[k]
+            if torch.is_tensor(pic):
+                jobs["src"][k], jobs["src_row_bytes"][k] = pic.data_ptr() + (i * int(pic.shape[1]) + j) * 3, int(pic.shape[1]) * 3
+            else:
+                jobs["src"][k], jobs["src_row_bytes"][k] = dev.data_ptr() + offs[k], w * 3
+            jobs["dst"][k], jobs["h"][k], jobs["w"][k], jobs["nearest"][k] = out[k].data_ptr(), h, w, 1 if near else 0
             if near:
                 if (h, w) != (oh, ow):
                     yt, xt = self._table("pil_nearest", h, oh), self._table("pil_nearest", w, ow)
