@@ -1,0 +1,369 @@
+"""Operands for which attention and the decoder's 3x3 convolution have an EXACT answer, built on the CPU in plain torch.
+
+Attention: softmax as an exact gather.  One key's logit exceeds every other key's by at least 150 in every query row, so exp() of every
+other term is zero in fp32 (exp(-150) = 7e-66) and the row's softmax is one-hot in any correct implementation: out[q] is the V row of
+key t(q) bit for bit, dV is an integer scatter-add of dO rows, and dS = P o (dP - Delta) -- hence dQ, dK and the rel-pos table gradient --
+is exactly zero.  Every operand is an integer that bf16 holds exactly and scale is a power of two, so every logit, lse, dP and Delta is an
+integer fp32 holds exactly.  V is position-coded: a wrong output row names the key, head and sample that arrived in its place.
+
+Convolution (64 channels, 3x3, padding 1): small integers, int64 references from nine shifted matmuls.
+
+The parametrisations of tests/test_attention_exact_gpu.py and tests/test_conv3x3_exact_gpu.py live here, so that
+tests/test_exact_cases_cpu.py can assert, without a GPU, the conditions those tests rest on -- for every one of them."""
+import functools
+from dataclasses import dataclass
+
+import torch
+from torch.overrides import TorchFunctionMode
+
+from tests.test_kernels_gpu import attn_reference
+from tests.test_vit_huge_kernels_gpu import _conv3x3, _conv3x3_dgrad, _conv3x3_wgrad, _tail
+
+SCALE = 0.125                 # head_dim 64 AND head_dim 80: a power of two keeps every logit an integer (80 ** -0.5 would not)
+MIN_MARGIN = 150.0
+AMPLITUDES = (6, 8, 10)       # a_q, cycling over q: neighbouring rows differ in lse and Delta
+TARGET_MAPS = ("identity", "reversal", "permutation", "all_to_last", "all_to_first")
+ATTN_KINDS = TARGET_MAPS + ("bias_rank",)
+
+
+# ------------------------------------------------------------------------------------------------ attention
+@dataclass(frozen=True)
+class AttnCase:
+    kind: str
+    B: int
+    H: int
+    Hp: int
+    Wp: int
+    hd: int
+    qkv: torch.Tensor         # f32 [B*L, 3*H*hd], integer-valued, the layout ops.attn_fwd takes
+    rel_h: torch.Tensor       # f32 [2Hp-1, hd]
+    rel_w: torch.Tensor       # f32 [2Wp-1, hd]
+    dout: torch.Tensor        # f32 [B*L, H*hd], entries in {-1, 0, 1}
+    scale: float = SCALE
+
+    @property
+    def L(self):
+        return self.Hp * self.Wp
+
+
+def _sign(c):
+    """+1 / -1 by the parity of the number of set bits of the channel index: no shift or swap of channels maps the pattern onto itself."""
+    return 1 - 2 * (bin(c).count("1") & 1)
+
+
+def position_coded_v(B, H, Hp, Wp, hd):
+    """-> f32 [B, L, H, hd]: blocks of 16 channels hold kh + 1, kw + 1, head + 1, sample + 1 (and for head_dim 80 1 + key mod 64), each
+    times _sign(channel).  Every magnitude is in 1 .. 64."""
+    assert hd % 16 == 0 and hd >= 64 and Hp <= 63 and Wp <= 63 and H <= 63 and B <= 63
+    L = Hp * Wp
+    k = torch.arange(L)
+    fields = [(k // Wp + 1)[None, :, None].expand(B, L, H), (k % Wp + 1)[None, :, None].expand(B, L, H),
+              (torch.arange(H) + 1)[None, None, :].expand(B, L, H), (torch.arange(B) + 1)[:, None, None].expand(B, L, H),
+              (k % 64 + 1)[None, :, None].expand(B, L, H)]
+    v = torch.stack([fields[c // 16] * _sign(c) for c in range(hd)], -1)
+    return v.float()
+
+
+def decode_v_row(row):
+    """What a position-coded V row says about itself -> dict(kh, kw, head, sample), or None when `row` is no V row (a mixture, zeros)."""
+    row = row.double().cpu()
+    vals = []
+    for blk in range(4):
+        seg = row[blk * 16:(blk + 1) * 16] * torch.tensor([_sign(c) for c in range(blk * 16, (blk + 1) * 16)], dtype=torch.float64)
+        if float(seg.min()) != float(seg.max()) or float(seg[0]) < 1 or float(seg[0]) != int(seg[0]):
+            return None
+        vals.append(int(seg[0]) - 1)
+    return dict(kh=vals[0], kw=vals[1], head=vals[2], sample=vals[3])
+
+
+def _ternary(shape, g):
+    return (torch.randint(0, 3, shape, generator=g) - 1).float()
+
+
+def _pack_qkv(q, k, v):
+    """[B, H, L, hd] x 3 -> [B*L, 3*H*hd] (qkv.reshape(B, L, 3, H, hd))."""
+    B, H, L, hd = q.shape
+    return torch.stack([q, k, v], 0).permute(1, 3, 0, 2, 4).reshape(B * L, 3 * H * hd).contiguous()
+
+
+def _target_map(kind, B, H, L, g):
+    q = torch.arange(L)
+    if kind == "identity":
+        t = q
+    elif kind == "reversal":
+        t = L - 1 - q
+    elif kind == "all_to_last":
+        t = torch.full((L,), L - 1)
+    elif kind == "all_to_first":
+        t = torch.zeros(L, dtype=torch.int64)
+    elif kind == "permutation":
+        return torch.stack([torch.randperm(L, generator=g) for _ in range(B * H)]).reshape(B, H, L)
+    else:
+        raise ValueError(kind)
+    return t[None, None, :].expand(B, H, L).contiguous()
+
+
+def content_case(B, H, Hp, Wp, hd, target_map, seed):
+    """The content term alone decides: key k carries a random sign code c_k in {-8, +8}^hd (drawn per sample and head), query q asks for
+    key t(q) with a_q * sign(c_t(q)).  Target logit 0.125 * hd * 8 * a_q >= 384; every other key's is a sum of hd random signs, a_q * 8 *
+    0.125 each.  Rel-pos tables are zero."""
+    g = torch.Generator().manual_seed(seed)
+    L = Hp * Wp
+    code = (torch.randint(0, 2, (B, H, L, hd), generator=g) * 16 - 8).float()
+    t = _target_map(target_map, B, H, L, g)
+    amp = torch.tensor(AMPLITUDES, dtype=torch.float32)[torch.arange(L) % len(AMPLITUDES)]
+    q = torch.gather(code, 2, t[..., None].expand(B, H, L, hd)) / 8 * amp[None, None, :, None]
+    v = position_coded_v(B, H, Hp, Wp, hd).permute(0, 2, 1, 3)
+    dout = _ternary((B * L, H * hd), g)
+    return AttnCase(target_map, B, H, Hp, Wp, hd, _pack_qkv(q, code, v), torch.zeros(2 * Hp - 1, hd), torch.zeros(2 * Wp - 1, hd), dout)
+
+
+def bias_rank_case(B, H, Hp, Wp, hd, seed):
+    """The bias alone decides, no row excluded: K = 0; q = +8 in channels 0..31; rel_pos_h[j][0..31] = w_h(j), rel_pos_w[j][0..31] = w_w(j),
+    seeded permutations of 0 .. 2Hp-2 and 0 .. 2Wp-2.  logit(q, k) = 256 * (w_h(qh-kh+Hp-1) + w_w(qw-kw+Wp-1)) (the bias term takes the
+    unscaled q): every query has one best reachable row offset and one best column offset, and the margin is 256 times the smaller of the
+    two gaps to the second best.  Logits reach 4e4: only the subtraction of the running maximum keeps exp() finite."""
+    g = torch.Generator().manual_seed(seed)
+    L = Hp * Wp
+    q = torch.zeros(B, H, L, hd)
+    q[..., :32] = 8.0
+    rel_h, rel_w = torch.zeros(2 * Hp - 1, hd), torch.zeros(2 * Wp - 1, hd)
+    rel_h[:, :32] = torch.randperm(2 * Hp - 1, generator=g).float()[:, None]
+    rel_w[:, :32] = torch.randperm(2 * Wp - 1, generator=g).float()[:, None]
+    v = position_coded_v(B, H, Hp, Wp, hd).permute(0, 2, 1, 3)
+    dout = _ternary((B * L, H * hd), g)
+    return AttnCase("bias_rank", B, H, Hp, Wp, hd, _pack_qkv(q, torch.zeros(B, H, L, hd), v), rel_h, rel_w, dout)
+
+
+class _CaptureLogits(TorchFunctionMode):
+    """Keeps the tensor attn_reference hands to torch.logsumexp: the fp64 logits as that function builds them, without restating it.
+    This rests on attn_reference calling torch.logsumexp on the complete logits exactly once; reference() asserts the call count, the dtype
+    and the [B*H, L, L] shape, so a rewrite of attn_reference that breaks it fails there and not silently."""
+    logits = None
+    calls = 0
+
+    def __torch_function__(self, func, types, args=(), kwargs=None):
+        if func is torch.logsumexp:
+            self.logits = args[0]
+            self.calls += 1
+        return func(*args, **(kwargs or {}))
+
+
+@dataclass(frozen=True)
+class AttnExpect:
+    target: torch.Tensor      # int64 [B, H, L]: argmax of the fp64 logits
+    margin: torch.Tensor      # f64 [B, H, L]: top-1 minus top-2
+    top: torch.Tensor         # f64 [B, H, L]: the winning logit (= lse wherever the margin holds)
+    lse: torch.Tensor         # f64 [B*H, L]: attn_reference's own
+    out: torch.Tensor         # f32 [B*L, H*hd]: the gathered V rows
+    dv: torch.Tensor          # int64 [B*L, H*hd]: scatter-add of dO rows
+    runner_up: torch.Tensor   # int64 [B, H, L]
+
+
+def reference(case):
+    """-> AttnExpect.  dq, dk and the rel-pos table gradient are expected to be exactly zero (nothing to return)."""
+    B, H, L, hd = case.B, case.H, case.L, case.hd
+    with _CaptureLogits() as cap:
+        _, lse = attn_reference(case.qkv, case.rel_h, case.rel_w, B, L, H, case.Hp, case.Wp, case.scale)
+    logits = cap.logits
+    assert cap.calls == 1 and logits is not None and logits.dtype == torch.float64 and logits.shape == (B * H, L, L)
+    top2, idx2 = logits.topk(2, dim=-1)
+    target = idx2[..., 0].reshape(B, H, L)
+    v = case.qkv.reshape(B, L, 3, H, hd)[:, :, 2].permute(0, 2, 1, 3)                    # [B, H, L, hd]
+    out = torch.gather(v, 2, target[..., None].expand(B, H, L, hd)).permute(0, 2, 1, 3).reshape(B * L, H * hd).contiguous()
+    do = case.dout.reshape(B, L, H, hd).permute(0, 2, 1, 3).to(torch.int64)
+    dv = torch.zeros(B, H, L, hd, dtype=torch.int64).scatter_add_(2, target[..., None].expand(B, H, L, hd), do)
+    return AttnExpect(target, (top2[..., 0] - top2[..., 1]).reshape(B, H, L), top2[..., 0].reshape(B, H, L), lse, out,
+                      dv.permute(0, 2, 1, 3).reshape(B * L, H * hd).contiguous(), idx2[..., 1].reshape(B, H, L))
+
+
+def dv_fp32_bound(case, exp):
+    """-> f64 [B*L, H*hd]: how far the fp32 build's dV may be from the integer scatter-add.  The backward kernels rebuild P from an lse kept
+    in natural-log units, so at the winner P = 1 +- |logit_q| * 2^-22 (tests/test_attention_exact_gpu.py); dV[k] = sum_q P_q dO_q then errs
+    by at most sum_q |dO_q| |logit_q| 2^-22, plus A[k] N[k] 2^-24 for the fp32 accumulation of N[k] terms whose magnitudes sum to A[k]."""
+    B, H, L, hd = case.B, case.H, case.L, case.hd
+    idx = exp.target[..., None].expand(B, H, L, hd)
+    absdo = case.dout.reshape(B, L, H, hd).permute(0, 2, 1, 3).abs().double()
+    add = lambda src: torch.zeros(B, H, L, hd, dtype=torch.float64).scatter_add_(2, idx, src)
+    A, N, Atop = add(absdo), add(torch.ones_like(absdo)), add(absdo * exp.top.abs()[..., None])
+    return (Atop * 2.0 ** -22 + A * N * 2.0 ** -24).permute(0, 2, 1, 3).reshape(B * L, H * hd)
+
+
+@functools.lru_cache(maxsize=None)
+def attn_case(kind, B, H, Hp, Wp, hd):
+    """The case of one (kind, shape) and its reference, built once per process and shared by every route that runs it: read-only."""
+    seed = 1000 * Hp + 10 * Wp + hd + ATTN_KINDS.index(kind)
+    case = bias_rank_case(B, H, Hp, Wp, hd, seed) if kind == "bias_rank" else content_case(B, H, Hp, Wp, hd, kind, seed)
+    return case, reference(case)
+
+
+# route -> (dtype name, head_dim, generation to set, kernel family the launch counters must show (0 generic, 1 generation 2, 2 generation 3),
+#           [(B, H, Hp, Wp)])
+_G3 = [(2, 2, 8, 28), (2, 2, 16, 28)]
+_G2_SHAPE = [(2, 2, 8, 12), (2, 2, 8, 20), (2, 2, 16, 16), (2, 2, 8, 24)]
+_GENERIC = [(2, 2, 8, 4), (2, 2, 16, 8), (2, 2, 4, 32)]
+_HD80_G2, _HD80_WP32, _HD80_GENERIC = [(2, 2, 8, 12), (2, 2, 16, 28)], [(2, 2, 4, 32)], [(2, 2, 8, 4)]
+FULL_GRID = (1, 1, 56, 28)                                     # 13 workgroups per head, the 13th with one live wave of four
+FULL_GRID_KINDS = ("reversal", "all_to_last", "all_to_first", "bias_rank")
+ATTN_ROUTES = {
+    "bf16_hd64_gen3": ("bf16", 64, 0, 2, _G3),
+    "bf16_hd64_gen3_full": ("bf16", 64, 0, 2, [FULL_GRID]),
+    "bf16_hd64_gen2_forced": ("bf16", 64, 2, 1, _G3),
+    "bf16_hd64_gen2": ("bf16", 64, 0, 1, _G2_SHAPE),
+    "bf16_hd64_generic": ("bf16", 64, 0, 0, _GENERIC),
+    "bf16_hd80_gen2": ("bf16", 80, 0, 1, _HD80_G2),
+    "bf16_hd80_gen2_wp32": ("bf16", 80, 0, 1, _HD80_WP32),
+    "bf16_hd80_generic": ("bf16", 80, 0, 0, _HD80_GENERIC),
+    "fp32_hd64": ("fp32", 64, 0, 0, _G3 + _G2_SHAPE + _GENERIC),
+    "fp32_hd64_full": ("fp32", 64, 0, 0, [FULL_GRID]),
+    "fp32_hd80": ("fp32", 80, 0, 0, _HD80_G2 + _HD80_WP32 + _HD80_GENERIC),
+}
+# the shortest grids the generation-2 kernels run through the C ABI (L = 64 and L = 96; attn2_ok alone would admit (2, 16), but pa_attn_fwd and
+# pa_attn_bwd refuse Hp % 4 != 0): new to the suite, kept apart and run after the rest
+SHORT_GRIDS = [(2, 2, 4, 16), (2, 2, 4, 24)]
+SHORT_ROUTES = {"bf16_hd64_gen2_short": ("bf16", 64, 0, 1, SHORT_GRIDS), "bf16_hd80_gen2_short": ("bf16", 80, 0, 1, SHORT_GRIDS)}
+PREP_LAUNCH_GRID = (2, 2, 16, 28)                              # the generation-3 backward with prep="launch"
+# ... on every kind there, and bias_rank once more on the full grid: the one case in which P's bf16 bits at the winner are not those of 1
+PREP_LAUNCH_CASES = [(kind, PREP_LAUNCH_GRID) for kind in ATTN_KINDS] + [("bias_rank", FULL_GRID)]
+
+
+def route_params(routes):
+    """-> [(route, kind, B, H, Hp, Wp)] in the order the GPU tests run them."""
+    out = []
+    for route, (_, _, _, _, grids) in routes.items():
+        for grid in grids:
+            for kind in (FULL_GRID_KINDS if grid == FULL_GRID else ATTN_KINDS):
+                out.append((route, kind) + grid)
+    return out
+
+
+def attn_shapes():
+    """Every distinct (kind, B, H, Hp, Wp, hd) the GPU tests build."""
+    seen = []
+    for routes in (ATTN_ROUTES, SHORT_ROUTES):
+        for route, kind, B, H, Hp, Wp in route_params(routes):
+            key = (kind, B, H, Hp, Wp, routes[route][1])
+            if key not in seen:
+                seen.append(key)
+    return seen
+
+
+# ------------------------------------------------------------------------------------------------ 3x3 convolution
+C = 64
+# route -> (dtype name, (B, Hi, Wi), P, takes the tile kernels of conv64.h)
+CONV_ROUTES = {"bf16_tile": ("bf16", (2, 8, 128), 8, True), "bf16_gather_p16": ("bf16", (2, 16, 96), 16, False),
+               "bf16_gather_p14": ("bf16", (2, 28, 56), 14, False), "fp32": ("fp32", (2, 8, 64), 8, False)}
+CONV_KINDS = ("int", "stamp")
+WGRAD_CAPS = (0, 1, 3, 5)     # knob 9 on the tile route: workgroups that walk many tiles
+
+
+@dataclass(frozen=True)
+class ConvCase:
+    kind: str
+    x: torch.Tensor           # f32 NHWC [B, Hi, Wi, 64]
+    dy: torch.Tensor          # f32 NHWC: the output gradient of the data-gradient check
+    dy_w: torch.Tensor        # f32 NHWC: the output gradient of the weight-gradient check
+    w3: torch.Tensor          # f32 [cout, cin, 3, 3]
+    b3: torch.Tensor          # f32 [64]
+    hot: tuple = ()           # stamp case: ((b, row, col, channel), ...), the hot pixels of x and of dy
+
+
+def conv_int_case(B, Hi, Wi, seed):
+    """x and dy sparse ternary (non-zero with probability 1/3), w3 ternary, b3 an integer in [-8, 8]."""
+    g = torch.Generator().manual_seed(seed)
+    sparse = lambda: _ternary((B, Hi, Wi, C), g) * (torch.rand((B, Hi, Wi, C), generator=g) < 0.5).float()      # 2/3 * 1/2 = 1/3 non-zero
+    x, dy = sparse(), sparse()
+    return ConvCase("int", x, dy, dy, _ternary((C, C, 3, 3), g), torch.randint(-8, 9, (C,), generator=g).float())
+
+
+def stamp_weight():
+    """w3[co][ci][ky][kx] = s(co) * (1 + 3 ky + kx + 9 (ci mod 8)), s alternating over co: magnitudes 1 .. 72 (inside the 81 allowed)."""
+    co, ci, ky, kx = torch.meshgrid(torch.arange(C), torch.arange(C), torch.arange(3), torch.arange(3), indexing="ij")
+    return ((1 - 2 * (co % 2)) * (1 + 3 * ky + kx + 9 * (ci % 8))).float()
+
+
+def stamp_bias():
+    return (torch.arange(C) % 17 - 8).float()
+
+
+def decode_stamp(value):
+    """|weight| -> (ky, kx, ci mod 8) of stamp_weight(), or None."""
+    m = int(round(abs(float(value)))) - 1
+    if m < 0 or m >= 72 or abs(float(value)) != m + 1:
+        return None
+    return dict(ky=(m % 9) // 3, kx=m % 3, ci_mod_8=m // 9)
+
+
+def stamp_pixels(B, Hi, Wi):
+    """Hot pixels (b, row, col), at least 3 apart within a sample: sample 0 -- the four corners (the last one is the sample's last pixel),
+    the middle of each edge, rows 1 | 2 (weight-gradient tile boundary) and rows 3 | 4 (forward tile boundary); sample 1 -- its first pixel,
+    its last pixel, columns 63 | 64 (strip boundary) where Wi > 64, and rows 1 | 2 and 3 | 4 once more at other columns."""
+    px = [(0, 0, 0), (0, 0, Wi - 1), (0, Hi - 1, 0), (0, Hi - 1, Wi - 1),
+          (0, 0, Wi // 2), (0, Hi - 1, Wi // 2), (0, Hi // 2, 0), (0, Hi // 2, Wi - 1),
+          (0, 1, 5), (0, 2, 8), (0, 3, 11), (0, 4, 14)]
+    if B > 1:
+        px += [(1, 0, 0), (1, Hi - 1, Wi - 1), (1, 1, 20), (1, 2, 23), (1, 3, 26), (1, 4, 29)]
+        if Wi > 64:
+            px += [(1, 2, 63), (1, 5, 64)]
+    for i, (b, r, c) in enumerate(px):
+        assert 0 <= r < Hi and 0 <= c < Wi
+        for (b2, r2, c2) in px[:i]:
+            assert b != b2 or max(abs(r - r2), abs(c - c2)) >= 3, ((b, r, c), (b2, r2, c2))
+    return px
+
+
+def conv_stamp_case(B, Hi, Wi):
+    """x (and dy for the data gradient) zero except single ones at stamp_pixels(), each in another channel: the output around a hot pixel is
+    the flipped (data gradient: un-flipped) kernel of that channel, stamped; everywhere else it is b3 (data gradient: 0).  For the weight
+    gradient dy_w is hot one tap away from each hot x pixel -- the tap cycles over the nine, clipped at the border, and is forced across
+    each boundary: row 1 -> 2, 2 -> 1, 3 -> 4, 4 -> 3, column 63 -> 64, 64 -> 63, and sample 0's last pixel pairs with the hot first pixel of
+    sample 1, which is NOT its neighbour."""
+    px = stamp_pixels(B, Hi, Wi)
+    x, dy, dy_w = (torch.zeros(B, Hi, Wi, C) for _ in range(3))
+    hot = []
+    for i, (b, r, c) in enumerate(px):
+        ch = (11 * i + 3) % C
+        hot.append((b, r, c, ch))
+        x[b, r, c, ch] = 1.0
+        dy[b, r, c, ch] = 1.0
+        dr, dc = i % 3 - 1, (i // 3) % 3 - 1
+        if r in (1, 3) and c not in (0, Wi - 1):
+            dr = 1
+        elif r in (2, 4) and c not in (0, Wi - 1, 63):
+            dr = -1
+        if c == 63:
+            dr, dc = 0, 1
+        elif c == 64 and r not in (0, Hi - 1):
+            dr, dc = 0, -1
+        r2, c2 = min(max(r + dr, 0), Hi - 1), min(max(c + dc, 0), Wi - 1)
+        dy_w[b, r2, c2, (7 * i + 1) % C] = 1.0
+    return ConvCase("stamp", x, dy, dy_w, stamp_weight(), stamp_bias(), tuple(hot))
+
+
+@dataclass(frozen=True)
+class ConvExpect:
+    y3: torch.Tensor          # int64 NHWC: conv + b3
+    dx: torch.Tensor          # int64 NHWC: the transposed conv of dy
+    dw: torch.Tensor          # int64 [cout, cin, 3, 3]: the weight gradient of (dy_w, x)
+
+
+def conv_reference(case):
+    """int64, by the shifted matmuls of tests/test_vit_huge_kernels_gpu.py (checked there against torch's own conv in fp64)."""
+    x, dy, dy_w, w3 = (t.to(torch.int64) for t in (case.x, case.dy, case.dy_w, case.w3))
+    return ConvExpect(_conv3x3(x, w3) + case.b3.to(torch.int64), _conv3x3_dgrad(dy, w3), _conv3x3_wgrad(dy_w, x))
+
+
+def unshuffle(dx, B, Hp, Wp, P):
+    """NHWC [B, Hp*P, Wp*P, 64] -> token rows [B*Hp*Wp, P*P*64] (the inverse of the decoder's pixel shuffle)."""
+    return dx.reshape(B, Hp, P, Wp, P, C).permute(0, 1, 3, 2, 4, 5).reshape(B * Hp * Wp, P * P * C)
+
+
+@functools.lru_cache(maxsize=None)
+def conv_case(kind, B, Hi, Wi):
+    case = conv_stamp_case(B, Hi, Wi) if kind == "stamp" else conv_int_case(B, Hi, Wi, 100 * Hi + Wi)
+    return case, conv_reference(case)
+
+
+def tail_reference(y3, gamma, beta, w1, b1, eps):
+    """LayerNorm2D(64) . GELU . Conv1x1(64 -> 3) in fp64 on NHWC y3 -> NCHW pred."""
+    return _tail(y3.double(), gamma.double(), beta.double(), w1.double(), b1.double(), eps)
