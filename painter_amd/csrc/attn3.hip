@@ -158,7 +158,9 @@ __global__ __launch_bounds__(NT, STAGES == 1 ? 4 : 2) void fwd_kernel(const bf16
             tmax = fmaxf(tmax, xor32(tmax));
             if (j == 0 || __any(tmax > THR)) {          // wave-uniform; after the first tiles almost never taken
                 const float delta = (j == 0) ? tmax : fmaxf(tmax, 0.f);
-                const float alpha = __builtin_amdgcn_exp2f(-delta);
+                // j == 0: l and O are still zero and there is nothing to rescale; exp2(-tmax) of a first tile that lies wholly below
+                // 2^-128 would be inf, and 0 * inf a NaN that never leaves the row
+                const float alpha = (j == 0) ? 1.f : __builtin_amdgcn_exp2f(-delta);
                 m += delta;
                 l *= alpha;
 #pragma unroll

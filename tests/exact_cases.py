@@ -6,9 +6,12 @@ key t(q) bit for bit, dV is an integer scatter-add of dO rows, and dS = P o (dP 
 is exactly zero.  Every operand is an integer that bf16 holds exactly and scale is a power of two, so every logit, lse, dP and Delta is an
 integer fp32 holds exactly.  V is position-coded: a wrong output row names the key, head and sample that arrived in its place.
 
+Attention with tied winners (tie_case, further down): 1, 2 or 4 keys tie at logit exactly 0 in every row, so P = 1/n and dS, dQ, dK and the
+table gradients are non-zero dyadic rationals; the expectation is the fp64 autograd of attn_reference.
+
 Convolution (64 channels, 3x3, padding 1): small integers, int64 references from nine shifted matmuls.
 
-The parametrisations of tests/test_attention_exact_gpu.py and tests/test_conv3x3_exact_gpu.py live here, so that
+The parametrisations of tests/test_attention_exact_gpu.py, tests/test_attention_ties_gpu.py and tests/test_conv3x3_exact_gpu.py live here, so that
 tests/test_exact_cases_cpu.py can assert, without a GPU, the conditions those tests rest on -- for every one of them."""
 import functools
 from dataclasses import dataclass
@@ -242,6 +245,305 @@ def attn_shapes():
     seen = []
     for routes in (ATTN_ROUTES, SHORT_ROUTES):
         for route, kind, B, H, Hp, Wp in route_params(routes):
+            key = (kind, B, H, Hp, Wp, routes[route][1])
+            if key not in seen:
+                seen.append(key)
+    return seen
+
+
+# ------------------------------------------------------------------------------------------------ attention: tied winners
+# Several keys tie exactly for first place, every other key is >= 150 below: P is exactly 1/n on the n winners (n in {1, 2, 4}) and 0
+# elsewhere, so dS = P o (dP - Delta) is a NON-ZERO dyadic rational of a few bits and so are dQ, dK, dV and both table gradients: the fp64
+# autograd of attn_reference is the exact answer (tests/test_attention_ties_gpu.py; conditions in tests/test_exact_cases_cpu.py).
+TIE_AMPLITUDES = (12, 14, 16)                       # a_q, cycling over q
+TIE_WINNERS = (4, 2, 1)                             # winners of a row: index (r % 3 + r % 5) % 3 with r = L - 1 - q -- the last row has four
+TIE_PLACEMENTS = ("near", "quarter", "mirror")
+TIE_KINDS = tuple("tie_" + p for p in TIE_PLACEMENTS) + tuple("tie_%s_sparse" % p for p in TIE_PLACEMENTS)     # dO dense | ~6 % non-zero
+
+
+def tie_kinds(grid, hd):
+    """A dense dO on the head-dim-64 grids below the full one; the sparse one everywhere.  Where V's magnitudes (key rows up to 56, the
+    fifth field of head dim 80 up to 64) meet a dense dO, some dS need a ninth significant bit and bf16 no longer holds them (asserted
+    case by case in tests/test_exact_cases_cpu.py for what IS built); the full grid runs once per placement in any case."""
+    return TIE_KINDS if hd == 64 and grid != FULL_GRID else TIE_KINDS[3:]
+
+TIE_SPARSE_DENSITY = 1.0 / 16
+
+
+def tie_layout(hd):
+    """-> (active, S1, S2, shift channels, offset channel): channel index lists.  The hd - 20 `active` channels carry the group's code, S1
+    and S2 (8 channels each) the two flip sets, the three shift channels (one per number of code channels a query keeps) bring every
+    winning logit to 0, and the offset channel codes the table row in both tables."""
+    na = hd - 20
+    # interleave the roles over the head dim, so that no 16-channel k-step holds one role alone
+    order = sorted(range(hd), key=lambda c: (c * 37) % hd)
+    return order[:na], order[na:na + 8], order[na + 8:na + 16], order[na + 16:na + 19], order[na + 19]
+
+
+def tie_members(placement, L):
+    """-> int64 [L/4, 4]: the keys of each group; member m and member m ^ 2 are the pair a two-way tie leaves."""
+    g = torch.arange(L // 4)
+    if placement == "near":                         # neighbours, two keys off the multiples of four: mostly one 32-key tile and one key row,
+        m = [(4 * g + 2 + i) % L for i in range(4)]  # some across a row or tile boundary, and one group is keys L - 2, L - 1, 0, 1
+    elif placement == "quarter":                    # a quarter of the grid apart: other tiles, key rows and dKV workgroups
+        m = [g, g + L // 4, g + L // 2, g + 3 * (L // 4)]
+    elif placement == "mirror":                     # k and L - 1 - k pair up: the first and last key rows and the last tile take part
+        m = [g, L // 2 - 1 - g, L - 1 - g, L // 2 + g]
+    else:
+        raise ValueError(placement)
+    return torch.stack(m, 1)
+
+
+def tie_winner_count(L):
+    r = L - 1 - torch.arange(L)
+    return torch.tensor(TIE_WINNERS)[(r % 3 + r % 5) % 3]
+
+
+def tie_case(B, H, Hp, Wp, hd, placement, sparse, seed):
+    """Keys come in groups of four that share a random code in {-8, +8} on the active channels and differ by the sign of one or both
+    flip sets; query q asks for the group of key t(q) (a permutation per (sample, head)) with a_q * sign(code), and is zero on both flip sets
+    (four winners), on S2 only (two: t and its partner) or on neither (one).  The nearest loser differs on a flip set the query kept: 16 a_q
+    >= 192 below.  Shift channels: a query keeps n_c = hd - 20, hd - 12 or hd - 4 code channels; the shift channel of that count holds
+    K = -8 n_c in every key and q = a_q there (zero in the other two), so every logit of the row moves down by the row's top logit a_q n_c
+    and the winners sit at exactly 0 -- as an integer sum inside the Q.K^T product.  (NOT through the tables: a constant table entry
+    times q would do the same in exact arithmetic, but the generation-2 kernels keep q . rel_pos_h times log2 e as bf16 -- attn2.hip:61 --
+    and the generic ones as a rounded fp32 -- attn_common.h:151 --, which un-ties nothing but moves lse by up to 2.  So q . R is exactly
+    zero in every tie case: q is zero wherever a table is not.)  Offset channel: q = K = 0, rel_pos_h[j] = rel_pos_w[j] = j + 1 -- no
+    logit changes, and dQ there is sum_k dS[q, k] (Rh[qh - kh] + Rw[qw - kw]), which names the offsets the kernel used.  Every q entry is 0
+    or +-a_q, three significant bits: that keeps the fp32 sums of the table gradients exact."""
+    g = torch.Generator().manual_seed(seed)
+    L = Hp * Wp
+    assert L % 4 == 0
+    active, s1, s2, shift, offset = tie_layout(hd)
+    members = tie_members(placement, L)
+    group_of, member_of = torch.empty(L, dtype=torch.int64), torch.empty(L, dtype=torch.int64)
+    group_of[members] = torch.arange(L // 4)[:, None].expand(L // 4, 4)
+    member_of[members] = torch.arange(4)[None, :].expand(L // 4, 4)
+    while True:                                     # group codes at least 8 active channels apart (>= 192 below, as the flip sets are)
+        gcode = (torch.randint(0, 2, (B, H, L // 4, hd), generator=g) * 16 - 8).float()
+        a = gcode[..., active] / 8
+        if int(((len(active) - a @ a.transpose(-1, -2)) / 2 + 99 * torch.eye(L // 4)).min()) >= 8:
+            break
+    k = gcode[:, :, group_of]                       # [B, H, L, hd]
+    k[..., s1] *= (1 - 2 * (member_of & 1)).float()[None, None, :, None]
+    k[..., s2] *= (1 - 2 * (member_of >> 1)).float()[None, None, :, None]
+    k[..., shift] = -8.0 * torch.tensor([len(active), len(active) + 8, len(active) + 16])       # for rows of 4, 2, 1 winners
+    k[..., offset] = 0
+    t = _target_map("permutation", B, H, L, g)
+    amp = torch.tensor(TIE_AMPLITUDES, dtype=torch.float32)[torch.arange(L) % len(TIE_AMPLITUDES)]
+    n = tie_winner_count(L)
+    q = torch.gather(k, 2, t[..., None].expand(B, H, L, hd)) / 8 * amp[None, None, :, None]
+    q[:, :, :, s1] *= (n < 4).float()[None, None, :, None]
+    q[:, :, :, s2] *= (n < 2).float()[None, None, :, None]
+    q[..., shift] = (amp[:, None] * (torch.tensor(TIE_WINNERS)[None, :] == n[:, None]).float())[None, None]
+    q[..., offset] = 0
+    rel_h, rel_w = torch.zeros(2 * Hp - 1, hd), torch.zeros(2 * Wp - 1, hd)
+    rel_h[:, offset], rel_w[:, offset] = torch.arange(1, 2 * Hp).float(), torch.arange(1, 2 * Wp).float()
+    v = position_coded_v(B, H, Hp, Wp, hd).permute(0, 2, 1, 3)
+    dout = _ternary((B * L, H * hd), g)
+    if sparse:
+        dout = dout * (torch.rand((B * L, H * hd), generator=g) < 1.5 * TIE_SPARSE_DENSITY).float()     # 2/3 * 3/32 = 1/16 non-zero
+    return AttnCase("tie_" + placement + ("_sparse" if sparse else ""), B, H, Hp, Wp, hd, _pack_qkv(q, k, v), rel_h, rel_w, dout)
+
+
+def tie_algebra(case, fault=None):
+    """Softmax attention forward and backward written out by hand in fp64 -> dict(logits, P, dP, delta, dS, dG_h, dG_w, out, lse, dq, dk,
+    dv, drh, drw), every matrix [B*H, L, .], the data gradients [B*L, H*hd], the tables [2Hp-1 | 2Wp-1, hd].  Without `fault` this is the
+    expectation once more (tie_reference asserts it against autograd); with one it is what a named wrong BACKWARD would return from the
+    right forward:
+      delta_next_row     Delta of query q + 1 (of the head's first query for its last)
+      kh_class_phase     the rel_pos_h row of the keys of one tile phase -- the 32-key tiles whose number is that of the last tile mod 7 --
+                         taken one too high (clamped), in dQ and in the table gradient
+      last_key_row       the keys of the last key row left out of the rel_pos_h gradient
+      l_previous_row     P divided by the l of query q - 1 instead of its own
+      dg_column_dropped  the middle column of the per-query bias gradient (rel_pos_h row Hp - 1: key row = query row) left out of the
+                         table-gradient contraction
+    On a tie case P is set to exactly 1 / n on the winners (fp64's exp(-log n) is 1e-16 off, and every loser's exp() is below 1e-65)."""
+    B, H, L, hd, Hp, Wp, s = case.B, case.H, case.L, case.hd, case.Hp, case.Wp, case.scale
+    q, k, v = case.qkv.double().reshape(B, L, 3, H, hd).permute(2, 0, 3, 1, 4).reshape(3, B * H, L, hd).unbind(0)
+    do = case.dout.double().reshape(B, L, H, hd).permute(0, 2, 1, 3).reshape(B * H, L, hd)
+    Rh, Rw = case.rel_h.double(), case.rel_w.double()
+    key = torch.arange(L)
+    ih = (key[:, None] // Wp - key[None, :] // Wp + Hp - 1)                      # [L, L]: table row of (query, key)
+    iw = (key[:, None] % Wp - key[None, :] % Wp + Wp - 1)
+    Gh, Gw = q @ Rh.t(), q @ Rw.t()                                               # the per-query bias tables [B*H, L, 2Hp-1 | 2Wp-1]
+    BH = B * H
+    logits = s * q @ k.transpose(1, 2) + torch.gather(Gh, 2, ih.expand(BH, L, L)) + torch.gather(Gw, 2, iw.expand(BH, L, L))
+    lse = torch.logsumexp(logits, -1)
+    P = torch.exp(logits - lse[..., None])
+    if case.kind.startswith("tie"):
+        P = (logits == 0).double() / (logits == 0).sum(-1, keepdim=True)
+    out = P @ v
+    dP = do @ v.transpose(1, 2)
+    delta = (out * do).sum(-1)
+    Pb, delta_b, ih_b = P, delta, ih
+    if fault == "delta_next_row":
+        delta_b = delta.roll(-1, 1)
+    elif fault == "l_previous_row":
+        Pb = P * torch.exp(lse - lse.roll(1, 1))[..., None]
+    elif fault == "kh_class_phase":
+        ih_b = torch.where(((key // 32) % 7 == ((L - 1) // 32) % 7)[None, :], (ih + 1).clamp_max(2 * Hp - 2), ih)
+    elif fault not in (None, "last_key_row", "dg_column_dropped"):
+        raise ValueError(fault)
+    dS = Pb * (dP - delta_b[..., None])
+    dS_h = dS * (key // Wp != Hp - 1)[None, None, :] if fault == "last_key_row" else dS
+    dG_hq = torch.zeros(BH, L, 2 * Hp - 1, dtype=torch.float64).scatter_add_(2, ih_b.expand(BH, L, L), dS)       # what dQ contracts
+    dG_h = dG_hq if fault != "last_key_row" else torch.zeros_like(dG_hq).scatter_add_(2, ih_b.expand(BH, L, L), dS_h)
+    dG_w = torch.zeros(BH, L, 2 * Wp - 1, dtype=torch.float64).scatter_add_(2, iw.expand(BH, L, L), dS)
+    dq = s * dS @ k + dG_hq @ Rh + dG_w @ Rw
+    if fault == "dg_column_dropped":
+        dG_h = dG_h.clone()
+        dG_h[..., Hp - 1] = 0
+    dk = s * dS.transpose(1, 2) @ q
+    dv = Pb.transpose(1, 2) @ do
+    rows = lambda t: t.reshape(B, H, L, hd).permute(0, 2, 1, 3).reshape(B * L, H * hd)
+    return dict(logits=logits, P=P, dP=dP, delta=delta, dS=dS, dG_h=dG_h, dG_w=dG_w, Gh=Gh, Gw=Gw, out=rows(out), lse=lse,
+                dq=rows(dq), dk=rows(dk), dv=rows(dv), drh=torch.einsum("bqj,bqc->jc", dG_h, q), drw=torch.einsum("bqj,bqc->jc", dG_w, q))
+
+
+def tie_quantum(t):
+    """The smallest spacing of the values of `t`: the largest power of two (down to 2^-10) that divides every one of them."""
+    for e in range(12, -11, -1):
+        x = t.double() * 2.0 ** -e
+        if float((x - x.round()).abs().max()) < 1e-9:
+            return 2.0 ** e
+    raise AssertionError("not dyadic to 2^-10")
+
+
+def tie_fp32_bounds(case, alg):
+    """-> dict(dq, dk, dv [B*L, H*hd], drcat [2Hp-1 + 2Wp-1, hd]), f64: how far the fp32 build may be from the exact answer, element by
+    element, as (sum of |terms|) * c * 2^-22.  The fp32 build runs the generic kernels.  At a winner s = 0 and the bias is 0, so the
+    backward's exponent is -lse2 alone, lse2 = lse * LOG2E_F (attn_bwd.hip:139, :201-204 and :415-418) with lse = (m + log2 l) * LN2_F
+    (attn_fwd.hip:150), m = 0 and l = n exactly: v_log_f32 is good to 1 ulp (2^-23 relative), the two multiplications round by 2^-24 each
+    and LN2_F * LOG2E_F is 1 - 2^-26.5, so the exponent is off by at most 2.13 * 2^-23 * log2 n <= 4.26 * 2^-23, P by a factor
+    1 +- (ln 2 * 4.26 + 1) * 2^-23 (v_exp_f32: 1 ulp) -- under 2 * 2^-22 -- and dS = P * (dP - Delta) (attn_bwd.hip:205-208) by 2.25 * 2^-22
+    of itself, dP and Delta being exact.  An fp32 sum of N non-zero terms in whatever order adds at most N * 2^-24 = (N / 4) * 2^-22 of the
+    sum of their magnitudes.  So c = 2.25 + N / 4 (dV: 2 + N / 4, it takes P), with N
+      dq     20: at most 4 winners -- 4 content products, 4 + 4 additions into the two bias-gradient tables (attn_bwd.hip:209-217), 4 + 4
+             table products (attn_bwd.hip:286);
+      dk dv  the number of queries the key wins;
+      drcat  in three steps.  The bias gradient dG[q][j] is a sum of at most 4 dS, 3.25 * 2^-22 of the sum of their magnitudes off, and
+             often far smaller than that sum.  The table gradient is a split-K GEMM over the B * L token rows, one batch per head
+             (attn_bwd.hip:618-640): slab (split z, head h) holds the rows [z * klen, (z + 1) * klen) of head h, klen = ceil(ceil(B L / 32) /
+             splits) * 32 with splits = min(16, ceil(B L / 32)) (gemm_engine.h:66-71, :228-229; BK = 32 for fp32, common.h:20; 16 is the
+             default that ops.py leaves in place), and one accumulator per output element adds a slab's products dG * q in sequence
+             (gemm_engine.h:192-217): (N_s / 4) * 2^-22 of the slab's
+             sum of |dG| |q|, N_s = its rows with a non-zero dG in that table row.  pa_slab_reduce then adds the S = splits * heads slabs in
+             an order this bound does not depend on: (S / 4) * 2^-22 of the whole sum.  (Both taken 1.001 times, for dG's own error.)"""
+    B, H, L, hd, Hp, Wp, s = case.B, case.H, case.L, case.hd, case.Hp, case.Wp, case.scale
+    q, k, _ = case.qkv.double().reshape(B, L, 3, H, hd).permute(2, 0, 3, 1, 4).reshape(3, B * H, L, hd).unbind(0)
+    do = case.dout.double().reshape(B, L, H, hd).permute(0, 2, 1, 3).reshape(B * H, L, hd)
+    key = torch.arange(L)
+    ih = (key[:, None] // Wp - key[None, :] // Wp + Hp - 1).expand(B * H, L, L)
+    iw = (key[:, None] % Wp - key[None, :] % Wp + Wp - 1).expand(B * H, L, L)
+    adS = alg["dS"].abs()
+    aGh = torch.zeros(B * H, L, 2 * Hp - 1, dtype=torch.float64).scatter_add_(2, ih, adS)
+    aGw = torch.zeros(B * H, L, 2 * Wp - 1, dtype=torch.float64).scatter_add_(2, iw, adS)
+    fan = (alg["P"] != 0).sum(1).double()[..., None]                                   # [B*H, L, 1]: queries the key wins
+    rows = lambda t: t.reshape(B, H, L, hd).permute(0, 2, 1, 3).reshape(B * L, H * hd)
+    u = 2.0 ** -22
+    aG = torch.cat([aGh, aGw], 2)
+    dG = torch.cat([alg["dG_h"], alg["dG_w"]], 2).abs()
+    R, nku = B * L, (B * L + 31) // 32
+    splits = min(16, nku)
+    klen = (nku + splits - 1) // splits * 32
+    nsl = (R + klen - 1) // klen
+
+    def slabs(t):       # [B*H, L, X] -> [H, slab, klen, X], token rows b * L + l, zero rows behind the end
+        t = t.reshape(B, H, L, -1).permute(1, 0, 2, 3).reshape(H, R, -1)
+        return torch.cat([t, t.new_zeros(H, nsl * klen - R, t.shape[-1])], 1).reshape(H, nsl, klen, -1)
+    a_slab = torch.einsum("hsrj,hsrc->hsjc", slabs(dG), slabs(q.abs()))
+    n_slab = (slabs(aG) != 0).sum(2).double()                                           # [H, slab, J]
+    tab_sum = (a_slab * n_slab[..., None] / 4).sum((0, 1)) + a_slab.sum((0, 1)) * (splits * H) / 4
+    return dict(dq=rows(s * adS @ k.abs() + aGh @ case.rel_h.double().abs() + aGw @ case.rel_w.double().abs()) * (2.25 + 20 / 4) * u,
+                dk=rows(s * adS.transpose(1, 2) @ q.abs() * (2.25 + fan / 4)) * u,
+                dv=rows(alg["P"].transpose(1, 2) @ do.abs() * (2 + fan / 4)) * u,
+                drcat=(torch.einsum("bqj,bqc->jc", aG, q.abs()) * 3.25 + tab_sum * 1.001) * u)
+
+
+def tie_exact_sums(case, alg):
+    """-> dict name -> the largest sum of |terms| of any fp32 accumulation behind that tensor, in units of 1/64 (dS is a multiple of 1/16, K
+    of 8 = 1 / scale, q of 2, the table entries and dO are integers, P a multiple of 1/4: every term of every sum is a multiple of 1/64 at
+    the least).  Below 2^24 every partial sum, in any order, is a multiple of 1/64 that fp32 holds exactly."""
+    B, H, L, hd, Hp, Wp, s = case.B, case.H, case.L, case.hd, case.Hp, case.Wp, case.scale
+    q, k, v = case.qkv.double().reshape(B, L, 3, H, hd).permute(2, 0, 3, 1, 4).reshape(3, B * H, L, hd).unbind(0)
+    do = case.dout.double().reshape(B, L, H, hd).permute(0, 2, 1, 3).reshape(B * H, L, hd)
+    key = torch.arange(L)
+    ih = (key[:, None] // Wp - key[None, :] // Wp + Hp - 1).expand(B * H, L, L)
+    iw = (key[:, None] % Wp - key[None, :] % Wp + Wp - 1).expand(B * H, L, L)
+    adS = alg["dS"].abs()
+    aGh = torch.zeros(B * H, L, 2 * Hp - 1, dtype=torch.float64).scatter_add_(2, ih, adS)
+    aGw = torch.zeros(B * H, L, 2 * Wp - 1, dtype=torch.float64).scatter_add_(2, iw, adS)
+    return {"q.k": float((q.abs() @ k.abs().transpose(1, 2)).max()) * 64, "dP": float((do.abs() @ v.abs().transpose(1, 2)).max()) * 64,
+            "delta": float((alg["P"] @ v.abs() * do.abs()).sum(-1).max()) * 64, "out": float((alg["P"] @ v.abs()).max()) * 64,
+            "dq": float((adS @ k.abs() + aGh @ case.rel_h.double().abs() + aGw @ case.rel_w.double().abs()).max()) * 64,
+            "dk": float((adS.transpose(1, 2) @ q.abs()).max()) * 64, "dv": float((alg["P"].transpose(1, 2) @ do.abs()).max()) * 64,
+            "drcat": float(torch.einsum("bqj,bqc->jc", torch.cat([aGh, aGw], 2), q.abs()).max()) * 64}
+
+
+TIE_FAULTS = ("delta_next_row", "kh_class_phase", "last_key_row", "l_previous_row", "dg_column_dropped")
+
+
+@dataclass(frozen=True)
+class TieExpect:
+    nwin: torch.Tensor        # int64 [B, H, L]: winners of the row (logit exactly 0)
+    loser: torch.Tensor       # f64: the largest logit below the winners, over the whole case
+    out: torch.Tensor         # f64 [B*L, H*hd]
+    lse: torch.Tensor         # f64 [B*H, L]: log nwin
+    dq: torch.Tensor          # f64 [B*L, H*hd] x 3: autograd of attn_reference, the exact dyadic answer
+    dk: torch.Tensor
+    dv: torch.Tensor
+    drcat: torch.Tensor       # f64 [2Hp-1 + 2Wp-1, hd]: d rel_pos_h over d rel_pos_w, the rows attn_bwd_relpos returns in front of its padding
+
+
+def tie_reference(case):
+    """fp64 autograd through attn_reference; the logits it built say who won."""
+    B, H, L = case.B, case.H, case.L
+    qkv = case.qkv.double().requires_grad_(True)
+    rh, rw = case.rel_h.double().requires_grad_(True), case.rel_w.double().requires_grad_(True)
+    with _CaptureLogits() as cap:
+        out, lse = attn_reference(qkv, rh, rw, B, L, H, case.Hp, case.Wp, case.scale)
+    logits = cap.logits.detach()
+    assert cap.calls == 1 and logits.dtype == torch.float64 and logits.shape == (B * H, L, L)
+    out.backward(case.dout.double())
+    D = H * case.hd
+    g = qkv.grad
+    nwin = (logits == 0).sum(-1)
+
+    def snap(t):        # autograd's values are the dyadic ones to 1e-80 or so; make them the dyadic ones, so that rounding them to bf16 is one rounding
+        r = (t.detach() * 1024).round() / 1024
+        assert float((r - t.detach()).abs().max()) < 1e-9
+        return r.contiguous()
+    return TieExpect(nwin.reshape(B, H, L), logits[logits != 0].max(), snap(out), lse.detach(), snap(g[:, :D]), snap(g[:, D:2 * D]),
+                     snap(g[:, 2 * D:]), snap(torch.cat([rh.grad, rw.grad], 0)))
+
+
+@functools.lru_cache(maxsize=None)
+def tie_attn_case(kind, B, H, Hp, Wp, hd):
+    """As attn_case: one (kind, shape) and its expectation, built once per process, read-only."""
+    i = TIE_KINDS.index(kind)
+    case = tie_case(B, H, Hp, Wp, hd, TIE_PLACEMENTS[i % 3], i >= 3, 7000 * Hp + 70 * Wp + hd + i)
+    return case, tie_reference(case)
+
+
+def tie_route_params(routes):
+    """-> [(route, kind, B, H, Hp, Wp)]: every route and grid of route_params, on the tie kinds of that grid and head dim."""
+    out = []
+    for route, (_, _, _, _, grids) in routes.items():
+        for grid in grids:
+            for kind in tie_kinds(grid, routes[route][1]):
+                out.append((route, kind) + grid)
+    return out
+
+
+TIE_PREP_LAUNCH_CASES = [(kind, PREP_LAUNCH_GRID) for kind in TIE_KINDS] + [("tie_mirror_sparse", FULL_GRID)]
+
+
+def tie_shapes():
+    """Every distinct (kind, B, H, Hp, Wp, hd) the tie GPU tests build."""
+    seen = []
+    for routes in (ATTN_ROUTES, SHORT_ROUTES):
+        for route, kind, B, H, Hp, Wp in tie_route_params(routes):
             key = (kind, B, H, Hp, Wp, routes[route][1])
             if key not in seen:
                 seen.append(key)

@@ -12,7 +12,7 @@ Where dV is NOT asserted bit for bit (the documented exception; equality holds e
 P = exp2(s * scale * log2e - lse * log2e) from the lse the forward stored in natural-log units:
     attn_fwd.hip:150   lse[(size_t)bh * L + q] = (m + __builtin_amdgcn_logf(lt)) * LN2_F;
     attn_bwd.hip:139   lse2 = lse[(size_t)bh * L + q] * LOG2E_F;
-    attn2.hip:204 / :284 and attn3.hip:202 / :341 are the same two lines; attn3.hip:206-209 stores -lse / scale as bf16 hi + lo.
+    attn2.hip:206 / :286 and attn3.hip:204 / :343 are the same two lines; attn3.hip:208-211 stores -lse / scale as bf16 hi + lo.
 m * LN2_F * LOG2E_F is not m: two fp32 roundings and two rounded constants, at most 2^-22 of m together.  At the winner the exponent is
 therefore not 0 but up to |logit| * log2e * 2^-22, and P = 1 +- |logit| * 2^-22 (dS is unharmed: P times an exact zero).
   * bf16 build, content cases (|logit| <= 800): |P - 1| <= 1.9e-4, far inside the half ulp of bf16 below 1 (2^-9 = 1.95e-3): P rounds to
@@ -28,7 +28,9 @@ therefore not 0 but up to |logit| * log2e * 2^-22, and P = 1 +- |logit| * 2^-22 
     row (an error of 1): tests/test_exact_cases_cpu.py asserts that it is below 1/2 in every element of every case (largest: 0.23 where
     1568 queries meet in one key; 0.04 on bias_rank, where |logit| reaches 4e4 but at most 8 queries share a key).
 
-What these tests cannot see: a one-hot softmax never exercises the dS arithmetic or the normaliser; the tolerance tests keep that job."""
+What these tests cannot see: a one-hot softmax makes dS exactly zero and keeps the normaliser at 1.  tests/test_attention_ties_gpu.py
+takes both from there -- tied winners, P = 1/n, a non-zero dyadic dS, dQ, dK and table gradients held to equality on the same routes;
+unequal probabilities within a row and the rounding of a non-dyadic dS stay with the tolerance tests."""
 import pytest
 import torch
 
@@ -167,7 +169,7 @@ def test_generation_3_backward_with_the_prep_launch_is_the_same_exact_result(kin
     """prep="launch" (pa_attn_bwd_prep writes Delta and the lse fields into the table tiles in front of the backward) against the fused
     default on one grid (and bias_rank on the full grid too): the same assertions on each route, and ALL of out, lse, dqkv (dV included, on every kind) and drcat the same
     between the two -- value for value, which for floats is bit for bit apart from the sign of a zero.  Both routes write -lse / scale as
-    the same bf16 hi + lo pair from the same stored lse (attn3.hip:206-209 and the prep kernel), and Delta is an integer here, so its
+    the same bf16 hi + lo pair from the same stored lse (attn3.hip:208-211 and the prep kernel), and Delta is an integer here, so its
     summation order does not matter.  bias_rank is the sensitive case: with |lse / scale| up to 3.4e5 the lo half of the lse field decides
     the bf16 bits of P, and with them dV (at the full grid some of them are not the bits of 1); on the content cases P rounds to 1 and a
     wrong lo half would hide."""
@@ -182,7 +184,7 @@ def test_generation_3_backward_with_the_prep_launch_is_the_same_exact_result(kin
 @pytest.mark.parametrize("route,kind,B,H,Hp,Wp", SHORT_PARAMS, ids=[_id(p) for p in SHORT_PARAMS])
 def test_attention_is_an_exact_gather_on_the_shortest_generation_2_grids(route, kind, B, H, Hp, Wp, generation):
     """(4, 16) and (4, 24): L = 64 and L = 96, two and three key tiles, half of the workgroup's waves without a query tile; head dim 64 and
-    80.  The shortest grids that reach the generation-2 kernels: attn2_ok (attn2.hip:575) alone would also admit (2, 16), but pa_attn_fwd /
+    80.  The shortest grids that reach the generation-2 kernels: attn2_ok (attn2.hip:576) alone would also admit (2, 16), but pa_attn_fwd /
     pa_attn_bwd return an error for Hp % 4 != 0 before they dispatch.  New to the suite; kept apart and run after the rest."""
     spec = X.SHORT_ROUTES[route]
     generation(spec[2])

@@ -158,3 +158,138 @@ def test_conv_case_references_equal_torch_conv_and_stay_exact(kind, B, Hi, Wi):
     if Wi > 64:
         assert near(63, 64, 2) and near(64, 63, 2)
     assert hx[0, Hi - 1, Wi - 1] == 1 and hy[1, 0, 0] + hy[1, 0, 1] + hy[1, 1, 0] + hy[1, 1, 1] >= 1
+
+
+# ------------------------------------------------------------------------------------------------ tied winners
+TIE_SHAPES = X.tie_shapes()
+OLD_GATE_BF16 = 1.6e-2                                  # test_attn_bwd's: max|a - b| / max|b| over the whole tensor
+
+
+def bf16_exact(t):
+    return torch.equal(t.float().to(torch.bfloat16).double(), t.double())
+
+
+def bf16_hi_lo_exact(t):
+    hi = t.float().to(torch.bfloat16).float()
+    lo = (t.float() - hi).to(torch.bfloat16).float()
+    return torch.equal((hi.double() + lo.double()), t.double())
+
+
+def test_the_tie_parametrisation_covers_what_it_says():
+    """Every route and grid of the gather tests runs the three placements; with a dense and a sparse dO on the head-dim-64 grids below the
+    full one, with the sparse one elsewhere; the full grid once per placement; the prep-launch route all six kinds and the full grid."""
+    assert X.TIE_KINDS == ("tie_near", "tie_quarter", "tie_mirror", "tie_near_sparse", "tie_quarter_sparse", "tie_mirror_sparse")
+    for routes in (X.ATTN_ROUTES, X.SHORT_ROUTES):
+        params = X.tie_route_params(routes)
+        assert {p[0] for p in params} == set(routes)
+        for route, spec in routes.items():
+            for grid in spec[4]:
+                kinds = [p[1] for p in params if p[0] == route and p[2:] == grid]
+                assert {k.replace("tie_", "").replace("_sparse", "") for k in kinds} == set(X.TIE_PLACEMENTS), (route, grid)
+                assert len(kinds) == (6 if spec[1] == 64 and grid != X.FULL_GRID else 3) and len(set(kinds)) == len(kinds)
+    assert [g for _, g in X.TIE_PREP_LAUNCH_CASES] == [X.PREP_LAUNCH_GRID] * 6 + [X.FULL_GRID]
+    assert len(TIE_SHAPES) == len(set(TIE_SHAPES))
+
+
+@pytest.mark.parametrize("kind,B,H,Hp,Wp,hd", TIE_SHAPES, ids=["%s-%dx%dx%dx%d-hd%d" % s for s in TIE_SHAPES])
+def test_tie_case_conditions_and_sensitivity(kind, B, H, Hp, Wp, hd):
+    """What tests/test_attention_ties_gpu.py rests on, for every case it builds.
+
+    Sensitivity: five wrong backward kernels (exact_cases.tie_algebra) each move at least one tensor by many quanta (148 at the least),
+    far outside the fp32 build's bound (46,000 times it at the least, taken at the element the fault moves most and only where the
+    bound is not 0; for the faults that touch the tables, on the tables).  NONE of them stays inside the gate of the tolerance tests (max|a - b| / max|b| < 1.6e-2) on these cases: the smallest
+    measure over all cases is 0.11 (last_key_row), and on Gaussian operands of test_attn_bwd's kind they are gross
+    as well (0.35 and more) -- each of the five is wrong in every row.  The faults the tolerance tests cannot see are the local ones (one
+    row, one slot, one column of one workgroup); here those are visible for another reason, asserted below: every value is exact, so
+    any single wrong contribution is at least one quantum."""
+    case, exp = X.tie_attn_case(kind, B, H, Hp, Wp, hd)
+    alg = X.tie_algebra(case)
+    L, D, nh = Hp * Wp, H * hd, 2 * Hp - 1
+    active, s1, s2, shift, offset = X.tie_layout(hd)
+    assert len(set(active + s1 + s2 + shift + [offset])) == hd
+    # winners: 1, 2 or 4 per row at logit exactly 0, all three counts, the pattern the builder meant (the last rows of the grid are tie rows);
+    # everyone else >= 150 below
+    assert torch.equal(exp.nwin, X.tie_winner_count(L)[None, None].expand(B, H, L)) and set(exp.nwin.unique().tolist()) == {1, 2, 4}
+    assert int(exp.nwin[0, 0, L - 1]) == 4 and int(exp.nwin[0, 0, L - 3]) == 2 and float(exp.loser) <= -X.MIN_MARGIN
+    for tile in range(L // 32):
+        assert set(exp.nwin[0, 0, 32 * tile:32 * tile + 32].tolist()) == {1, 2, 4}
+    logits = alg["logits"]
+    assert float(logits.max()) == 0 and torch.equal((logits == 0).sum(-1).reshape(B, H, L), exp.nwin)
+    members = X.tie_members(kind.split("_")[1], L)
+    assert torch.equal(members.flatten().sort().values, torch.arange(L))
+    win = (logits.reshape(B, H, L, L) == 0)
+    for n, want in ((4, (4,)), (2, (2,))):                # the winners of a row are members of ONE group: all four, or a member and its partner m ^ 2
+        rows = win[0, 0][exp.nwin[0, 0] == n]
+        in_group = rows[:, members].sum(-1)                # [rows, L/4]
+        assert bool((in_group.max(-1).values == n).all())
+        if n == 2:
+            pair = rows[:, members][in_group == 2]         # [rows, 4]
+            assert bool((pair[:, 0] == pair[:, 2]).all() and (pair[:, 1] == pair[:, 3]).all())
+    t = win.float().argmax(-1)
+    assert not torch.equal(t[0, 0], t[-1, -1]) or B * H == 1                      # another target permutation per (sample, head)
+    # operands are bf16-exact; so are scale * q and the per-query bias tables, which are zero (q is zero where the tables are not)
+    for name in ("qkv", "rel_h", "rel_w", "dout"):
+        assert bf16_exact_integers(getattr(case, name)), name
+    q = case.qkv.reshape(B, L, 3, H, hd)[:, :, 0]
+    assert bf16_exact(q * case.scale) and case.scale == 0.125
+    assert float(alg["Gh"].abs().max()) == 0 and float(alg["Gw"].abs().max()) == 0
+    assert float(case.rel_h.abs().sum()) == float(case.rel_h[:, offset].sum()) == nh * (nh + 1) / 2
+    assert float(case.rel_w.abs().sum()) == float(case.rel_w[:, offset].sum()) == Wp * (2 * Wp - 1)
+    assert set(case.dout.unique().tolist()) == {-1.0, 0.0, 1.0}
+    density = float((case.dout != 0).float().mean())
+    assert abs(density - (1 / 16 if kind.endswith("sparse") else 2 / 3)) < 0.02
+    # every fp32 accumulation is exact: sum of |terms| in units of 1/64 (the finest any term has) below 2^24
+    sums = X.tie_exact_sums(case, alg)
+    assert max(sums.values()) < 2 ** 24, sums
+    assert bool((alg["dS"] * 16 == (alg["dS"] * 16).round()).all()) and bool((alg["P"] * 4 == (alg["P"] * 4).round()).all())
+    # what the bf16 kernels pack into 16 bits: out, P, dS and the per-query bias gradient survive bf16; Delta and -lse / scale a hi + lo pair
+    for name in ("out", "P", "dS", "dG_h", "dG_w"):
+        assert bf16_exact(alg[name]), (name, int((alg[name].float().to(torch.bfloat16).double() != alg[name]).sum()))
+    assert bf16_hi_lo_exact(alg["delta"])
+    x = -exp.lse.float() / case.scale                     # the fp32 value the forward splits (lse itself is log 1, log 2 or log 4 rounded to fp32)
+    hi = x.to(torch.bfloat16).float()
+    back = (hi + (x - hi).to(torch.bfloat16).float()).double() * case.scale
+    assert float((torch.exp(-exp.lse.float().double() - back) - 1).abs().max()) < 2.0 ** -11
+    assert torch.equal(exp.lse, torch.log(exp.nwin.double()).reshape(B * H, L))
+    # expectations: autograd == the hand algebra, dyadic (times 32 an integer), non-zero where the issue says
+    for name, a, b in (("out", exp.out, alg["out"]), ("dq", exp.dq, alg["dq"]), ("dk", exp.dk, alg["dk"]), ("dv", exp.dv, alg["dv"]),
+                       ("drh", exp.drcat[:nh], alg["drh"]), ("drw", exp.drcat[nh:], alg["drw"])):
+        assert float((a - b).abs().max()) < 1e-9 and float((a * 32 - (a * 32).round()).abs().max()) < 1e-9, name
+        assert float(a.abs().max()) < 2 ** 15
+    # (dQ of a tie row is zero on the channels its winners share: sum_k dS = 0.  The flip sets and the offset channel carry it.)
+    off_dq = exp.dq.reshape(B * L, H, hd)[:, :, offset]
+    assert bf16_exact(exp.out) and float((exp.dq != 0).double().mean()) > 0.02 and float((off_dq != 0).double().mean()) > 0.3
+    assert float((exp.dk != 0).double().mean()) > 0.4
+    assert float((exp.drcat[:nh].abs().sum(1) != 0).double().mean()) > 0.5
+    if "quarter" not in kind:                             # a quarter of the grid apart is a whole number of key rows: the same key column, no rel_pos_w gradient
+        assert float((exp.drcat[nh:].abs().sum(1) != 0).double().mean()) > 0.5
+    # the fp32 build's bound: below half a quantum in every element of dq, dk, dv and both table gradients (largest: 0.05 of a quantum for
+    # dq, 0.32 for a table row), so no value one quantum off can hide inside it
+    bound = X.tie_fp32_bounds(case, alg)
+    quanta = {n: X.tie_quantum(getattr(exp, n)) for n in ("dq", "dk", "dv", "drcat")}
+    ratio = {n: float(bound[n].max()) / quanta[n] for n in bound}
+    print("%s %dx%dx%dx%d hd%d: quanta %s; fp32 bound / quantum %s" % (kind, B, H, Hp, Wp, hd, quanta, {n: "%.3f" % r for n, r in ratio.items()}))
+    assert min(quanta.values()) >= 1 / 32
+    assert max(ratio.values()) < 0.5, ratio
+    # sensitivity
+    want = dict(dq=alg["dq"], dk=alg["dk"], dv=alg["dv"], drcat=torch.cat([alg["drh"], alg["drw"]], 0))
+    line = []
+    for fault in X.TIE_FAULTS:
+        w = X.tie_algebra(case, fault)
+        got = dict(dq=w["dq"], dk=w["dk"], dv=w["dv"], drcat=torch.cat([w["drh"], w["drw"]], 0))
+        diff = {n: (got[n] - want[n]).abs() for n in want}
+        seen = {n: float(diff[n].max()) / quanta[n] for n in want}
+        # ... against the bound only where there is one: where it is 0 every term is 0 and the fp32 build has to return 0 itself
+        # ... and at the element the fault moves most, not at one whose bound happens to be tiny
+        at = {n: int((diff[n] * (bound[n] > 0)).argmax()) for n in want}
+        beyond = {n: float(diff[n].flatten()[at[n]] / bound[n].flatten()[at[n]].clamp_min(1e-300)) for n in want}
+        measure = max(float(diff[n].max() / want[n].abs().max().clamp_min(1e-30)) for n in ("dq", "dk", "dv"))
+        measure = max(measure, float(diff["drcat"][:nh].max() / want["drcat"][:nh].abs().max().clamp_min(1e-30)),
+                      float(diff["drcat"][nh:].max() / want["drcat"][nh:].abs().max().clamp_min(1e-30)) if float(want["drcat"][nh:].abs().max()) else 0.0)
+        tables_only = fault in ("last_key_row", "dg_column_dropped")           # these two change nothing but d rel_pos_h
+        far = beyond["drcat"] if tables_only or fault == "kh_class_phase" else max(beyond.values())
+        line.append("%s: %.0f quanta, %.0f x the fp32 bound, old measure %.2g" % (fault, max(seen.values()), far, measure))
+        assert max(seen.values()) >= 1, (fault, seen)
+        assert far >= 16, (fault, beyond)
+        assert not tables_only or max(seen[n] for n in ("dq", "dk", "dv")) == 0
+    print("  " + "; ".join(line))
