@@ -33,11 +33,13 @@ FLAGS = FLAGS + os.environ.get("PA_EXTRA_FLAGS", "").split()
 # IoU thresholds that COCOeval makes in float64 (tests/painter_ap_host.py).  painter_kpt.hip: the photo coordinates equal
 # painter_engine.to_image bit for bit, and the float32 / float64 steps that feed exp in the two OKS forms are stated operation by operation
 # (tests/painter_kpt_host.py).  painter_paint.hip: the float64 divisions and the product with 79 decide the cell, and with it the colour, of
-# an instance target exactly as the reference's Python floats do (tests/painter_paint_host.py).
+# an instance target exactly as the reference's Python floats do (tests/painter_paint_host.py).  painter_minmax.hip: one float64 division, its
+# rounding to float32, one float32 division and one float32 subtraction are an instance's score, bit for bit (tests/painter_minmax_host.py).
 EXTRA = {"seggpt_io.hip": ["-ffp-contract=off"], "pair_io.hip": ["-ffp-contract=off"], "painter_io.hip": ["-ffp-contract=off"],
          "painter_inst.hip": ["-ffp-contract=off"], "painter_pano.hip": ["-ffp-contract=off"], "painter_pose.hip": ["-ffp-contract=off"],
          "painter_score.hip": ["-ffp-contract=off"], "painter_restore.hip": ["-ffp-contract=off"], "painter_pq.hip": ["-ffp-contract=off"],
-         "painter_ap.hip": ["-ffp-contract=off"], "painter_kpt.hip": ["-ffp-contract=off"], "painter_paint.hip": ["-ffp-contract=off"]}
+         "painter_ap.hip": ["-ffp-contract=off"], "painter_kpt.hip": ["-ffp-contract=off"], "painter_paint.hip": ["-ffp-contract=off"],
+         "painter_minmax.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():
@@ -65,6 +67,7 @@ def headers():
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_hip.h"))
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_rle.h"))
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_paint.h"))
+    hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_minmax.h"))
     return sorted(hs)
 
 

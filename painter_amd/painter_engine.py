@@ -17,6 +17,9 @@ the digests the unmodified scripts produced); the float64 output of the three re
 `instances` / `PainterEngine.run_instances` decode a painted `coco_pano_inst` picture into class-agnostic instances on the device
 (csrc/painter_inst.hip): the evaluator's threshold route and its Matrix NMS (COCOCAInstSegEvaluatorCustom.py:252-354,
 util/matrix_nms.py) on exact integers and bit masks, ties defined (tests/painter_inst_host.py is the definition).
+`instances_minmax` / `run_instances(..., post_type="minmax")` are the evaluator's other route (:172-250, csrc/painter_minmax.hip,
+include/painter_minmax.h): every pixel goes to the nearest of the 6401 colours, every colour that wins a pixel is an instance, its score
+comes from the mean distance of its pixels -- no NMS, no top-k (tests/painter_minmax_host.py is the definition).
 
 `classify_instances`, `panoptic` and `run_panoptic` finish what COCO panoptic evaluation needs (csrc/painter_pano.hip): every instance
 gets the thing class its pixels vote for in the painted `coco_pano_semseg` picture, and instances and semantic picture are combined into
@@ -472,6 +475,95 @@ def instances(picture, palette=None, dist_thr=19.0, nms_pre=2000, max_num=100, k
     -> dict(scores float32 [n], labels float32 [n], masks bool [n][H][W], candidates int32 [n] = t * K + c of each instance).
     Ties are defined (include/painter_hip.h): exact integer statistics, rational maskness order, stable sorts, float64 NMS."""
     return InstanceDecode(_pictures(picture, _device([picture], device)), palette, dist_thr, nms_pre, max_num, kernel, sigma).result()
+
+
+# ---- instance decode by nearest colour, the evaluator's post_type "minmax" (csrc/painter_minmax.hip, include/painter_minmax.h)
+POST_TYPES = ("threshold", "minmax")                 # COCOEvaluatorCustom.process (:135-141)
+MINMAX_DEFAULTS = dict(palette=None)
+MINMAX_RECORD = np.dtype([("colour", np.int32), ("cls", np.int32), ("n", np.uint32), ("reserved", np.uint32), ("S", np.uint64),
+                          ("neg", np.float32), ("score", np.float32)])                           # pa_minmax_record
+
+
+class MinmaxDecode:
+    """One launched pa_minmax_decode: label and distance map, statistics, instance records and the colour -> slot table, all in ONE device
+    buffer.  The masks are not part of it: their number is the instance count, so `bits()` reads the count back (once) and sizes them by
+    it -- any number of instances up to K + 1 comes out, nothing is cut."""
+
+    def __init__(self, picture, palette=None):
+        dev = picture.device
+        self.img = img = _pictures(picture, dev)
+        pal = np.concatenate([_rgb_palette(palette, location_palette), np.zeros((1, 3), np.float32)])      # black appended (:114-115)
+        self.h, self.w, self.k = int(img.shape[0]), int(img.shape[1]), int(pal.shape[0])
+        self.words = (self.h * self.w + 31) // 32
+        self.shape = (self.h, self.w, self.k)
+        self.workspace = _workspace(lib.pa_minmax_workspace_bytes, self.shape, "pa_minmax_decode (sizes %s)" % (self.shape,), dev)
+        self.params = torch.from_numpy(pal).to(dev, non_blocking=True)
+        hw = self.h * self.w
+        self.at, size = _layout([("count", np.int32, 1, 4), ("records", MINMAX_RECORD, self.k, 8), ("slot", np.int32, self.k, 4),
+                                 ("label", np.uint16, hw, 2), ("dist", np.uint16, hw, 2)])
+        self.out = torch.zeros(size, dtype=torch.uint8, device=dev)
+        self._n, self._bits, self._bytes = None, None, None
+        check(lib.pa_minmax_decode(img.data_ptr(), self.params.data_ptr(), self.h, self.w, self.k, self.workspace.data_ptr(), self.ptr("label"),
+                                   self.ptr("dist"), self.ptr("count"), self.ptr("records"), self.ptr("slot"), _stream()), "pa_minmax_decode")
+
+    def ptr(self, name):
+        return self.out.data_ptr() + self.at[name][0]
+
+    def count(self):
+        """The number of instances: four bytes back and the one synchronisation, once."""
+        if self._n is None:
+            o = self.at["count"][0]
+            self._n = int(self.out[o:o + 4].cpu().numpy().view(np.int32)[0])
+        return self._n
+
+    def bits(self, with_bytes=False):
+        """-> (bit masks int32 CUDA [n][ceil(H W / 32)] in pa_inst_decode's layout, n): what `masks=` arguments and the RLE encode take.
+        with_bytes: -> (bits, bool CUDA [n][H][W], n)."""
+        n = self.count()
+        if self._bits is None or (with_bytes and self._bytes is None):
+            dev = self.out.device
+            bits = torch.empty((n, self.words), dtype=torch.int32, device=dev)
+            dense = torch.empty((n, self.h, self.w), dtype=torch.bool, device=dev) if with_bytes else None
+            check(lib.pa_minmax_masks(self.ptr("label"), self.ptr("slot"), self.h, self.w, self.k, 0, n, bits.data_ptr(),
+                                      None if dense is None else dense.data_ptr(), _stream()), "pa_minmax_masks")
+            self._bits, self._bytes = bits, dense if dense is not None else self._bytes
+        return (self._bits, self._bytes, n) if with_bytes else (self._bits, n)
+
+    def result(self, with_bits=False):
+        """The copy back of the buffer, then the masks' launch and copy back."""
+        a = self.out.cpu().numpy()
+        self._n = n = int(_section(a, self.at, "count")[0])
+        rec = _section(a, self.at, "records", n)
+        bits, dense, _ = self.bits(with_bytes=True)
+        res = dict(scores=rec["score"].copy(), labels=rec["cls"].astype(np.float32), candidates=rec["colour"].copy(),
+                   areas=rec["n"].astype(np.int32), pred_map=_section(a, self.at, "label").astype(np.int32).reshape(self.h, self.w),
+                   dist_map=_section(a, self.at, "dist").astype(np.float32).reshape(self.h, self.w), masks=dense.cpu().numpy())
+        if with_bits:
+            res["bits"] = bits.cpu().numpy().view(np.uint32)
+        return res
+
+
+def instances_minmax(picture, palette=None, device="cuda"):
+    """COCOCAInstSegEvaluatorCustom.post_process_segm_output_by_minmax (:172-250), the evaluator's `post_type="minmax"`: uint8 [H][W][3]
+    picture (numpy or CUDA tensor), palette [K][3] without the background row (default `location_palette()`; black is appended as the
+    evaluator's constructor does) -> dict(scores float32 [n], labels float32 [n] (0 for the background instance, otherwise 1), candidates
+    int32 [n] (the palette row), areas int32 [n], pred_map int32 [H][W], dist_map float32 [H][W], masks bool [n][H][W]), the instances in
+    ascending palette row.  Every pixel goes to its nearest colour in L1, the lowest row on a tie; there is no NMS and no top-k
+    (tests/painter_minmax_host.py is the definition)."""
+    return MinmaxDecode(_pictures(picture, _device([picture], device)), palette).result()
+
+
+def _post_type(who, kw, semseg_engine=None):
+    """Pops `post_type` (default "threshold") from the keywords of a run_* entry point, before their own check.  "minmax" takes `palette`
+    only of the instance keywords and has no class vote behind it; anything else raises as the evaluator does (:141)."""
+    post_type = kw.pop("post_type", "threshold")
+    if post_type not in POST_TYPES:
+        raise NotImplementedError("post_type %r (one of %s)" % (post_type, ", ".join(POST_TYPES)))
+    if post_type == "minmax":
+        if semseg_engine is not None:
+            raise ValueError("%s: post_type=\"minmax\" is not offered together with semseg_engine" % who)
+        _check_arguments(who + " (post_type=\"minmax\")", kw, MINMAX_DEFAULTS)
+    return post_type
 
 
 # ---- pose keypoints (csrc/painter_pose.hip)
@@ -1916,15 +2008,26 @@ class InstanceResults:
     of a PanopticDecode and the RLE buffer -- never `masks`."""
 
     def __init__(self, decode, image_id):
+        if isinstance(decode, MinmaxDecode):             # bits sized by the count (read back once); the encode reads both where they lie
+            self.decode, self.inst, self.image_id = decode, decode, image_id
+            bits, n = decode.bits()
+            self.encode = RleEncode(bits, decode.ptr("count"), decode.h, decode.w, n, device=decode.out.device, keep=decode.out)
+            return
         inst = decode if isinstance(decode, InstanceDecode) else getattr(decode, "decode", None)
         if inst is None:
-            raise TypeError("instance_results: neither an InstanceDecode nor a PanopticDecode chained behind one")
+            raise TypeError("instance_results: neither an InstanceDecode, a MinmaxDecode nor a PanopticDecode chained behind one")
         self.decode, self.inst, self.image_id = decode, inst, image_id
         base = inst.out.data_ptr()
         self.encode = RleEncode(base + inst.obits, base + inst.at["count"][0], inst.h, inst.w, inst.max_num, device=inst.out.device, keep=inst.out)
 
     def result(self):
         inst = self.inst
+        if isinstance(inst, MinmaxDecode):
+            o, n = inst.at["records"][0], inst.count()
+            rec = inst.out[o:o + MINMAX_RECORD.itemsize * n].cpu().numpy().view(MINMAX_RECORD)
+            strings = self.encode.result()["strings"]
+            return [dict(image_id=self.image_id, category_id=int(c), bbox=[0.0, 0.0, 0.0, 0.0], score=float(s),
+                         segmentation={"size": [inst.h, inst.w], "counts": t}) for c, s, t in zip(rec["cls"], rec["score"], strings)]
         a = inst.out[:inst.obits].cpu().numpy()
         n = int(_section(a, inst.at, "count")[0])
         if n == 0:            # :302-310: one all-zero mask, score 0, label 0.  Slot 0 of the decode's bits is zero then: encode it as one mask
@@ -1949,19 +2052,24 @@ def instance_results(decode, image_id):
     PanopticDecode chained behind one: image_id; category_id = the voted class behind a PanopticDecode, otherwise the label 1, and 0 for
     the empty-prediction mask; bbox = [0.0] * 4, for the evaluators set zero boxes (:246, :350); score = the Python float of the float32;
     segmentation = {"size": [h, w], "counts": str}, pycocotools.mask.encode's RLE computed on the device (`RleEncode`).  A decode without
-    candidates gives the reference's single entry (:302-310): score 0, category 0, the all-zero mask (counts of [h w])."""
+    candidates gives the reference's single entry (:302-310): score 0, category 0, the all-zero mask (counts of [h w]).  A MinmaxDecode
+    gives one entry per instance in ascending palette row, category_id = its class (0 for the background instance, :220-223)."""
     return InstanceResults(decode, image_id).result()
 
 
 def run_instance_results(inst_engine, pictures, image_ids, sizes=None, semseg_engine=None, **kw):
     """`run_instance_ap`'s loop ending in `instance_results`: forwards, decodes and RLE encodes of a batch are all enqueued before the
     first copy back, and no mask is copied back.  With `semseg_engine` (task coco_pano_semseg) every instance carries the class the
-    panoptic decode's vote gives it.  -> the flat list the evaluator `json.dumps` into coco_instances_results.json."""
+    panoptic decode's vote gives it.  -> the flat list the evaluator `json.dumps` into coco_instances_results.json.  post_type="minmax":
+    the decodes are `MinmaxDecode`s (keyword `palette` only, no semseg_engine); their masks and encodes follow once the counts are back."""
     if inst_engine.task != "coco_pano_inst" or (semseg_engine is not None and semseg_engine.task != "coco_pano_semseg"):
         raise ValueError("painter_engine: run_instance_results takes a coco_pano_inst engine and, optionally, a coco_pano_semseg engine, not %r and %r"
                          % (inst_engine.task, None if semseg_engine is None else semseg_engine.task))
     kw = {k: v for k, v in kw.items() if k != "device"}
-    if semseg_engine is None:
+    minmax = _post_type("run_instance_results", kw, semseg_engine) == "minmax"
+    if minmax:
+        args = dict(MINMAX_DEFAULTS, **kw)
+    elif semseg_engine is None:
         _check_arguments("run_instance_results", kw, INSTANCE_DEFAULTS)         # before the first forward is enqueued
         args = dict(INSTANCE_DEFAULTS, **kw)
     else:
@@ -1980,9 +2088,11 @@ def run_instance_results(inst_engine, pictures, image_ids, sizes=None, semseg_en
         for j in range(0, len(pics), step):
             inst = inst_engine._launch_batch(pics[j:j + step], sizes[j:j + step], False)
             for i in range(inst.n_jobs):
-                dec = InstanceDecode(inst.picture(i), *args.values()) if sem is None else \
+                dec = MinmaxDecode(inst.picture(i), *args.values()) if minmax else InstanceDecode(inst.picture(i), *args.values()) if sem is None else \
                     _launch_panoptic(sem.picture(j + i), inst.picture(i), None, palette, n_things, merge, kw)
-                jobs.append(InstanceResults(dec, items[j + i][1]))
+                jobs.append((dec, items[j + i][1]) if minmax else InstanceResults(dec, items[j + i][1]))
+        if minmax:               # every decode of the batch is enqueued; the masks and the encodes are sized by the counts read back now
+            jobs = [InstanceResults(dec, image_id) for dec, image_id in jobs]
         return [e for job in jobs for e in job.result()]
 
     first = inst_engine if semseg_engine is None else semseg_engine
@@ -2609,16 +2719,20 @@ class PainterEngine:
     def run_instances(self, pictures, sizes=None, **kw):
         """coco_pano_inst: forward and decode as `run`, then `instances(picture, **kw)` of every decoded picture straight from the
         decode plan's device-resident uint8 output -- no PNG, no host copy of the picture; the decodes of a batch are all enqueued behind
-        its forward before the first copy back.  -> one dict per picture, as `instances` returns it."""
+        its forward before the first copy back.  -> one dict per picture, as `instances` returns it.  post_type="minmax": the evaluator's
+        other route, `instances_minmax(picture, palette=...)`; it takes `palette` only."""
         if self.task != "coco_pano_inst":
             raise ValueError("painter_engine: run_instances decodes the pictures of coco_pano_inst, not of %r" % self.task)
         kw.pop("device", None)
-        _check_arguments("run_instances", kw, INSTANCE_DEFAULTS)          # before the first forward is enqueued
-        args = dict(INSTANCE_DEFAULTS, **kw)
+        minmax = _post_type("run_instances", kw) == "minmax"
+        if not minmax:
+            _check_arguments("run_instances", kw, INSTANCE_DEFAULTS)      # before the first forward is enqueued
+        args = dict(MINMAX_DEFAULTS if minmax else INSTANCE_DEFAULTS, **kw)
+        decode = MinmaxDecode if minmax else InstanceDecode
 
         def batch(pics, sizes):
             plan = self._launch_batch(pics, sizes, False)
-            jobs = [InstanceDecode(plan.picture(i), *args.values()) for i in range(plan.n_jobs)]
+            jobs = [decode(plan.picture(i), *args.values()) for i in range(plan.n_jobs)]
             return [j.result() for j in jobs]
         return [o for b in self._run(pictures, sizes, batch) for o in b]
 
