@@ -68,6 +68,7 @@ def headers():
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_rle.h"))
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_paint.h"))
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_minmax.h"))
+    hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_anysize.h"))
     return sorted(hs)
 
 

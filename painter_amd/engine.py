@@ -17,7 +17,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import hostmath, ops
+from . import hostmath, ops, ops_anysize
 from ._lib import EPI_BIAS, EPI_BIAS_F32, EPI_BIAS_RESID, KNOB_RELPOS_SPLITS, KNOB_WGRAD_TARGET
 
 
@@ -87,6 +87,20 @@ class HotPathConfig:
             err.append("depth %d puts a feature tap at or before the stream merge (block %d)" % (self.depth, self.merge_idx))
         if err:
             raise NotImplementedError("painter_amd HIP path: " + "; ".join(err))
+
+
+class _Grid:
+    """The configuration at a run-time input size other than the constructed one (HotPath.grid): every field of the HotPathConfig it was
+    derived from, with H, W, Hp, Wp, L of the run; forward only."""
+
+    def __init__(self, cfg, H, W):
+        self.__dict__.update(cfg.__dict__)
+        self.H, self.W = int(H), int(W)
+        self.Hp, self.Wp = self.H // cfg.P, self.W // cfg.P
+        self.L = self.Hp * self.Wp
+        self.attn_any = not ops_anysize.attn_fwd_takes(self.L, self.Hp, self.Wp)     # a grid such as 16 x 8 changes only the tables
+        self.M = None              # per device: the rows of abs_pos_operator(src, Hp, Wp)
+        self.rel = {}              # the resized, packed rel-pos tables (HotPath.relpos_grid)
 
 
 class _Saved:
@@ -217,6 +231,7 @@ class HotPath:
         self._wcache = {}
         self._pcache = {}
         self._rcache = {}
+        self._grids = {}               # (H, W) -> _Grid: per-grid state of forwards at other sizes than the constructed one
         self._side = {}
         self._lnws = {}                # per device: ring of workspaces for the deferred LayerNorm-backward reductions (ln_workspace)
         # parameter-gradient kernels (dW = dY^T.X, bias column sums) are off the backward's critical path: they go to a second HIP
@@ -258,6 +273,69 @@ class HotPath:
                 e.record(side)
                 ring["events"][k] = e
         return buf, done
+
+    # ------------------------------------------------------------------ run-time input sizes
+    def grid(self, H, W):
+        """-> the configuration a forward at H x W runs with: self.cfg itself at the constructed size (today's route, nothing derived),
+        otherwise a _Grid, cached per size -- token grid, position-operator rows and the resized, packed rel-pos tables; a few sizes used
+        alternately each keep their own.  What remains required of another size: H == 2W and both whole numbers of patches
+        (NotImplementedError before anything is launched).  The constructed size's "width a multiple of 4" follows from that where a
+        forward kernel needs it -- the patch embedding reads 8-pixel groups of a patch row only when P % 8 == 0, pixel by pixel otherwise
+        (patch 14 at 140 x 70) -- and the loss, the decoder tail and patchify address single pixels.  Forward only: the backward kernels
+        are built for the constructed grid."""
+        c = self.cfg
+        H, W = int(H), int(W)
+        if (H, W) == (c.H, c.W):
+            return c
+        g = self._grids.get((H, W))
+        if g is None:
+            err = []
+            if H != 2 * W: err.append("the stitched pair must be (2W, W)")
+            if H < c.P or W < c.P or H % c.P or W % c.P: err.append("both sides must be whole numbers of %d-pixel patches" % c.P)
+            if err:
+                raise NotImplementedError("painter_amd HIP path: input size %d x %d (constructed at %d x %d): %s" % (H, W, c.H, c.W, "; ".join(err)))
+            g = self._grids[(H, W)] = _Grid(c, H, W)
+        return g
+
+    def grid_pos_operator(self, g, device):
+        """The sparse rows of abs_pos_operator(src, Hp, Wp) for a run-time grid (forward half only), cached on the grid."""
+        if g.M is None or g.M[0].device != device:
+            idx, val, _ = hostmath.sparse_rows(hostmath.abs_pos_operator(g.src, g.Hp, g.Wp))
+            g.M = (torch.from_numpy(idx).to(device), torch.from_numpy(val).to(device))
+        return g.M
+
+    def relpos_grid(self, g, pre, P):
+        """Rcat of block `pre` for the run-time grid g: every block's tables are resized to 2Hp - 1 / 2Wp - 1 rows by ONE launch
+        (pa_relpos_resize: the reference's get_rel_pos, F.interpolate(mode="linear")) into a buffer that pa_relpos_pack_batch then packs
+        for the grid -- two launches per (grid, table version), none afterwards.  Cached like relpos(), on the grid: keyed on the tables'
+        addresses and versions, so two sizes used alternately each keep their tables."""
+        c = self.cfg
+        i = int(pre.split(".")[1])
+        rh, rw = P[pre + "attn.rel_pos_h"], P[pre + "attn.rel_pos_w"]
+        st = g.rel
+        if st and st["dev"] == rh.device and st["T"] == self.T and st["ptr"][i] == (rh.data_ptr(), rw.data_ptr()) and \
+                st["ver"][i] == (rh._version, rw._version):
+            return st["rcat"][i]
+        hs = [P["blocks.%d.attn.rel_pos_h" % k] for k in range(c.depth)]
+        ws = [P["blocks.%d.attn.rel_pos_w" % k] for k in range(c.depth)]
+        hd, sh, sw = rh.shape[1], rh.shape[0], rw.shape[0]
+        for t, n in [(t, sh) for t in hs] + [(t, sw) for t in ws]:
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == rh.device and t.shape == (n, hd)
+        ptr = [(h.data_ptr(), w.data_ptr()) for h, w in zip(hs, ws)]
+        same = bool(st) and st["dev"] == rh.device and st["T"] == self.T and st["ptr"] == ptr
+        tabs = st["tabs"] if same else torch.tensor([q[0] for q in ptr] + [q[1] for q in ptr], dtype=torch.int64).to(rh.device)
+        dh, dw = 2 * g.Hp - 1, 2 * g.Wp - 1
+        resized = ops_anysize.relpos_resize(tabs, c.depth, sh, sw, dh, dw, hd, out=st["resized"] if same else None)
+        if resized is None:                       # both lengths stay: the stored tables are the operands
+            addr = tabs
+        else:
+            addr = st["addr"] if same else ops_anysize.table_addresses(resized, dh)
+        rcat, rcatT = ops.relpos_pack_batch(addr, c.depth, g.Hp, g.Wp, hd, self.T, rcat=st["rcat"] if same else None,
+                                            rcatT=st["rcatT"] if same else None)
+        st.clear()
+        st.update(dev=rh.device, T=self.T, ptr=ptr, ver=[(h._version, w._version) for h, w in zip(hs, ws)], tabs=tabs, resized=resized,
+                  addr=addr, rcat=rcat, rcatT=rcatT)
+        return rcat[i]
 
     # ------------------------------------------------------------------ constants / casts
     def pos_operator(self, device):
@@ -338,6 +416,8 @@ class HotPath:
         self._wcache.clear()
         self._pcache.clear()
         self._rcache.clear()
+        for g in self._grids.values():
+            g.rel.clear()
 
     def shadow_buffers(self):
         """{parameter data_ptr: cached bf16 copy} -- lets painter_amd.optim.AdamW refresh the copies inside its update pass."""
@@ -356,10 +436,17 @@ class HotPath:
         """need_grad: save what a backward needs (any input, parameter or the prediction may need a gradient).  want: the parameter names
         whose gradients the backward will be asked for (None = all): tensors that only serve frozen parameters' gradients are not kept --
         the im2col operand (patch weight), the tap concat (decoder_embed.weight), decoder_embed's output (decoder_pred.0.weight)."""
-        c, T = self.cfg, self.T
+        T = self.T
+        c = self.grid(imgs.shape[2], imgs.shape[3])        # self.cfg at the constructed size; the per-grid state of another size otherwise
+        other = c is not self.cfg
+        if other and need_grad:
+            raise NotImplementedError("painter_amd HIP path: input size %d x %d differs from the constructed %d x %d, which is forward only "
+                                      "(the backward kernels are built for the constructed grid): call under torch.no_grad()"
+                                      % (c.H, c.W, self.cfg.H, self.cfg.W))
         dev = imgs.device
         B = imgs.shape[0]
         L, D = c.L, c.D
+        assert tuple(imgs.shape) == (B, 3, c.H, c.W) and tgts.shape == imgs.shape and mask_u8.shape[-1] == L, (imgs.shape, tgts.shape, mask_u8.shape)
         S = _Saved()
         S.B, S.need_grad = B, need_grad
         keep = lambda n: need_grad and (want is None or n in want)
@@ -367,7 +454,7 @@ class HotPath:
         S.drop = drop_scales
         S.seg_type = seg_type if c.seggpt else None
         pe = P["pos_embed"][0, c.cls:]
-        pos = ops.pos_fwd(self.pos_operator(dev)[0], pe, L, D)
+        pos = ops.pos_fwd(self.grid_pos_operator(c, dev) if other else self.pos_operator(dev)[0], pe, L, D)
         tok_args = (P["patch_embed.proj.bias"], P["mask_token"], P["segment_token_x"], P["segment_token_y"], pos, mask_u8,
                     P.get("type_token_cls") if c.seggpt else None, P.get("type_token_ins") if c.seggpt else None,
                     seg_type if c.seggpt else None)
@@ -395,9 +482,12 @@ class HotPath:
             sk_a = None if merge > 0 else ds_a
             ln1, mean1, rstd1 = ops.layernorm_fwd(x, P[pre + "norm1.weight"], P[pre + "norm1.bias"], c.ln_eps, T)
             qkv = ops.linear_fwd(ln1, self.w(pre + "attn.qkv.weight", P), P[pre + "attn.qkv.bias"], EPI_BIAS, rowskip=sk_a, skip_rows_per_sample=L)
-            rcat = self.relpos(pre, P, False)
-            ao, lse, atab = ops.attn_fwd(qkv, rcat, Bc, L, c.heads, c.Hp, c.Wp, c.scale, need_tables=True, rowskip=sk_a) if need_grad else \
-                ops.attn_fwd(qkv, rcat, Bc, L, c.heads, c.Hp, c.Wp, c.scale, rowskip=sk_a) + (None,)
+            rcat = self.relpos_grid(c, pre, P) if other else self.relpos(pre, P, False)
+            if other and c.attn_any:       # a grid pa_attn_fwd refuses (70 x 35): the any-grid forward; a dropped sample is computed, its factor is 0
+                ao, lse, atab = ops_anysize.attn_any_fwd(qkv, rcat, Bc, L, c.heads, c.Hp, c.Wp, c.scale) + (None,)
+            else:
+                ao, lse, atab = ops.attn_fwd(qkv, rcat, Bc, L, c.heads, c.Hp, c.Wp, c.scale, need_tables=True, rowskip=sk_a) if need_grad else \
+                    ops.attn_fwd(qkv, rcat, Bc, L, c.heads, c.Hp, c.Wp, c.scale, rowskip=sk_a) + (None,)
             group = 0
             if merge > 0:
                 # x1 = x0 + s_a * ens(proj(...)) (models_seggpt.py:207-238).  Differentiable like the reference's Block.forward: mean over

@@ -295,7 +295,17 @@ class Painter(nn.Module):
             raise RuntimeError("painter_amd runs the hot path on an MI355X only (HIP kernels, no CPU/PyTorch fallback); "
                                "move the module and inputs to 'cuda'. The CPU oracle lives in oracle/ for tests.")
         B = imgs.shape[0]
-        L = self.patch_embed.num_patches
+        assert imgs.dim() == 4 and imgs.shape[1] == 3 and tgts.shape == imgs.shape, (imgs.shape, tgts.shape)
+        # The run-time size decides the token grid (models_painter.py:385-400 is size-agnostic: get_abs_pos / get_rel_pos resize).  At the
+        # constructed size grid is self._cfg and everything below is what it always was; another size is forward only and is refused here,
+        # before anything is launched, when it breaks a structural requirement or when autograd would record the call.
+        grid = self._hot.grid(imgs.shape[2], imgs.shape[3])
+        if grid is not self._cfg and torch.is_grad_enabled() and \
+                (imgs.requires_grad or tgts.requires_grad or any(p_.requires_grad for p_ in self.parameters())):
+            raise NotImplementedError("painter_amd HIP path: input size %d x %d differs from the constructed %d x %d, which is forward only "
+                                      "(the backward kernels are built for the constructed grid): call under torch.no_grad()"
+                                      % (grid.H, grid.W, self._cfg.H, self._cfg.W))
+        L = grid.L
         if bool_masked_pos is None:
             bool_masked_pos = torch.zeros((B, L), dtype=torch.bool, device=imgs.device)
         else:
@@ -305,7 +315,7 @@ class Painter(nn.Module):
         # (kept in the graph: a bf16 / fp16 input under autocast gets its gradient back in its own dtype)
         imgs_c = imgs.to(torch.float32).contiguous()
         tgts_c = tgts.to(torch.float32).contiguous()
-        assert imgs_c.shape == (B, 3, self._cfg.H, self._cfg.W) and tgts_c.shape == imgs_c.shape, imgs_c.shape
+        assert imgs_c.shape == (B, 3, grid.H, grid.W) and tgts_c.shape == imgs_c.shape, imgs_c.shape
         if valid is None:
             valid = torch.ones_like(tgts_c)
         in_place = valid.dtype == torch.float32 and valid.is_contiguous() and valid.is_cuda

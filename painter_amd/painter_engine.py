@@ -290,8 +290,10 @@ def _coco_params(iou_thrs, area_ranges, max_dets):
 
 def _forward(model, imgs, tgts):
     """The model call of the scripts' run_one_image (painter_inference_segm.py:76-84): second half of the canvas masked, everything
-    valid; eval mode, no_grad.  -> float32 tokens [N][L][p*p*3]."""
-    n = model.patch_embed.num_patches
+    valid; eval mode, no_grad.  -> float32 tokens [N][L][p*p*3].  The mask has the RUN-TIME number of tokens (h * w // patch_size ** 2,
+    painter_inference_pano_semseg.py:78): an engine at input_size=560 runs the 896 x 448 checkpoint on 70 x 35 tokens."""
+    p = int(model.patch_size)
+    n = (imgs.shape[2] // p) * (imgs.shape[3] // p)
     masked = torch.zeros(1, n, device=imgs.device)
     masked[:, n // 2:] = 1
     return model(imgs, tgts, masked, torch.ones_like(tgts))[1]
