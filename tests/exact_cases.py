@@ -9,9 +9,14 @@ integer fp32 holds exactly.  V is position-coded: a wrong output row names the k
 Attention with tied winners (tie_case, further down): 1, 2 or 4 keys tie at logit exactly 0 in every row, so P = 1/n and dS, dQ, dK and the
 table gradients are non-zero dyadic rationals; the expectation is the fp64 autograd of attn_reference.
 
+Attention on any token grid (ANY_ROUTES, further down): the same cases on ragged grids for the forward of csrc/attn_any.hip, one more kind
+(below_zero: every logit <= -150) and any_algebra, an fp64 forward over that kernel's own key walk that also returns what named wrong
+kernels would.
+
 Convolution (64 channels, 3x3, padding 1): small integers, int64 references from nine shifted matmuls.
 
-The parametrisations of tests/test_attention_exact_gpu.py, tests/test_attention_ties_gpu.py and tests/test_conv3x3_exact_gpu.py live here, so that
+The parametrisations of tests/test_attention_exact_gpu.py, tests/test_attention_ties_gpu.py, tests/test_attention_any_exact_gpu.py and
+tests/test_conv3x3_exact_gpu.py live here, so that
 tests/test_exact_cases_cpu.py can assert, without a GPU, the conditions those tests rest on -- for every one of them."""
 import functools
 from dataclasses import dataclass
@@ -548,6 +553,174 @@ def tie_shapes():
             if key not in seen:
                 seen.append(key)
     return seen
+
+
+# ------------------------------------------------------------------------------------------------ attention on any token grid
+# csrc/attn_any.hip (pa_attn_any_fwd) is the generic forward with other index arithmetic: the exact cases above carry over to ragged grids,
+# forward only (tests/test_attention_any_exact_gpu.py; conditions and named wrong forwards in tests/test_exact_cases_cpu.py).
+# (B, H, Hp, Wp), each the smallest grid that reaches what it names:
+ANY_RAGGED = [(2, 2, 2, 1),       # L = 2, Wp = 1, one wave live
+              (2, 2, 6, 3),       # the Wp < 4 branch, a single partial tile
+              (2, 2, 11, 2),      # the same with Wp = 2
+              (1, 2, 3, 11),      # L = 33: the last tile holds 1 key
+              (2, 2, 9, 7),       # L = 63: the last tile holds 31 keys
+              (2, 2, 10, 5),      # the grid of the model-level fixture
+              (2, 2, 5, 13),      # L = 65: three query tiles and one idle wave
+              (2, 2, 4, 33),      # Wp > 32: a tile lies inside one key row; five tiles, the second workgroup has one live wave
+              (2, 2, 12, 6),      # L % 4 == 0 and Wp % 4 != 0
+              (1, 1, 35, 17)]     # L = 595, half of 70 x 35: 19 tiles, five workgroups
+ANY_BIAS_ONLY = (1, 1, 62, 31)    # L = 1922, bias_rank alone: the content cases' margin drops to 132 there, below MIN_MARGIN
+ANY_ALIGNED = [(2, 2, 8, 4), (2, 2, 8, 28)]       # grids pa_attn_fwd takes as well: both kernels must equal the expectation
+ANY_TIE_ONLY = [(2, 2, 10, 6),    # L = 60: tied winners with a partial tile
+                (2, 2, 12, 3)]    # ... and in the Wp < 4 branch
+ANY_HD80_MAX_L = 200
+ANY_KINDS = ATTN_KINDS + ("below_zero",)
+# 70 x 35 itself (the COCO panoptic size) stays with the tolerance test tests/test_any_size_gpu.py::test_attn_any_vs_float64:
+# position_coded_v holds Hp, Wp <= 63.
+
+
+def _any_grids(hd):
+    grids = ANY_RAGGED + [ANY_BIAS_ONLY] + ANY_ALIGNED + ANY_TIE_ONLY
+    return [g for g in grids if hd == 64 or g[2] * g[3] <= ANY_HD80_MAX_L]
+
+
+# route -> (dtype name, head_dim, the launch counter that must move by one per call, [(B, H, Hp, Wp)])
+ANY_ROUTES = {"any_bf16_hd64": ("bf16", 64, "pa_attn_any_launches", _any_grids(64)),
+              "any_bf16_hd80": ("bf16", 80, "pa_attn_any_launches", _any_grids(80)),
+              "any_fp32_hd64": ("fp32", 64, "pa_attn_any_launches", _any_grids(64)),
+              "any_fp32_hd80": ("fp32", 80, "pa_attn_any_launches", _any_grids(80))}
+
+
+def any_kinds(grid):
+    """The kinds one grid runs: the six gather kinds and below_zero, and all six tie kinds where L % 4 == 0 (forward only: a dense dO
+    costs nothing here, so head dim 80 runs the dense kinds too)."""
+    if grid == ANY_BIAS_ONLY:
+        return ("bias_rank",)
+    if grid in ANY_TIE_ONLY:
+        return TIE_KINDS
+    return ANY_KINDS + (TIE_KINDS if grid[2] * grid[3] % 4 == 0 else ())
+
+
+def any_route_params():
+    """-> [(route, kind, B, H, Hp, Wp)] in the order the GPU tests run them."""
+    return [(route, kind) + grid for route, spec in ANY_ROUTES.items() for grid in spec[3] for kind in any_kinds(grid)]
+
+
+def any_shapes():
+    """Every distinct (kind, B, H, Hp, Wp, hd) the any-grid GPU tests build."""
+    seen = []
+    for route, kind, B, H, Hp, Wp in any_route_params():
+        key = (kind, B, H, Hp, Wp, ANY_ROUTES[route][1])
+        if key not in seen:
+            seen.append(key)
+    return seen
+
+
+BELOW_ZERO_CHANNEL = 37
+
+
+def below_zero_case(B, H, Hp, Wp, hd, seed):
+    """content_case on a permutation with channel 37 turned into a shift channel, the way tie_case does it: K = -8 (hd + 24) there in
+    every key and q = a_q.  The target's logit is a_q (hd - 1) from the hd - 1 code channels and -a_q (hd + 24) from the shift channel:
+    -25 a_q = -150, -200 or -250, every other key's lower by 2 a_q per code channel it differs in.  EVERY logit of every row is far below
+    zero -- the first tile's running maximum too, the regime of the generation-2 / 3 NaN -- and a key >= L that stayed alive with its zeroed
+    K row (logit 0) would win every row by >= 150 and return its zero V row."""
+    base = content_case(B, H, Hp, Wp, hd, "permutation", seed)
+    L = Hp * Wp
+    x = base.qkv.clone().reshape(B, L, 3, H, hd)
+    amp = torch.tensor(AMPLITUDES, dtype=torch.float32)[torch.arange(L) % len(AMPLITUDES)]
+    x[:, :, 0, :, BELOW_ZERO_CHANNEL] = amp[None, :, None]
+    x[:, :, 1, :, BELOW_ZERO_CHANNEL] = -8.0 * (hd + 24)
+    return AttnCase("below_zero", B, H, Hp, Wp, hd, x.reshape(B * L, 3 * H * hd).contiguous(), base.rel_h, base.rel_w, base.dout)
+
+
+@functools.lru_cache(maxsize=None)
+def any_case(kind, B, H, Hp, Wp, hd):
+    """-> (case, AttnExpect | TieExpect) of one (kind, shape): the cases of attn_case and tie_attn_case as they are (shared with the routes
+    above where the grid is), below_zero built here.  Read-only."""
+    if kind in TIE_KINDS:
+        return tie_attn_case(kind, B, H, Hp, Wp, hd)
+    if kind == "below_zero":
+        case = below_zero_case(B, H, Hp, Wp, hd, 1000 * Hp + 10 * Wp + hd + len(ATTN_KINDS))
+        return case, reference(case)
+    return attn_case(kind, B, H, Hp, Wp, hd)
+
+
+ANY_FAULTS = ("row_of_first_key", "column_wrap_zero", "carry_lost", "tail_keys_alive", "last_key_dropped", "tail_tile_dropped",
+              "pad_row_stored")
+
+
+def any_key_walk(L, Hp, Wp, fault=None):
+    """The key walk of attn_any.hip restated -> (kh, kw, zero_col), [ceil(L / 32) * 32] each: for every key slot of every 32-key tile the
+    key row (clamped to Hp - 1, as the kernel clamps it) and key column whose table entries the logit takes, and whether the column entry
+    reads as 0.  A tile is eight runs of four keys; a run starts at the (kh, kw) its lane carries from tile to tile -- + 32 / Wp rows,
+    + 32 % Wp columns, one carry -- and steps key by key.  (For Wp >= 4 the kernel does not step: it selects between two row entries and
+    reads four consecutive column entries from a table that repeats its first three behind its end, which is the same walk.)  Faults:
+      row_of_first_key   the keys of a run behind a row crossing take the run's first row
+      column_wrap_zero   the same keys read a zero column entry (the repeated entries were never written)
+      carry_lost         the per-tile column wrap does not bump the row"""
+    nt = (L + 31) // 32
+    kh, kw = torch.empty(nt * 32, dtype=torch.int64), torch.empty(nt * 32, dtype=torch.int64)
+    zero = torch.zeros(nt * 32, dtype=torch.bool)
+    start = [((4 * r) // Wp, (4 * r) % Wp) for r in range(8)]
+    for j in range(nt):
+        for r in range(8):
+            h0, w0 = start[r]
+            hh, ww = h0, w0
+            for t in range(4):
+                k = 32 * j + 4 * r + t
+                kh[k] = h0 if fault == "row_of_first_key" else hh
+                kw[k] = ww
+                zero[k] = fault == "column_wrap_zero" and hh != h0
+                ww += 1
+                if ww == Wp:
+                    ww, hh = 0, hh + 1
+            h0, w0 = h0 + 32 // Wp, w0 + 32 % Wp
+            if w0 >= Wp:
+                h0, w0 = h0 + (0 if fault == "carry_lost" else 1), w0 - Wp
+            start[r] = (h0, w0)
+    return kh.clamp_max(Hp - 1), kw, zero
+
+
+def any_algebra(case, fault=None):
+    """The any-grid forward written out in fp64 over the kernel's own key walk -> dict(logits [B*H, L, Lp], out [B*L, H*hd], lse [B*H, L]),
+    Lp = the keys of whole tiles.  Without `fault` it is the expectation once more; with one it is what a named wrong kernel would
+    return (real outputs, not an argmax).  The walk faults: any_key_walk.  The others:
+      tail_keys_alive    keys >= L keep their zeroed K and V rows, a clamped row entry and a FINITE logit
+      last_key_dropped   key L - 1 is left out
+      tail_tile_dropped  the partial last tile is skipped (with a single tile every row is 0 / 0 = NaN)
+      pad_row_stored     rows >= L of the last query tile -- copies of row L - 1 -- are written where they point: the next sample's first rows
+    Winners at a common logit with every other key >= 150 below give exactly 1 / n here: exp(0) = 1, the losers' exp() is below 1e-65."""
+    B, H, L, hd, Hp, Wp, s = case.B, case.H, case.L, case.hd, case.Hp, case.Wp, case.scale
+    assert fault is None or fault in ANY_FAULTS
+    q, k, v = case.qkv.double().reshape(B, L, 3, H, hd).permute(2, 0, 3, 1, 4).reshape(3, B * H, L, hd).unbind(0)
+    Rh, Rw = case.rel_h.double(), case.rel_w.double()
+    kh, kw, zero = any_key_walk(L, Hp, Wp, fault)
+    Lp, BH = kh.numel(), B * H
+    alive = torch.arange(Lp) < L
+    if fault == "tail_keys_alive":
+        alive[:] = True
+    elif fault == "last_key_dropped":
+        alive[L - 1] = False
+    elif fault == "tail_tile_dropped" and L % 32:
+        alive[L // 32 * 32:] = False
+    pad = torch.zeros(BH, Lp - L, hd, dtype=torch.float64)
+    kx, vx = torch.cat([k, pad], 1), torch.cat([v, pad], 1)
+    qi = torch.arange(L)
+    ih = (qi[:, None] // Wp - kh[None, :] + Hp - 1).expand(BH, L, Lp)                # the table rows of (query, key slot)
+    iw = (qi[:, None] % Wp - kw[None, :] + Wp - 1).expand(BH, L, Lp)
+    Gh, Gw = q @ Rh.t(), q @ Rw.t()
+    logits = (s * q) @ kx.transpose(1, 2) + torch.gather(Gh, 2, ih) + torch.gather(Gw, 2, iw) * (~zero).double()[None, None, :]
+    logits = logits.masked_fill(~alive[None, None, :], float("-inf"))
+    m = logits.max(-1, keepdim=True).values
+    e = torch.exp(logits - m)
+    l = e.sum(-1, keepdim=True)
+    out = ((e / l) @ vx).reshape(B, H, L, hd).permute(0, 2, 1, 3).reshape(B * L, H * hd).contiguous()
+    if fault == "pad_row_stored":
+        for b in range(B - 1):
+            n = min(Lp - L, L)
+            out[(b + 1) * L:(b + 1) * L + n] = out[b * L + L - 1]
+    return dict(logits=logits, out=out, lse=(m + torch.log(l)).squeeze(-1))
 
 
 # ------------------------------------------------------------------------------------------------ 3x3 convolution

@@ -152,6 +152,46 @@ def test_relpos_resize_vs_float64(sh, sw, dh, dw, hd):
         assert torch.equal(rcat[k, :dh + dw], out[k]) and not rcat[k, dh + dw:].any()
 
 
+DYADIC_PAIRS = [(8, 16), (16, 8), (8, 32), (32, 8), (12, 48), (45, 15), (27, 9), (3, 6), (6, 3), (4, 1), (1, 4)]
+
+
+def dyadic_tables(n, hd, nb, seed):
+    """nb tables [n, hd] whose entries are integer multiples of 8 in [-248, 248]."""
+    g = torch.Generator().manual_seed(seed)
+    return [(torch.randint(-31, 32, (n, hd), generator=g) * 8).float() for _ in range(nb)]
+
+
+@pytest.mark.parametrize("hd", [64, 80])
+@pytest.mark.parametrize("role", ["h", "w"])
+@pytest.mark.parametrize("src,dst", DYADIC_PAIRS, ids=["%dto%d" % p for p in DYADIC_PAIRS])
+def test_relpos_resize_dyadic_cases_are_exact(src, dst, role, hd):
+    """Length pairs whose ratio is a power of two, or 3 with an odd source: the source coordinate n_src / n_dst * (j + 0.5) - 0.5 and both
+    weights are dyadic rationals of a few bits, and the entries are multiples of 8 up to 248, so float32 computes every output without a
+    rounding -- CPU F.interpolate in float32 equals the float64 statement bit for bit (asserted here), and the kernel must too: no
+    `2 x torch's own deviation`.  Each pair resizes rel_pos_h while rel_pos_w keeps another pair, and the other way round; even lengths,
+    which no model asks for, are lengths like any other to the kernel.  Covered: the gather index, both clamps (s < 0 at j = 0, i1 at the
+    end), 1 -> n and n -> 1, and the block and table addressing (three blocks, h rows in front of w rows)."""
+    nb = 3
+    other = (15, 5)                                            # the other table: ratio 3, odd source, exact as well
+    (sh, dh), (sw, dw) = ((src, dst), other) if role == "h" else (other, (src, dst))
+    hs, ws = dyadic_tables(sh, hd, nb, 100 * src + dst), dyadic_tables(sw, hd, nb, 100 * src + dst + 7)
+    for t in hs + ws:
+        assert float(t.abs().max()) <= 248 and bool((t % 8 == 0).all())
+    dev_h, dev_w = [t.cuda() for t in hs], [t.cuda() for t in ws]
+    tabs = torch.tensor([t.data_ptr() for t in dev_h] + [t.data_ptr() for t in dev_w], dtype=torch.int64).cuda()
+    out = ops_anysize.relpos_resize(tabs, nb, sh, sw, dh, dw, hd)
+    assert out.shape == (nb, dh + dw, hd) and out.dtype == torch.float32
+    out = out.cpu()
+    for k in range(nb):
+        for name, t, got, n in (("rel_pos_h", hs[k], out[k, :dh], dh), ("rel_pos_w", ws[k], out[k, dh:], dw)):
+            want = resize_statement(t, n)
+            assert torch.equal(want.float().double(), want) and torch.equal(torch_resize(t, n).double(), want)      # (the case is exact)
+            bad = (got.double() != want).nonzero()
+            assert not len(bad), ("block %d %s %d -> %d: %d of %d entries differ from the float64 statement; first: row %d channel %d, got %r, expected %r"
+                                  % (k, name, t.shape[0], n, len(bad), got.numel(), int(bad[0][0]), int(bad[0][1]),
+                                     float(got[tuple(bad[0])]), float(want[tuple(bad[0])])))
+
+
 def test_relpos_resize_to_the_same_lengths_launches_nothing(monkeypatch):
     counting = CountingLib(ops_anysize.lib)
     monkeypatch.setattr(ops_anysize, "lib", counting)

@@ -1,5 +1,8 @@
 """The conditions tests/test_attention_exact_gpu.py and tests/test_conv3x3_exact_gpu.py rest on, asserted on the CPU for every case those
-files build (the parametrisations are shared through tests/exact_cases.py)."""
+files build (the parametrisations are shared through tests/exact_cases.py); and for tests/test_attention_any_exact_gpu.py, together with
+the named wrong forwards its cases must see."""
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -293,3 +296,163 @@ def test_tie_case_conditions_and_sensitivity(kind, B, H, Hp, Wp, hd):
         assert far >= 16, (fault, beyond)
         assert not tables_only or max(seen[n] for n in ("dq", "dk", "dv")) == 0
     print("  " + "; ".join(line))
+
+
+# ------------------------------------------------------------------------------------------------ attention on any token grid
+ANY_SHAPES = X.any_shapes()
+_ANY_IDS = ["%s-%dx%dx%dx%d-hd%d" % s for s in ANY_SHAPES]
+
+
+def test_the_any_grid_parametrisation_covers_what_it_says():
+    """Four routes (bf16 / fp32, head dim 64 / 80) on the any-grid launch counter; the six gather kinds and below_zero on every ragged and
+    every aligned grid, the six tie kinds wherever L % 4 == 0 and on the two tie grids, bias_rank alone at 62 x 31; head dim 80 up to
+    L = 200.  70 x 35 is not here: position_coded_v holds Hp, Wp <= 63, and that grid stays with the tolerance test."""
+    params = X.any_route_params()
+    assert set(X.ANY_ROUTES) == {"any_%s_hd%d" % (t, hd) for t in ("bf16", "fp32") for hd in (64, 80)}
+    ragged = {(2, 2, 2, 1), (2, 2, 6, 3), (2, 2, 11, 2), (1, 2, 3, 11), (2, 2, 9, 7), (2, 2, 10, 5), (2, 2, 5, 13), (2, 2, 4, 33),
+              (2, 2, 12, 6), (1, 1, 35, 17)}
+    assert set(X.ANY_RAGGED) == ragged and X.ANY_BIAS_ONLY == (1, 1, 62, 31) and X.ANY_ALIGNED == [(2, 2, 8, 4), (2, 2, 8, 28)]
+    assert X.ANY_TIE_ONLY == [(2, 2, 10, 6), (2, 2, 12, 3)]
+    for route, (tname, hd, counter, grids) in X.ANY_ROUTES.items():
+        assert counter == "pa_attn_any_launches" and route == "any_%s_hd%d" % (tname, hd)
+        every = X.ANY_RAGGED + [X.ANY_BIAS_ONLY] + X.ANY_ALIGNED + X.ANY_TIE_ONLY
+        assert grids == [g for g in every if hd == 64 or g[2] * g[3] <= 200]
+        assert hd == 64 or {g for g in every if g not in grids} == {(1, 1, 35, 17), (1, 1, 62, 31), (2, 2, 8, 28)}
+        for grid in grids:
+            kinds = [p[1] for p in params if p[0] == route and p[2:] == grid]
+            assert len(kinds) == len(set(kinds))
+            L = grid[2] * grid[3]
+            if grid == X.ANY_BIAS_ONLY:
+                assert kinds == ["bias_rank"]
+            elif grid in X.ANY_TIE_ONLY:
+                assert set(kinds) == set(X.TIE_KINDS) and L % 4 == 0 and L % 32 != 0
+            else:
+                assert set(kinds) == set(X.ATTN_KINDS) | {"below_zero"} | (set(X.TIE_KINDS) if L % 4 == 0 else set())
+    tie_grids = {p[2:] for p in params if p[1] in X.TIE_KINDS}
+    assert {(2, 2, 12, 6), (2, 2, 4, 33), (2, 2, 8, 4), (2, 2, 10, 6), (2, 2, 12, 3)} <= tie_grids
+    assert not any(ops_takes(g) for g in X.ANY_RAGGED + [X.ANY_BIAS_ONLY] + X.ANY_TIE_ONLY) and all(ops_takes(g) for g in X.ANY_ALIGNED)
+    assert max(B * H * Hp * Wp for _, _, B, H, Hp, Wp in params) == 1922 and len(ANY_SHAPES) == len(set(ANY_SHAPES))
+
+
+def ops_takes(grid):
+    """pa_attn_fwd's shape conditions (include/painter_hip.h), restated without importing the library."""
+    _, _, Hp, Wp = grid
+    return Hp * Wp % 32 == 0 and Hp % 4 == 0 and Wp % 4 == 0
+
+
+@pytest.mark.parametrize("Hp,Wp", sorted({s[3:5] for s in ANY_SHAPES}), ids=lambda v: str(v))
+def test_any_key_walk_without_a_fault_is_row_major(Hp, Wp):
+    """The walk of attn_any.hip restated (exact_cases.any_key_walk) visits key k at (k // Wp, k % Wp); keys >= L clamp to the last row."""
+    L = Hp * Wp
+    kh, kw, zero = X.any_key_walk(L, Hp, Wp)
+    k = torch.arange(kh.numel())
+    assert kh.numel() == (L + 31) // 32 * 32 and not bool(zero.any())
+    assert torch.equal(kh, (k // Wp).clamp_max(Hp - 1)) and torch.equal(kw, k % Wp)
+    # each walk fault moves some key < L exactly where its name says, or the grid has no such key
+    crossing = (k // Wp != (k - k % 4) // Wp) & (k < L)                     # keys behind a row crossing inside their 4-key run
+    fh, _, _ = X.any_key_walk(L, Hp, Wp, "row_of_first_key")
+    assert torch.equal((fh != kh) & (k < L), crossing) and torch.equal(fh[crossing], ((k - k % 4) // Wp)[crossing])
+    _, fw, fz = X.any_key_walk(L, Hp, Wp, "column_wrap_zero")
+    assert torch.equal(fz & (k < L), crossing) and torch.equal(fw, kw)
+    ch, cw, _ = X.any_key_walk(L, Hp, Wp, "carry_lost")
+    assert torch.equal(cw, kw) and bool((ch <= kh).all()) and torch.equal(ch[:32], kh[:32])
+    if 32 % Wp == 0 or L <= 32:                                              # no wrap ever, or no second tile: nothing to lose
+        assert torch.equal(ch, kh)
+
+
+@functools.lru_cache(maxsize=None)
+def any_fault_rows(kind, B, H, Hp, Wp, hd):
+    """-> (quantum of the expected out, {fault: number of (token, head) output rows the wrong forward moves by at least one quantum})."""
+    case, exp = X.any_case(kind, B, H, Hp, Wp, hd)
+    want = exp.out.double()
+    quantum = X.tie_quantum(want)
+    rows = {}
+    for fault in X.ANY_FAULTS:
+        got = X.any_algebra(case, fault)["out"]
+        diff = torch.nan_to_num((got - want).abs(), nan=float("inf"))        # 0 / 0 of a row without keys counts as wrong
+        rows[fault] = int((diff.reshape(B * Hp * Wp, H, hd).max(-1).values >= quantum).sum())
+    return quantum, rows
+
+
+@pytest.mark.parametrize("kind,B,H,Hp,Wp,hd", ANY_SHAPES, ids=_ANY_IDS)
+def test_any_grid_case_conditions(kind, B, H, Hp, Wp, hd):
+    """What tests/test_attention_any_exact_gpu.py rests on, for every case it builds: the margin, integer operands that bf16 holds, an
+    expected out that bf16 holds, and -- the forward algebra over the kernel's own key walk gives the expectation bit for bit."""
+    case, exp = X.any_case(kind, B, H, Hp, Wp, hd)
+    L = Hp * Wp
+    alg = X.any_algebra(case)
+    for name in ("qkv", "rel_h", "rel_w"):
+        assert bf16_exact_integers(getattr(case, name)), name
+    assert case.scale == 0.125 and (case.B, case.H, case.Hp, case.Wp, case.hd, case.kind) == (B, H, Hp, Wp, hd, kind)
+    assert torch.equal(alg["out"], exp.out.double()) and bf16_exact(exp.out) and alg["logits"].shape == (B * H, L, (L + 31) // 32 * 32)
+    assert float((alg["lse"] - exp.lse).abs().max()) < 1e-9
+    logits = alg["logits"][..., :L]
+    assert bool(torch.isinf(alg["logits"][..., L:]).all()) and bool((logits == logits.round()).all()) and float(logits.abs().max()) < 2 ** 24
+    quantum, rows = any_fault_rows(kind, B, H, Hp, Wp, hd)
+    if kind in X.TIE_KINDS:
+        # the conditions of test_tie_case_conditions_and_sensitivity, restricted to the forward quantities
+        assert torch.equal(exp.nwin, X.tie_winner_count(L)[None, None].expand(B, H, L)) and set(exp.nwin.unique().tolist()) == {1, 2, 4}
+        assert int(exp.nwin[0, 0, L - 1]) == 4 and int(exp.nwin[0, 0, L - 3]) == 2 and float(exp.loser) <= -X.MIN_MARGIN
+        for tile in range(L // 32):
+            assert set(exp.nwin[0, 0, 32 * tile:32 * tile + 32].tolist()) == {1, 2, 4}
+        assert float(logits.max()) == 0 and torch.equal((logits == 0).sum(-1).reshape(B, H, L), exp.nwin)
+        q = case.qkv.reshape(B, L, 3, H, hd)[:, :, 0]
+        assert bf16_exact(q * case.scale)
+        assert float((q.double() @ case.rel_h.double().t()).abs().max()) == 0 and float((q.double() @ case.rel_w.double().t()).abs().max()) == 0
+        assert torch.equal(exp.lse, torch.log(exp.nwin.double()).reshape(B * H, L))
+        assert quantum in (0.25, 0.5, 1.0) and float((exp.out * 4 - (exp.out * 4).round()).abs().max()) == 0
+        # P = 1 / n and l = n exactly, and the fp32 sum of the winners' V rows is exact: |V| <= 64, four terms
+        assert float(X.tie_exact_sums(case, X.tie_algebra(case))["out"]) < 2 ** 24
+        if L % 32:                    # a key >= L left alive sits at exactly 0 and joins every row's tie: V / n becomes V / (n + phantoms)
+            assert rows["tail_keys_alive"] == B * H * L
+    else:
+        assert exp.margin.shape == (B, H, L) and float(exp.margin.min()) >= X.MIN_MARGIN, float(exp.margin.min())
+        assert torch.equal(exp.lse.reshape(B, H, L), exp.top) and torch.equal(exp.top, exp.top.round())
+        assert bf16_exact_integers(exp.out) and 1 <= float(exp.out.abs().min()) and float(exp.out.abs().max()) <= 64 and quantum >= 1
+    if kind == "below_zero":
+        assert float(exp.top.max()) <= -150 and float(logits.max()) <= -150
+        assert all(torch.equal(exp.target[b, h].sort().values, torch.arange(L)) for b in range(B) for h in range(H))
+        assert float(case.rel_h.abs().max()) == 0 and float(case.rel_w.abs().max()) == 0
+        kq = case.qkv.reshape(B, L, 3, H, hd)
+        assert bool((kq[:, :, 1, :, X.BELOW_ZERO_CHANNEL] == -8 * (hd + 24)).all()) and set(kq[:, :, 0, :, X.BELOW_ZERO_CHANNEL].unique().tolist()) == set(X.AMPLITUDES[:min(L, 3)])
+        if L % 32:                    # a zero-K key >= L left alive wins every row by >= 150 and returns its zero V row
+            assert rows["tail_keys_alive"] == B * H * L
+            assert float(X.any_algebra(case, "tail_keys_alive")["out"].abs().max()) < 1e-60      # (fp64 keeps exp(-150); fp32 does not)
+    if kind == "all_to_last":
+        assert rows["last_key_dropped"] == B * H * L
+        assert L % 32 == 0 or rows["tail_tile_dropped"] == B * H * L
+    if L % 32 == 0:
+        assert rows["tail_keys_alive"] == rows["tail_tile_dropped"] == rows["pad_row_stored"] == 0
+    elif B > 1:
+        # rows >= L of the last query tile are copies of row L - 1; stored, they land on the next sample's first rows, whose expected
+        # content differs in every row and head (V names its sample).  On the device this is also held through a pre-filled out buffer.
+        n = min((L + 31) // 32 * 32 - L, L)
+        assert rows["pad_row_stored"] == (B - 1) * H * n
+        want = exp.out.double().reshape(B, L, H, hd)
+        assert bool((want[1:, :n] != want[:-1, L - 1:L]).any(-1).all())
+    print("%s %dx%dx%dx%d hd%d: quantum %g; output rows (of %d) each wrong forward moves: %s" % (kind, B, H, Hp, Wp, hd, quantum, B * H * L, rows))
+
+
+@pytest.mark.parametrize("hd", [64, 80])
+@pytest.mark.parametrize("fault", X.ANY_FAULTS)
+def test_every_named_wrong_forward_is_caught(fault, hd):
+    """Each wrong forward of exact_cases.any_algebra changes some out element of some case by at least one quantum -- for either head dim, and
+    for the two faults of the 4-key run also in each of the kernel's two branches (Wp < 4: stepping per key; Wp >= 4: two row entries and a
+    select).  A condition, not a measurement: a fault no case sees wants another case."""
+    seen = {True: [], False: []}
+    for s in ANY_SHAPES:
+        if s[5] == hd and any_fault_rows(*s)[1][fault]:
+            seen[s[4] < 4].append("%s %dx%d: %d rows" % (s[0], s[3], s[4], any_fault_rows(*s)[1][fault]))
+    print("%s hd%d: caught by %d cases with Wp < 4, %d with Wp >= 4; first %s" % (fault, hd, len(seen[True]), len(seen[False]), (seen[True] + seen[False])[:3]))
+    assert seen[True] or seen[False], fault
+    if fault in ("row_of_first_key", "column_wrap_zero"):
+        assert seen[True] and seen[False], (fault, seen)
+
+
+ANY_BIAS_SHAPES = [s for s in ANY_SHAPES if s[0] == "bias_rank" and s not in ATTN_SHAPES]
+
+
+@pytest.mark.parametrize("kind,B,H,Hp,Wp,hd", ANY_BIAS_SHAPES, ids=["%dx%dx%dx%d-hd%d" % s[1:] for s in ANY_BIAS_SHAPES])
+def test_bias_rank_tables_decide_alone_on_ragged_grids(kind, B, H, Hp, Wp, hd):
+    """test_bias_rank_tables_decide_alone on the grids only the any-grid kernel takes: one right (kh, kw) per query, margin a multiple of 256."""
+    test_bias_rank_tables_decide_alone(kind, B, H, Hp, Wp, hd)
