@@ -1,4 +1,4 @@
-"""ctypes binding of libpainter_hip.so.  Prototypes are parsed from include/painter_hip.h (and include/painter_rle.h, painter_paint.h, painter_minmax.h, painter_anysize.h) so the Python
+"""ctypes binding of libpainter_hip.so.  Prototypes are parsed from include/painter_hip.h (and include/painter_rle.h, painter_paint.h, painter_minmax.h, painter_anysize.h, painter_anysize_grad.h) so the Python
 side cannot drift from the C ABI.  There is NO fallback: if the library is missing the import of any
 compute entry point raises (the product path never routes through PyTorch ops or the oracle)."""
 import ctypes
@@ -9,7 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(HERE), "include", "painter_hip.h")
 # further headers of the same library, in the same declaration style: their entry points are additions, PA_ABI_VERSION lives in HEADER
 MORE_HEADERS = (os.path.join(os.path.dirname(HERE), "include", "painter_rle.h"), os.path.join(os.path.dirname(HERE), "include", "painter_paint.h"),
-                os.path.join(os.path.dirname(HERE), "include", "painter_minmax.h"), os.path.join(os.path.dirname(HERE), "include", "painter_anysize.h"))
+                os.path.join(os.path.dirname(HERE), "include", "painter_minmax.h"), os.path.join(os.path.dirname(HERE), "include", "painter_anysize.h"),
+                os.path.join(os.path.dirname(HERE), "include", "painter_anysize_grad.h"))
 LIB_PATH = os.environ.get("PAINTER_AMD_LIB") or os.path.join(HERE, "lib", "libpainter_hip.so")      # PAINTER_AMD_LIB: A/B builds (diagnostics)
 
 PA_F32, PA_BF16 = 0, 1

@@ -69,6 +69,7 @@ def headers():
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_paint.h"))
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_minmax.h"))
     hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_anysize.h"))
+    hs.append(os.path.join(os.path.dirname(HERE), "include", "painter_anysize_grad.h"))
     return sorted(hs)
 
 

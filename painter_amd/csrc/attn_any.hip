@@ -10,37 +10,9 @@
 //      images -- they are never read from memory, where they are the next sample's first tokens or nobody's (0 * NaN would be NaN);
 //   3. rows >= L of the last query tile run on a copy of row L - 1 (a load that stays inside the sample) and are not stored.
 #include "attn_common.h"
+#include "attn_any.h"
 #include "../../include/painter_hip.h"
 #include "../../include/painter_anysize.h"
-
-// RowStage / TrStage with a row bound: rows >= nrows of the 32-row tile are zeros
-template <typename T, int NT, int HD> struct RowStageB : RowStage<T, NT, HD> {
-    typedef RowStage<T, NT, HD> S;
-    DEVI void load(const T* src, size_t ld, int tid, int nrows) {
-#pragma unroll
-        for (int i = 0; i < S::CK; ++i) {
-            const int c = tid + NT * i;
-            if (c < S::NCH) {
-                const int row = c / S::SL;
-                this->r[i] = row < nrows ? *reinterpret_cast<const uint4*>(src + (size_t)row * ld + (c % S::SL) * TT<T>::EPC) : zero4();
-            }
-        }
-    }
-};
-template <typename T, int HD> struct TrStageB : TrStage<T, HD> {
-    typedef TrStage<T, HD> S;
-    DEVI void load(const T* src, size_t ld, int tid, int nrows) {
-        if (tid < 8 * S::CBN) {
-            const int cb = tid % S::CBN, rb = tid / S::CBN;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = rb * 4 + i;
-                if (row < nrows) this->r[i] = *reinterpret_cast<const typename S::Vec4*>(src + (size_t)row * ld + cb * 4);
-                else zero_vec(this->r[i]);
-            }
-        }
-    }
-};
 
 template <typename T, int NW, int HD>
 __global__ __launch_bounds__(NW * 64) void attn_any_kernel(const T* __restrict__ qkv, size_t ldq, const T* __restrict__ rcat,

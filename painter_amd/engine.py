@@ -91,7 +91,7 @@ class HotPathConfig:
 
 class _Grid:
     """The configuration at a run-time input size other than the constructed one (HotPath.grid): every field of the HotPathConfig it was
-    derived from, with H, W, Hp, Wp, L of the run; forward only."""
+    derived from, with H, W, Hp, Wp, L of the run.  The backward reads the grid of its forward from _Saved.grid."""
 
     def __init__(self, cfg, H, W):
         self.__dict__.update(cfg.__dict__)
@@ -99,7 +99,7 @@ class _Grid:
         self.Hp, self.Wp = self.H // cfg.P, self.W // cfg.P
         self.L = self.Hp * self.Wp
         self.attn_any = not ops_anysize.attn_fwd_takes(self.L, self.Hp, self.Wp)     # a grid such as 16 x 8 changes only the tables
-        self.M = None              # per device: the rows of abs_pos_operator(src, Hp, Wp)
+        self.M = None              # per device: the sparse rows of abs_pos_operator(src, Hp, Wp) and of its transpose
         self.rel = {}              # the resized, packed rel-pos tables (HotPath.relpos_grid)
 
 
@@ -188,13 +188,18 @@ class _Streams:
 
 class _Backward:
     """The per-call context the parts of HotPath.backward share."""
-    __slots__ = ("P", "S", "sync", "want", "st", "G", "flats", "rc_shape", "dnorm")
+    __slots__ = ("P", "S", "sync", "want", "st", "G", "flats", "rc_shape", "rel_shape", "dnorm")
 
     def __init__(self, P, S, sync, want, st):
         self.P, self.S, self.sync, self.want, self.st = P, S, sync, want, st
         self.G = {}
         self.flats = {}                                    # block -> its flat small-gradient buffer (HotPath.block_flat)
-        self.rc_shape = tuple(S.blocks[-1].rcat.shape)     # Rcat [NRP, head_dim]: the same for every block
+        self.rc_shape = tuple(S.blocks[-1].rcat.shape)     # Rcat [NRP, head_dim] of the forward's grid: the same for every block
+        # the rel-pos gradient slot of a block's flat buffer: [NRP, head_dim] at the STORED table lengths (the constructed grid's)
+        self.rel_shape = self.rc_shape
+        if isinstance(S.grid, _Grid):
+            sh, sw = P["blocks.0.attn.rel_pos_h"].shape[0], P["blocks.0.attn.rel_pos_w"].shape[0]
+            self.rel_shape = (ops.lib.pa_relpos_rows_padded((sh + 1) // 2, (sw + 1) // 2), self.rc_shape[1])
         self.dnorm = None                                  # the four taps' accumulated d(norm.weight, norm.bias)
 
     def need(self, n):
@@ -239,6 +244,7 @@ class HotPath:
         # allocator hazard on the gradient buckets, and SLP-packed fp32 VALU code mis-computing beside another kernel's MFMA
         # workgroups (build.py: -fno-slp-vectorize); DESIGN.md section 6.
         self.use_side_stream = _SIDE_STREAM
+        self.grad_any_size = False     # the backward at another size than the constructed one is refused unless switched on
         _configure_library()
 
     def side_stream(self, device):
@@ -281,8 +287,8 @@ class HotPath:
         alternately each keep their own.  What remains required of another size: H == 2W and both whole numbers of patches
         (NotImplementedError before anything is launched).  The constructed size's "width a multiple of 4" follows from that where a
         forward kernel needs it -- the patch embedding reads 8-pixel groups of a patch row only when P % 8 == 0, pixel by pixel otherwise
-        (patch 14 at 140 x 70) -- and the loss, the decoder tail and patchify address single pixels.  Forward only: the backward kernels
-        are built for the constructed grid."""
+        (patch 14 at 140 x 70) -- and the loss, the decoder tail and patchify address single pixels.  A forward that saves for a backward
+        at another size needs the switch grad_any_size."""
         c = self.cfg
         H, W = int(H), int(W)
         if (H, W) == (c.H, c.W):
@@ -298,14 +304,16 @@ class HotPath:
         return g
 
     def grid_pos_operator(self, g, device):
-        """The sparse rows of abs_pos_operator(src, Hp, Wp) for a run-time grid (forward half only), cached on the grid."""
-        if g.M is None or g.M[0].device != device:
-            idx, val, _ = hostmath.sparse_rows(hostmath.abs_pos_operator(g.src, g.Hp, g.Wp))
-            g.M = (torch.from_numpy(idx).to(device), torch.from_numpy(val).to(device))
+        """-> (sparse rows of M, sparse rows of M^T) of abs_pos_operator(src, Hp, Wp) for a run-time grid, cached on the grid: the bicubic
+        resize of the position grid and its transpose, through which pos_embed gets its gradient."""
+        if g.M is None or g.M[0][0].device != device:
+            M = hostmath.abs_pos_operator(g.src, g.Hp, g.Wp)
+            dev = lambda t: (torch.from_numpy(t[0]).to(device), torch.from_numpy(t[1]).to(device))
+            g.M = (dev(hostmath.sparse_rows(M)), dev(hostmath.sparse_rows(M.T)))
         return g.M
 
-    def relpos_grid(self, g, pre, P):
-        """Rcat of block `pre` for the run-time grid g: every block's tables are resized to 2Hp - 1 / 2Wp - 1 rows by ONE launch
+    def relpos_grid(self, g, pre, P, transposed=False):
+        """Rcat (or Rcat^T, for the backward) of block `pre` for the run-time grid g: every block's tables are resized to 2Hp - 1 / 2Wp - 1 rows by ONE launch
         (pa_relpos_resize: the reference's get_rel_pos, F.interpolate(mode="linear")) into a buffer that pa_relpos_pack_batch then packs
         for the grid -- two launches per (grid, table version), none afterwards.  Cached like relpos(), on the grid: keyed on the tables'
         addresses and versions, so two sizes used alternately each keep their tables."""
@@ -315,7 +323,7 @@ class HotPath:
         st = g.rel
         if st and st["dev"] == rh.device and st["T"] == self.T and st["ptr"][i] == (rh.data_ptr(), rw.data_ptr()) and \
                 st["ver"][i] == (rh._version, rw._version):
-            return st["rcat"][i]
+            return (st["rcatT"] if transposed else st["rcat"])[i]
         hs = [P["blocks.%d.attn.rel_pos_h" % k] for k in range(c.depth)]
         ws = [P["blocks.%d.attn.rel_pos_w" % k] for k in range(c.depth)]
         hd, sh, sw = rh.shape[1], rh.shape[0], rw.shape[0]
@@ -335,7 +343,7 @@ class HotPath:
         st.clear()
         st.update(dev=rh.device, T=self.T, ptr=ptr, ver=[(h._version, w._version) for h, w in zip(hs, ws)], tabs=tabs, resized=resized,
                   addr=addr, rcat=rcat, rcatT=rcatT)
-        return rcat[i]
+        return (rcatT if transposed else rcat)[i]
 
     # ------------------------------------------------------------------ constants / casts
     def pos_operator(self, device):
@@ -439,22 +447,23 @@ class HotPath:
         T = self.T
         c = self.grid(imgs.shape[2], imgs.shape[3])        # self.cfg at the constructed size; the per-grid state of another size otherwise
         other = c is not self.cfg
-        if other and need_grad:
+        if other and need_grad and not self.grad_any_size:
             raise NotImplementedError("painter_amd HIP path: input size %d x %d differs from the constructed %d x %d, which is forward only "
-                                      "(the backward kernels are built for the constructed grid): call under torch.no_grad()"
-                                      % (c.H, c.W, self.cfg.H, self.cfg.W))
+                                      "by default: call under torch.no_grad(), or switch the backward at any size on "
+                                      "(model.grad_at_any_size(True) / HotPath.grad_any_size)" % (c.H, c.W, self.cfg.H, self.cfg.W))
         dev = imgs.device
         B = imgs.shape[0]
         L, D = c.L, c.D
         assert tuple(imgs.shape) == (B, 3, c.H, c.W) and tgts.shape == imgs.shape and mask_u8.shape[-1] == L, (imgs.shape, tgts.shape, mask_u8.shape)
         S = _Saved()
         S.B, S.need_grad = B, need_grad
+        S.grid = c                                         # the backward runs on the grid of its forward
         keep = lambda n: need_grad and (want is None or n in want)
         S.imgs, S.tgts, S.mask, S.valid = imgs, tgts, mask_u8, valid
         S.drop = drop_scales
         S.seg_type = seg_type if c.seggpt else None
         pe = P["pos_embed"][0, c.cls:]
-        pos = ops.pos_fwd(self.grid_pos_operator(c, dev) if other else self.pos_operator(dev)[0], pe, L, D)
+        pos = ops.pos_fwd((self.grid_pos_operator(c, dev) if other else self.pos_operator(dev))[0], pe, L, D)
         tok_args = (P["patch_embed.proj.bias"], P["mask_token"], P["segment_token_x"], P["segment_token_y"], pos, mask_u8,
                     P.get("type_token_cls") if c.seggpt else None, P.get("type_token_ins") if c.seggpt else None,
                     seg_type if c.seggpt else None)
@@ -578,7 +587,7 @@ class HotPath:
 
     def _backward_decoder(self, X, dloss, dpatch, want_tgts):
         """Loss, decoder tail and decoder_embed -> (dconcat T [B*L, 4D], the loss's own term of dpred or None)."""
-        c, T, P, S, G, st, need = self.cfg, self.T, X.P, X.S, X.G, X.st, X.need
+        c, T, P, S, G, st, need = X.S.grid, self.T, X.P, X.S, X.G, X.st, X.need
         B = S.B
         dpred_loss = None          # the loss's own term of dpred: its direct gradient w.r.t. tgts is -dpred_loss
         if dpatch is None:
@@ -634,7 +643,7 @@ class HotPath:
         writes block i's fc2 bias gradient into it."""
         if i not in X.flats:
             D = self.cfg.D
-            sizes = [2 * D, 2 * D, 3 * D, D, self.cfg.hidden, D, X.rc_shape[0] * X.rc_shape[1]]
+            sizes = [2 * D, 2 * D, 3 * D, D, self.cfg.hidden, D, X.rel_shape[0] * X.rel_shape[1]]
             fb = X.st.shared(torch.empty((sum(sizes),), dtype=torch.float32, device=X.S.imgs.device))
             X.flats[i] = (fb, dict(zip(("n1", "n2", "qkv", "proj", "fc1", "fc2", "rel"), torch.split(fb, sizes))))
         return X.flats[i]
@@ -642,7 +651,8 @@ class HotPath:
     def _backward_block(self, X, i, dconcat, dx, dyT_next):
         """Block i: (dx of its output -- None at the last block --, the dY of its fc2 when block i + 1's norm1 backward emitted it)
         -> (dx of its input, the dY of block i - 1's fc2 or None)."""
-        c, T, P, S, G, st, need = self.cfg, self.T, X.P, X.S, X.G, X.st, X.need
+        c, T, P, S, G, st, need = X.S.grid, self.T, X.P, X.S, X.G, X.st, X.need
+        other = c is not self.cfg                  # a backward at another size than the constructed one (grad_any_size)
         B, L, D = S.B, c.L, c.D
         dev = S.imgs.device
         tr = self._tr
@@ -712,15 +722,38 @@ class HotPath:
         dao = ops.linear_dgrad(dyA, self.w(pre + "attn.proj.weight", P), out=dln2, rowskip=sk_a, rows_per_sample=L)
         tr("%d.dao" % i, dao)
         del dyA
-        rcatT = self.relpos(pre, P, True)
-        dqkv, dG = ops.attn_bwd_core(b.qkv, b.rcat, rcatT, b.ao, dao, b.lse, b.Bc, L, c.heads, c.Hp, c.Wp, c.scale, tables=b.atab, rowskip=sk_a)
-        if need(pre + "attn.rel_pos_h") or need(pre + "attn.rel_pos_w"):
-            # (the dQ kernel still writes its rel-pos partials / dG when the tables are frozen: only this reduction is skipped)
-            drcat = st.run(lambda: ops.attn_bwd_relpos(dG, b.qkv, nrp, b.Bc, L, c.heads, c.Hp, c.Wp, out=fl["rel"].view(nrp, hd)), dG, b.qkv)
-            nh, nw = 2 * c.Hp - 1, 2 * c.Wp - 1
-            G[pre + "attn.rel_pos_h"] = drcat[:nh]
-            G[pre + "attn.rel_pos_w"] = drcat[nh:nh + nw]
-        del dG
+        want_rel = need(pre + "attn.rel_pos_h") or need(pre + "attn.rel_pos_w")
+        if other:
+            # The tables of this run are the stored ones resized (relpos_grid): the attention backward gives their gradient at the run-time
+            # lengths (scratch), pa_relpos_resize_bwd -- a parameter gradient: side stream -- carries it to the stored lengths, into the
+            # block's flat buffer.  A grid pa_attn_bwd refuses goes through the any-grid backward, which computes a dropped sample too
+            # (its dout rows are zeros); a grid such as 16 x 8 through the existing kernels.
+            rcatT = self.relpos_grid(c, pre, P, transposed=True)
+            dG = None
+            if c.attn_any:
+                dqkv, drun = ops_anysize.attn_any_bwd(b.qkv, b.rcat, rcatT, b.ao, dao, b.lse, b.Bc, L, c.heads, c.Hp, c.Wp, c.scale, need_drcat=want_rel)
+            else:
+                dqkv, dG = ops.attn_bwd_core(b.qkv, b.rcat, rcatT, b.ao, dao, b.lse, b.Bc, L, c.heads, c.Hp, c.Wp, c.scale, tables=b.atab, rowskip=sk_a)
+            if want_rel:
+                sh, sw = P[pre + "attn.rel_pos_h"].shape[0], P[pre + "attn.rel_pos_w"].shape[0]
+
+                def table_grads():
+                    d = drun if dG is None else ops.attn_bwd_relpos(dG, b.qkv, nrp, b.Bc, L, c.heads, c.Hp, c.Wp)
+                    return ops_anysize.relpos_resize_bwd(d, sh, sw, 2 * c.Hp - 1, 2 * c.Wp - 1, out=fl["rel"].view(X.rel_shape))
+                drcat = st.run(table_grads, dG, b.qkv, drun if dG is None else None)
+                G[pre + "attn.rel_pos_h"] = drcat[:sh]
+                G[pre + "attn.rel_pos_w"] = drcat[sh:sh + sw]
+            del dG
+        else:
+            rcatT = self.relpos(pre, P, True)
+            dqkv, dG = ops.attn_bwd_core(b.qkv, b.rcat, rcatT, b.ao, dao, b.lse, b.Bc, L, c.heads, c.Hp, c.Wp, c.scale, tables=b.atab, rowskip=sk_a)
+            if want_rel:
+                # (the dQ kernel still writes its rel-pos partials / dG when the tables are frozen: only this reduction is skipped)
+                drcat = st.run(lambda: ops.attn_bwd_relpos(dG, b.qkv, nrp, b.Bc, L, c.heads, c.Hp, c.Wp, out=fl["rel"].view(nrp, hd)), dG, b.qkv)
+                nh, nw = 2 * c.Hp - 1, 2 * c.Wp - 1
+                G[pre + "attn.rel_pos_h"] = drcat[:nh]
+                G[pre + "attn.rel_pos_w"] = drcat[nh:nh + nw]
+            del dG
         tr("%d.dqkv" % i, dqkv)
         X.param_grads(pre + "attn.qkv.weight", pre + "attn.qkv.bias", dqkv, b.ln1, fl["qkv"])
         dln1 = ops.linear_dgrad(dqkv, self.w(pre + "attn.qkv.weight", P), out=dao, rowskip=sk_a, rows_per_sample=L)
@@ -750,7 +783,7 @@ class HotPath:
 
     def _backward_tokens(self, X, dx, dpred_loss, want_imgs, want_tgts):
         """Token assembly + patch embedding (and the last gradient bucket) -> (d imgs, d tgts), None where not asked for."""
-        c, T, P, S, G, need = self.cfg, self.T, X.P, X.S, X.G, X.need
+        c, T, P, S, G, need = X.S.grid, self.T, X.P, X.S, X.G, X.need
         B, L, D = S.B, c.L, c.D
         if X.dnorm is not None:
             G["norm.weight"], G["norm.bias"] = X.dnorm[0], X.dnorm[1]
@@ -764,7 +797,8 @@ class HotPath:
             G["patch_embed.proj.bias"] = ops.colsum(dpe)
         if need("pos_embed"):
             dposemb = torch.zeros_like(P["pos_embed"])
-            ops.pos_bwd(self.pos_operator(S.imgs.device)[1], sums[0], sums[1], dposemb[0, c.cls:], c.src * c.src, D)
+            opT = (self.grid_pos_operator(c, S.imgs.device) if c is not self.cfg else self.pos_operator(S.imgs.device))[1]
+            ops.pos_bwd(opT, sums[0], sums[1], dposemb[0, c.cls:], c.src * c.src, D)
             G["pos_embed"] = dposemb
         for k_, nm in enumerate(("segment_token_x", "segment_token_y", "mask_token")):
             if need(nm):

@@ -290,6 +290,14 @@ class Painter(nn.Module):
                 out.append((s[2 * i, :bc], s[2 * i + 1, :bc]))         # contiguous row prefixes: no copies
         return out
 
+    def grad_at_any_size(self, on=True):
+        """Switch the backward at input sizes other than the constructed one on or off (off by default: such a call is refused as soon as
+        autograd would record it).  On, a call at any (2W, W) of whole patches is differentiable with respect to the parameters, imgs,
+        tgts and through pred_patch: the any-grid attention backward, the adjoint of the rel-pos table resize and the transposed bicubic
+        position operator carry the gradients to the stored parameters.  The constructed size takes the same route either way.  -> self."""
+        self._hot.grad_any_size = bool(on)
+        return self
+
     def _run(self, imgs, tgts, bool_masked_pos, valid, seg_type=None, merge_between_batch=-1):
         if not imgs.is_cuda:
             raise RuntimeError("painter_amd runs the hot path on an MI355X only (HIP kernels, no CPU/PyTorch fallback); "
@@ -297,14 +305,14 @@ class Painter(nn.Module):
         B = imgs.shape[0]
         assert imgs.dim() == 4 and imgs.shape[1] == 3 and tgts.shape == imgs.shape, (imgs.shape, tgts.shape)
         # The run-time size decides the token grid (models_painter.py:385-400 is size-agnostic: get_abs_pos / get_rel_pos resize).  At the
-        # constructed size grid is self._cfg and everything below is what it always was; another size is forward only and is refused here,
-        # before anything is launched, when it breaks a structural requirement or when autograd would record the call.
+        # constructed size grid is self._cfg and everything below is what it always was; another size is refused here, before anything is
+        # launched, when it breaks a structural requirement or -- unless grad_at_any_size(True) -- when autograd would record the call.
         grid = self._hot.grid(imgs.shape[2], imgs.shape[3])
-        if grid is not self._cfg and torch.is_grad_enabled() and \
+        if grid is not self._cfg and not self._hot.grad_any_size and torch.is_grad_enabled() and \
                 (imgs.requires_grad or tgts.requires_grad or any(p_.requires_grad for p_ in self.parameters())):
             raise NotImplementedError("painter_amd HIP path: input size %d x %d differs from the constructed %d x %d, which is forward only "
-                                      "(the backward kernels are built for the constructed grid): call under torch.no_grad()"
-                                      % (grid.H, grid.W, self._cfg.H, self._cfg.W))
+                                      "by default: call under torch.no_grad(), or switch the backward at any size on with "
+                                      "model.grad_at_any_size(True)" % (grid.H, grid.W, self._cfg.H, self._cfg.W))
         L = grid.L
         if bool_masked_pos is None:
             bool_masked_pos = torch.zeros((B, L), dtype=torch.bool, device=imgs.device)

@@ -10,6 +10,14 @@ variants of every comparison alternating, medians of >= 20 runs with the spread:
 
     python tools/any_size_bench.py [--runs 20 --iters 5 --skip-model] -> lines per comparison, then one JSON line
 
+--grad measures the BACKWARD at that size instead, same conventions:
+  (a) attention backward alone -- pa_attn_any_bwd (Delta, dQ + dG, dK / dV, table contraction) at 70 x 35, B = 8, 16 heads, bf16, beside
+      the existing backward (ops.attn_bwd, reported by kernel family) on the grid padded to 72 x 36 -- another function, a cost yardstick
+      only, and one pa_attn_bwd may refuse (its dK / dV kernel's table tile ends at Hp + Wp = 94 for head_dim 64): the refusal is then
+      what the log records -- and beside the existing backward at the constructed 56 x 28, by its rate per (query, key) pair.
+  (b) the ViT-L forward + backward at 1120 x 560 (grad_at_any_size), bf16, B = 1 and the largest B of 8, 4, 2 that fits, beside the
+      oracle's torch op sequence under bf16 autocast with autograd on the same GPU.  Reported only.
+
 (c), the bench.py line against the parent commit, needs the parent's tree and is taken by alternating fresh processes of the two trees;
 its log is filed beside this one."""
 import argparse
@@ -84,6 +92,80 @@ def attention(runs, iters, B=8, H=16):
     return res
 
 
+def attention_bwd(runs, iters, B=8, H=16):
+    scale = 0.125
+    legs, res_extra = {}, {}
+    for name, (Hp, Wp) in (("attn_any_bwd_70x35", (70, 35)), ("attn_bwd_padded_72x36", (72, 36)), ("attn_bwd_56x28", (56, 28))):
+        L = Hp * Wp
+        g = torch.Generator().manual_seed(3)
+        qkv = torch.randn((B * L, 3 * H * 64), generator=g).to(BF16).cuda()
+        dout = torch.randn((B * L, H * 64), generator=g).to(BF16).cuda()
+        rel_h, rel_w = (0.2 * torch.randn((2 * Hp - 1, 64), generator=g)).cuda(), (0.2 * torch.randn((2 * Wp - 1, 64), generator=g)).cuda()
+        rcat, rcatT = ops.relpos_pack(rel_h, rel_w, Hp, Wp, BF16), ops.relpos_pack_t(rel_h, rel_w, Hp, Wp, BF16)
+        if name.startswith("attn_any"):
+            out, lse = ops_anysize.attn_any_fwd(qkv, rcat, B, L, H, Hp, Wp, scale)
+            legs[name] = lambda a=(qkv, rcat, rcatT, out, dout, lse, B, L, H, Hp, Wp, scale): ops_anysize.attn_any_bwd(*a)
+            continue
+        out, lse, tables = ops.attn_fwd(qkv, rcat, B, L, H, Hp, Wp, scale, need_tables=True)
+        c0 = ops.attn_launch_counts()["bwd"]
+        try:
+            ops.attn_bwd(qkv, rcat, rcatT, out, dout, lse, B, L, H, Hp, Wp, scale, tables=tables)
+        except RuntimeError as e:          # (72 x 36: the generic dK / dV kernel's table tile holds Hp + Wp <= 94 at head_dim 64)
+            res_extra[name] = {"refused": str(e)}
+            continue
+        c1 = ops.attn_launch_counts()["bwd"]
+        res_extra[name] = {"kernels": ("generation 1", "generation 2", "generation 3")[[y - x for x, y in zip(c0, c1)].index(1)]}
+        legs[name] = lambda a=(qkv, rcat, rcatT, out, dout, lse, B, L, H, Hp, Wp, scale), t=tables: ops.attn_bwd(*a, tables=t)
+    res = alternate(legs, runs, iters)
+    pairs = {"attn_any_bwd_70x35": B * H * 2450 ** 2, "attn_bwd_padded_72x36": B * H * 2450 ** 2, "attn_bwd_56x28": B * H * 1568 ** 2}
+    for k, v in res.items():
+        v["useful_pairs_per_ns"] = round(pairs[k] / (v["median"] * 1e6), 2)
+    for k, v in res_extra.items():
+        res.setdefault(k, {}).update(v)
+    if "median" in res.get("attn_bwd_padded_72x36", {}):
+        res["native_over_padded_median"] = round(res["attn_any_bwd_70x35"]["median"] / res["attn_bwd_padded_72x36"]["median"], 3)
+    return res
+
+
+def model_grad(runs, iters, batches=(1, 8)):
+    cfg = O.vit_large_config()
+    run = dataclasses.replace(cfg, img_size=(1120, 560))
+    m = models_painter.painter_vit_large_patch16_input896x448_win_dec64_8glb_sl1(compute_dtype="bf16")
+    P = O.random_params(cfg, 1)
+    m.load_state_dict(P, strict=True)
+    m = m.cuda().eval().grad_at_any_size(True)
+    Pd = {k: v.cuda().requires_grad_(True) for k, v in P.items()}
+    out = {}
+    for B in batches:
+        while B > 1:                                    # the largest batch at which both legs fit
+            try:
+                imgs, tgts, mask, valid = (t.cuda() for t in O.synthetic_batch(run, B, 2, "half"))
+                with torch.autocast("cuda", dtype=BF16):
+                    O.forward(Pd, cfg, imgs, tgts, mask, valid.clone())[0].backward()
+                break
+            except torch.cuda.OutOfMemoryError:
+                B //= 2
+                torch.cuda.empty_cache()
+        imgs, tgts, mask, valid = (t.cuda() for t in O.synthetic_batch(run, B, 2, "half"))
+        mb = mask.reshape(B, 70, 35)
+
+        def ours():
+            m.zero_grad(set_to_none=True)
+            m(imgs, tgts, bool_masked_pos=mb, valid=valid)[0].backward()
+
+        def oracle():
+            for p in Pd.values():
+                p.grad = None
+            with torch.autocast("cuda", dtype=BF16):
+                loss = O.forward(Pd, cfg, imgs, tgts, mask, valid.clone())[0]
+            loss.backward()
+        res = alternate({"painter_amd_ms": ours, "torch_ops_bf16_autocast_ms": oracle}, runs, iters if B == 1 else 1)
+        res["speedup_median"] = round(res["torch_ops_bf16_autocast_ms"]["median"] / res["painter_amd_ms"]["median"], 2)
+        out["B%d" % B] = res
+        print("model forward + backward 1120x560 B=%d: %s" % (B, json.dumps(res)), flush=True)
+    return out
+
+
 def model(runs, iters, batches=(1, 8)):
     cfg = O.vit_large_config()
     run = dataclasses.replace(cfg, img_size=(1120, 560))
@@ -116,12 +198,21 @@ def main():
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--grad", action="store_true", help="the backward at that size (DESIGN.md 4.22) instead of the forward")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("any_size_bench: needs the MI355X (nothing here is measured on a CPU)")
     assert a.runs >= 20, "medians of at least 20 runs"
     summary = {"what": "forward at 1120 x 560 on the 896 x 448 ViT-L (70 x 35 tokens)", "device": torch.cuda.get_device_name(0),
                "runs": a.runs, "iters": a.iters}
+    if a.grad:
+        summary["what"] = "forward + backward at 1120 x 560 on the 896 x 448 ViT-L (70 x 35 tokens)"
+        summary["attention_bwd_B8_H16_bf16_ms"] = attention_bwd(a.runs, a.iters)
+        print("attention backward: %s" % json.dumps(summary["attention_bwd_B8_H16_bf16_ms"]), flush=True)
+        if not a.skip_model:
+            summary["model_fwd_bwd_bf16"] = model_grad(a.runs, a.iters)
+        print(json.dumps(summary))
+        return
     summary["attention_B8_H16_bf16_ms"] = attention(a.runs, a.iters)
     print("attention: %s" % json.dumps(summary["attention_B8_H16_bf16_ms"]), flush=True)
     if not a.skip_model:
