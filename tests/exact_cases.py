@@ -11,12 +11,13 @@ table gradients are non-zero dyadic rationals; the expectation is the fp64 autog
 
 Attention on any token grid (ANY_ROUTES, further down): the same cases on ragged grids for the forward of csrc/attn_any.hip, one more kind
 (below_zero: every logit <= -150) and any_algebra, an fp64 forward over that kernel's own key walk that also returns what named wrong
-kernels would.
+kernels would.  ANY_BWD_ROUTES, behind it: the backward of csrc/attn_any_bwd.hip on tie cases for ragged L (tie_loners) and on the gather
+kinds, with any_bwd_algebra, the fp64 backward over that kernel's key walk and its named wrong kernels.
 
 Convolution (64 channels, 3x3, padding 1): small integers, int64 references from nine shifted matmuls.
 
-The parametrisations of tests/test_attention_exact_gpu.py, tests/test_attention_ties_gpu.py, tests/test_attention_any_exact_gpu.py and
-tests/test_conv3x3_exact_gpu.py live here, so that
+The parametrisations of tests/test_attention_exact_gpu.py, tests/test_attention_ties_gpu.py, tests/test_attention_any_exact_gpu.py,
+tests/test_attention_any_bwd_exact_gpu.py and tests/test_conv3x3_exact_gpu.py live here, so that
 tests/test_exact_cases_cpu.py can assert, without a GPU, the conditions those tests rest on -- for every one of them."""
 import functools
 from dataclasses import dataclass
@@ -175,7 +176,10 @@ def reference(case):
         _, lse = attn_reference(case.qkv, case.rel_h, case.rel_w, B, L, H, case.Hp, case.Wp, case.scale)
     logits = cap.logits
     assert cap.calls == 1 and logits is not None and logits.dtype == torch.float64 and logits.shape == (B * H, L, L)
-    top2, idx2 = logits.topk(2, dim=-1)
+    if L == 1:                                      # a single key: no runner-up, the margin is infinite
+        top2, idx2 = torch.cat([logits, torch.full_like(logits, float("-inf"))], -1), torch.zeros(B * H, 1, 2, dtype=torch.int64)
+    else:
+        top2, idx2 = logits.topk(2, dim=-1)
     target = idx2[..., 0].reshape(B, H, L)
     v = case.qkv.reshape(B, L, 3, H, hd)[:, :, 2].permute(0, 2, 1, 3)                    # [B, H, L, hd]
     out = torch.gather(v, 2, target[..., None].expand(B, H, L, hd)).permute(0, 2, 1, 3).reshape(B * L, H * hd).contiguous()
@@ -285,8 +289,36 @@ def tie_layout(hd):
     return order[:na], order[na:na + 8], order[na + 8:na + 16], order[na + 16:na + 19], order[na + 19]
 
 
-def tie_members(placement, L):
-    """-> int64 [L/4, 4]: the keys of each group; member m and member m ^ 2 are the pair a two-way tie leaves."""
+def tie_loners(L, Wp):
+    """-> the L % 4 keys of a ragged grid that stay outside every group of four (ascending; none where L % 4 == 0).  A loner has a group
+    code of its own, so a row that asks for it has ONE winner.  Loners are taken from the interior: outside the first and the last key row
+    and the first and the last 32-key tile where the grid has such keys; else outside both key rows and the last tile; else anywhere but
+    key 0 and the last tile -- never in the last tile, whose keys must all carry a non-zero dS, unless the grid has one tile only
+    (L <= 32), and never key 0 or L - 1, which the `near` and `mirror` placements pair up.  Wish i is key L // 2 - 3 - 5 i; the nearest
+    free key of the tier is taken."""
+    n, last = L % 4, (L - 1) // 32 * 32
+    if n == 0:
+        return []
+    keys = range(L)
+    tiers = ([k for k in keys if Wp <= k < L - Wp and 32 <= k < last], [k for k in keys if Wp <= k < L - Wp and k < last],
+             [k for k in keys if 0 < k < min(last, L - 1)], [k for k in keys if Wp <= k < L - Wp and L <= 32],
+             [k for k in keys if 0 < k < L - 1 and L <= 32])
+    room = next((t for t in tiers if len(t) >= n), None)
+    if room is None:
+        raise ValueError("a grid of %d keys has no room for %d loners: use the gather kinds there" % (L, n))
+    out = []
+    for i in range(n):
+        out.append(min((k for k in room if k not in out), key=lambda k: (abs(k - (L // 2 - 3 - 5 * i)), k)))
+    return sorted(out)
+
+
+def tie_members(placement, L, Wp=None):
+    """-> int64 [L // 4, 4]: the keys of each group; member m and member m ^ 2 are the pair a two-way tie leaves.  On a ragged grid
+    (L % 4 != 0; Wp is needed then) the groups are placed over the L - L % 4 keys that are no loners, in key order."""
+    if L % 4:
+        loners = tie_loners(L, Wp)
+        rest = torch.tensor([k for k in range(L) if k not in loners])
+        return rest[tie_members(placement, L - L % 4)]
     g = torch.arange(L // 4)
     if placement == "near":                         # neighbours, two keys off the multiples of four: mostly one 32-key tile and one key row,
         m = [(4 * g + 2 + i) % L for i in range(4)]  # some across a row or tile boundary, and one group is keys L - 2, L - 1, 0, 1
@@ -315,19 +347,23 @@ def tie_case(B, H, Hp, Wp, hd, placement, sparse, seed):
     and the generic ones as a rounded fp32 -- attn_common.h:151 --, which un-ties nothing but moves lse by up to 2.  So q . R is exactly
     zero in every tie case: q is zero wherever a table is not.)  Offset channel: q = K = 0, rel_pos_h[j] = rel_pos_w[j] = j + 1 -- no
     logit changes, and dQ there is sum_k dS[q, k] (Rh[qh - kh] + Rw[qw - kw]), which names the offsets the kernel used.  Every q entry is 0
-    or +-a_q, three significant bits: that keeps the fp32 sums of the table gradients exact."""
+    or +-a_q, three significant bits: that keeps the fp32 sums of the table gradients exact.
+    Ragged grids (L % 4 != 0): the L % 4 keys of tie_loners each form a group of their own and the groups of four are placed over the
+    other keys; with L % 4 == 0 the draws, and so the case, are what they were before ragged grids were admitted."""
     g = torch.Generator().manual_seed(seed)
     L = Hp * Wp
-    assert L % 4 == 0
     active, s1, s2, shift, offset = tie_layout(hd)
-    members = tie_members(placement, L)
-    group_of, member_of = torch.empty(L, dtype=torch.int64), torch.empty(L, dtype=torch.int64)
+    members, loners = tie_members(placement, L, Wp), tie_loners(L, Wp)
+    ng = L // 4 + len(loners)                       # groups of four, then one group per loner (member 0 of its own code)
+    assert L // 4 >= 4
+    group_of, member_of = torch.empty(L, dtype=torch.int64), torch.zeros(L, dtype=torch.int64)
     group_of[members] = torch.arange(L // 4)[:, None].expand(L // 4, 4)
     member_of[members] = torch.arange(4)[None, :].expand(L // 4, 4)
+    group_of[loners] = L // 4 + torch.arange(len(loners))
     while True:                                     # group codes at least 8 active channels apart (>= 192 below, as the flip sets are)
-        gcode = (torch.randint(0, 2, (B, H, L // 4, hd), generator=g) * 16 - 8).float()
+        gcode = (torch.randint(0, 2, (B, H, ng, hd), generator=g) * 16 - 8).float()
         a = gcode[..., active] / 8
-        if int(((len(active) - a @ a.transpose(-1, -2)) / 2 + 99 * torch.eye(L // 4)).min()) >= 8:
+        if int(((len(active) - a @ a.transpose(-1, -2)) / 2 + 99 * torch.eye(ng)).min()) >= 8:
             break
     k = gcode[:, :, group_of]                       # [B, H, L, hd]
     k[..., s1] *= (1 - 2 * (member_of & 1)).float()[None, None, :, None]
@@ -337,6 +373,20 @@ def tie_case(B, H, Hp, Wp, hd, placement, sparse, seed):
     t = _target_map("permutation", B, H, L, g)
     amp = torch.tensor(TIE_AMPLITUDES, dtype=torch.float32)[torch.arange(L) % len(TIE_AMPLITUDES)]
     n = tie_winner_count(L)
+    if L % 4:
+        # dK = scale * dS q with dS a multiple of 1/16 in a four-winner row whose V rows sum to an odd number (groups placed over a ragged
+        # grid do): amplitude 14 would make dK a multiple of 1/64 there, the expectations are to stay multiples of 1/32
+        amp = torch.where((n == 4) & (amp == 14), torch.tensor(16.0), amp)
+    # a row that asks for a loner has one winner whatever n says: hand every loner to a row that is to have one winner anyway (the first
+    # such rows whose own target is no loner), so that the rows keep the winner counts of tie_winner_count -- the last row its four
+    for bh in range(B * H if loners else 0):
+        tb = t[bh // H, bh % H]
+        is_loner = torch.zeros(L, dtype=torch.bool)
+        is_loner[loners] = True
+        free = [q for q in range(L) if int(n[q]) == 1 and not bool(is_loner[tb[q]])]
+        for q in [q for q in range(L) if int(n[q]) != 1 and bool(is_loner[tb[q]])]:
+            q2 = free.pop(0)
+            tb[q], tb[q2] = int(tb[q2]), int(tb[q])
     q = torch.gather(k, 2, t[..., None].expand(B, H, L, hd)) / 8 * amp[None, None, :, None]
     q[:, :, :, s1] *= (n < 4).float()[None, None, :, None]
     q[:, :, :, s2] *= (n < 2).float()[None, None, :, None]
@@ -415,8 +465,10 @@ def tie_quantum(t):
     raise AssertionError("not dyadic to 2^-10")
 
 
-def tie_fp32_bounds(case, alg):
-    """-> dict(dq, dk, dv [B*L, H*hd], drcat [2Hp-1 + 2Wp-1, hd]), f64: how far the fp32 build may be from the exact answer, element by
+def tie_fp32_bounds(case, alg, n_dq=20, n_dg=4):
+    """(n_dq, n_dg: the term counts of dQ and of one bias-gradient entry; the defaults are attn_bwd.hip's, derived below;
+    any_bwd_fp32_bounds passes attn_any_bwd.hip's.)
+    -> dict(dq, dk, dv [B*L, H*hd], drcat [2Hp-1 + 2Wp-1, hd]), f64: how far the fp32 build may be from the exact answer, element by
     element, as (sum of |terms|) * c * 2^-22.  The fp32 build runs the generic kernels.  At a winner s = 0 and the bias is 0, so the
     backward's exponent is -lse2 alone, lse2 = lse * LOG2E_F (attn_bwd.hip:139, :201-204 and :415-418) with lse = (m + log2 l) * LN2_F
     (attn_fwd.hip:150), m = 0 and l = n exactly: v_log_f32 is good to 1 ulp (2^-23 relative), the two multiplications round by 2^-24 each
@@ -460,10 +512,10 @@ def tie_fp32_bounds(case, alg):
     a_slab = torch.einsum("hsrj,hsrc->hsjc", slabs(dG), slabs(q.abs()))
     n_slab = (slabs(aG) != 0).sum(2).double()                                           # [H, slab, J]
     tab_sum = (a_slab * n_slab[..., None] / 4).sum((0, 1)) + a_slab.sum((0, 1)) * (splits * H) / 4
-    return dict(dq=rows(s * adS @ k.abs() + aGh @ case.rel_h.double().abs() + aGw @ case.rel_w.double().abs()) * (2.25 + 20 / 4) * u,
+    return dict(dq=rows(s * adS @ k.abs() + aGh @ case.rel_h.double().abs() + aGw @ case.rel_w.double().abs()) * (2.25 + n_dq / 4) * u,
                 dk=rows(s * adS.transpose(1, 2) @ q.abs() * (2.25 + fan / 4)) * u,
                 dv=rows(alg["P"].transpose(1, 2) @ do.abs() * (2 + fan / 4)) * u,
-                drcat=(torch.einsum("bqj,bqc->jc", aG, q.abs()) * 3.25 + tab_sum * 1.001) * u)
+                drcat=(torch.einsum("bqj,bqc->jc", aG, q.abs()) * (2.25 + n_dg / 4) + tab_sum * 1.001) * u)
 
 
 def tie_exact_sums(case, alg):
@@ -556,8 +608,9 @@ def tie_shapes():
 
 
 # ------------------------------------------------------------------------------------------------ attention on any token grid
-# csrc/attn_any.hip (pa_attn_any_fwd) is the generic forward with other index arithmetic: the exact cases above carry over to ragged grids,
-# forward only (tests/test_attention_any_exact_gpu.py; conditions and named wrong forwards in tests/test_exact_cases_cpu.py).
+# csrc/attn_any.hip (pa_attn_any_fwd) is the generic forward with other index arithmetic: the exact cases above carry over to ragged grids.
+# This section: the forward (tests/test_attention_any_exact_gpu.py; conditions and named wrong forwards in tests/test_exact_cases_cpu.py);
+# the backward of csrc/attn_any_bwd.hip has the section after it.
 # (B, H, Hp, Wp), each the smallest grid that reaches what it names:
 ANY_RAGGED = [(2, 2, 2, 1),       # L = 2, Wp = 1, one wave live
               (2, 2, 6, 3),       # the Wp < 4 branch, a single partial tile
@@ -721,6 +774,266 @@ def any_algebra(case, fault=None):
             n = min(Lp - L, L)
             out[(b + 1) * L:(b + 1) * L + n] = out[b * L + L - 1]
     return dict(logits=logits, out=out, lse=(m + torch.log(l)).squeeze(-1))
+
+
+# ------------------------------------------------------------------------------------------------ attention on any token grid: the backward
+# csrc/attn_any_bwd.hip (pa_attn_any_bwd): the tie cases on ragged grids (tie_loners lifts L % 4 == 0) and the gather kinds, held to
+# equality by tests/test_attention_any_bwd_exact_gpu.py; conditions, caps and named wrong backwards in tests/test_exact_cases_cpu.py.
+# (B, H, Hp, Wp) of the tie kinds, each the smallest grid that reaches what it names:
+ANY_BWD_TIE_GRIDS = [(2, 2, 12, 3),     # the Wp < 4 stepping branch; L = 36: a partial second tile
+                     (2, 2, 6, 3),      # the same with L = 18: one partial tile
+                     (2, 2, 9, 7),      # 4 <= Wp < 8; L = 63
+                     (2, 2, 10, 5),     # the grid of the model-level fixture
+                     (2, 2, 12, 6),     # L % 4 == 0 and Wp % 4 != 0
+                     (1, 2, 3, 11),     # Wp >= 8; L = 33: one key and one query row in the last tile
+                     (2, 2, 5, 13),     # L = 65: the same, and one idle wave in both kernels
+                     (2, 2, 4, 33),     # Wp > 32
+                     (2, 2, 8, 4),      # aligned: pa_attn_bwd must return the same values
+                     (2, 2, 31, 19)]    # L = 589: 19 tiles, five workgroups.  (In place of (1, 1, 35, 17), which misses its cap: with one
+#                                         sample and one head every kind leaves a key of the last tile, or a tie row of the last query
+#                                         tile, without a non-zero dS; (2, 2, 35, 17) loses tie_near_sparse to the same condition.)
+ANY_BWD_GATHER_ONLY = [(2, 2, 1, 1), (2, 2, 2, 1), (2, 2, 11, 2), (2, 2, 5, 2)]       # too few keys for groups of four, or Wp = 2 once more
+ANY_BWD_ALIGNED = (2, 2, 8, 4)
+ANY_BWD_CHAIN = ("tie_mirror_sparse", (2, 2, 8, 5), 64)      # through the resize adjoint: table lengths 15 -> 45 and 9 -> 27, both dyadic pairs
+# route -> (dtype name, head_dim, the launch counter that must move by one per call, [(B, H, Hp, Wp)])
+ANY_BWD_ROUTES = {"any_bwd_%s_hd%d" % (t, hd): (t, hd, "pa_attn_any_bwd_launches", ANY_BWD_TIE_GRIDS + ANY_BWD_GATHER_ONLY)
+                  for t in ("bf16", "fp32") for hd in (64, 80)}
+# Tie kinds that are NOT exact on a grid, (head dim, grid) -> {kind: the condition of any_bwd_condition_failed that fails}: found by running
+# that function, and asserted -- each entry fails as it says, every kind not listed passes -- by tests/test_exact_cases_cpu.py.  A dense dO
+# meets V magnitudes up to 64 (the fifth field of head dim 80, key rows and columns of the larger grids): some dS or class sum then needs a
+# ninth significant bit.
+_DS, _DK, _ROWS = "bf16-exact dS", "dyadic to 1/32: dk", "last query tile: every tie row has a non-zero dS"
+ANY_BWD_LEFT_OUT = {
+    (64, (2, 2, 12, 3)): {"tie_near": _DK, "tie_near_sparse": _DK},       # L % 4 == 0: the case is today's, amplitude 14 in four-winner rows
+    (64, (2, 2, 9, 7)): {"tie_quarter_sparse": _ROWS},
+    (64, (2, 2, 4, 33)): {"tie_near": _DS, "tie_mirror": _DS},
+    (64, (2, 2, 8, 4)): {"tie_quarter_sparse": _ROWS},
+    (64, (2, 2, 31, 19)): {"tie_near": _DS, "tie_quarter": _DS, "tie_mirror": _DS},
+    (80, (2, 2, 12, 3)): {"tie_near": _DK, "tie_near_sparse": _DK},
+    (80, (2, 2, 9, 7)): {"tie_quarter": _DS, "tie_mirror": _DS, "tie_mirror_sparse": _DS},
+    (80, (2, 2, 10, 5)): {"tie_near": _DS, "tie_quarter": _DS, "tie_mirror": _DS},
+    (80, (2, 2, 12, 6)): {"tie_quarter": _DS, "tie_mirror": _DS},
+    (80, (1, 2, 3, 11)): {"tie_quarter": _DS, "tie_mirror": _DS},
+    (80, (2, 2, 5, 13)): {"tie_near": _DS, "tie_quarter": _DS},
+    (80, (2, 2, 4, 33)): {"tie_near": _DS, "tie_quarter": _DS, "tie_mirror": _DS},
+    (80, (2, 2, 31, 19)): {"tie_near": _DS, "tie_quarter": _DS, "tie_mirror": _DS, "tie_quarter_sparse": _DS},
+}
+# ... and in the fp32 build alone (the bound of any_bwd_fp32_bounds reaches half a quantum somewhere): none
+ANY_BWD_LEFT_OUT_FP32 = {}
+
+
+def any_bwd_kinds(route, grid):
+    """The kinds one route runs on one grid: the gather kinds and below_zero everywhere, and every tie kind that is exact there."""
+    tname, hd = ANY_BWD_ROUTES[route][:2]
+    if grid in ANY_BWD_GATHER_ONLY:
+        return ANY_KINDS
+    out = set(ANY_BWD_LEFT_OUT.get((hd, grid), {})) | (set(ANY_BWD_LEFT_OUT_FP32.get((hd, grid), {})) if tname == "fp32" else set())
+    return ANY_KINDS + tuple(k for k in TIE_KINDS if k not in out)
+
+
+def any_bwd_route_params():
+    """-> [(route, kind, B, H, Hp, Wp)] in the order the GPU tests run them."""
+    return [(route, kind) + grid for route, spec in ANY_BWD_ROUTES.items() for grid in spec[3] for kind in any_bwd_kinds(route, grid)]
+
+
+def any_bwd_shapes():
+    """Every distinct (kind, B, H, Hp, Wp, hd) the any-grid backward tests build, the chain case included."""
+    seen = [(ANY_BWD_CHAIN[0],) + ANY_BWD_CHAIN[1] + (ANY_BWD_CHAIN[2],)]
+    for route, kind, B, H, Hp, Wp in any_bwd_route_params():
+        key = (kind, B, H, Hp, Wp, ANY_BWD_ROUTES[route][1])
+        if key not in seen:
+            seen.append(key)
+    return seen
+
+
+def _bf16_exact(t):
+    return torch.equal(t.float().to(torch.bfloat16).double(), t.double())
+
+
+def any_bwd_fp32_bounds(case, alg):
+    """tie_fp32_bounds for csrc/attn_any_bwd.hip.  The arithmetic per logit is attn_bwd.hip's in the same form: lse = (m + log2 l) * LN2_F
+    (attn_any.hip:177), lse2 = lse * LOG2E_F (attn_any_bwd.hip:74; kernel B reads the same lse2 from the aux tile, :86 and :426),
+    p = exp2(fma(s, scale * log2e, bias) - lse2) (:163, :434), dS = p * (dP - Delta) (:164, :436): dS is 2.25 * 2^-22 of itself off, dV's
+    P 2 * 2^-22, as derived in tie_fp32_bounds.  The term counts differ:
+      bias gradient  one entry of a query's row or column table takes a non-zero dS through at most 5 additions: the partial sum over the
+                     eight keys of a register group (r0 / r1, :179-183; acc, :185-196) holds at most 4 non-zero values -- a row has at most 4
+                     winners -- and is added to the table once (:182, :183, :191, :196); a column entry takes them one by one (:210, :214).
+                     n_dg = 5: (2.25 + 5 / 4) * 2^-22 of the sum of |dS|.
+      dq             4 content products (:229) + 5 + 5 for the two tables + 4 + 4 table products (:288): n_dq = 22.
+      dk dv          the number of queries the key wins (:451, :452), as before.
+      drcat          the same pa_attn_bwd_relpos at B * L token rows (:629): the slab arithmetic of tie_fp32_bounds, which pads the last
+                     slab with zero rows where B * L is no multiple of its length -- the GEMM engine bounds its K tiles by B * L."""
+    return tie_fp32_bounds(case, alg, n_dq=22, n_dg=5)
+
+
+def any_bwd_condition_failed(case, exp, alg, fp32=False):
+    """The conditions a tie case must meet for the any-grid backward to be exact on it -> None, or the name of the first that fails."""
+    B, H, L, hd = case.B, case.H, case.L, case.hd
+    loners = tie_loners(L, case.Wp)
+    last = (L - 1) // 32 * 32
+    logits, dS = alg["logits"], alg["dS"]
+    nwin = (logits == 0).sum(-1)
+    if set(nwin.unique().tolist()) != {1, 2, 4} or not torch.equal(nwin.reshape(B, H, L), exp.nwin) or float(logits.max()) != 0:
+        return "winner counts"
+    if not bool((nwin[:, L - 1] == 4).all()):
+        return "last row has four winners"
+    if float(exp.loser) > -MIN_MARGIN:
+        return "margin"
+    if L > 32 and any(k >= last for k in loners):
+        return "last tile in full groups"
+    alive = [k for k in range(last, L) if k not in loners]
+    if not bool((dS[:, :, alive] != 0).any(1).any(0).all()):
+        return "last tile: every key has a non-zero dS"
+    tie_rows = (nwin[:, last:] > 1)
+    if not bool(((dS[:, last:] != 0).any(-1) | ~tie_rows).any(0).all()):
+        return "last query tile: every tie row has a non-zero dS"
+    if max(tie_exact_sums(case, alg).values()) >= 2 ** 24:
+        return "fp32 sums below 2^24"
+    for name in ("out", "P", "dS", "dG_h", "dG_w"):
+        if not _bf16_exact(alg[name]):
+            return "bf16-exact " + name
+    want = dict(dq=exp.dq, dk=exp.dk, dv=exp.dv, drcat=exp.drcat)
+    for name, t in want.items():
+        if float((t * 32 - (t * 32).round()).abs().max()) > 1e-9 or float(t.abs().max()) >= 2 ** 15:
+            return "dyadic to 1/32: " + name
+    if fp32:
+        bound = any_bwd_fp32_bounds(case, alg)
+        for name, t in want.items():
+            if float(bound[name].max()) >= 0.5 * tie_quantum(t):
+                return "fp32 bound below half a quantum: " + name
+    return None
+
+
+ANY_BWD_FAULTS = ("row_carry_lost_in_group", "half1_offset_no_wrap", "tile_carry_lost", "column_wrap_lost", "tail_keys_alive_dq",
+                  "tail_keys_alive_dkv", "tail_rows_alive_dkv", "aux_row_shift", "dg_emit_off_by_one", "last_tile_skipped_in_table_gradient")
+
+
+def any_bwd_key_walk(L, Hp, Wp, fault=None):
+    """Kernel A's key walk (attn_any_bwd.hip:106-236) restated -> (bh, bw, rh, cw), int64 [ceil(L / 32) * 32] each: per key slot the row
+    entry (clamped to Hp - 1) and column entry of the bias READ, and the row entry (Hp: none, the value is dropped) and column entry
+    (>= Wp: behind the table, lost) that its dS is ADDED to.  Per tile and register group rg the two half-waves of a query hold keys
+    8 rg .. 8 rg + 7; (kh8, kw8) is the row and column of key 8 rg, advanced per tile by 32 / Wp rows and 32 % Wp columns with one carry.
+      read   half g starts 4 g keys behind (kh8, kw8), wrapping with a while loop; Wp >= 4: row entry hh for the keys in front of the
+             crossing and hh + 1 behind it, four consecutive column entries; Wp < 4: (hh, ww) steps per key;
+      rows   half 0: Wp >= 8: r0 = the keys in front of the crossing into row hh, r1 = the rest into row hh + 1 (dropped where hh + 1 = Hp:
+             keys >= L only); Wp < 8: stepping, the sum flushed at every crossing;
+      cols   half 1: the column steps per key and wraps to 0.
+    Faults: row_carry_lost_in_group (r1 into row hh), half1_offset_no_wrap (the read of half 1 keeps row kh8 across the wrap of its + 4
+    columns), tile_carry_lost (the per-tile wrap of kw8 does not bump kh8), column_wrap_lost (the column sum's ww runs on past Wp)."""
+    nt = (L + 31) // 32
+    bh, bw, rh, cw = (torch.empty(nt * 32, dtype=torch.int64) for _ in range(4))
+    kh8, kw8 = [8 * rg // Wp for rg in range(4)], [8 * rg % Wp for rg in range(4)]
+    for j in range(nt):
+        for rg in range(4):
+            for g in (0, 1):
+                hh, ww = kh8[rg], kw8[rg]
+                if g:
+                    ww += 4
+                    while ww >= Wp:
+                        ww -= Wp
+                        hh += 0 if fault == "half1_offset_no_wrap" else 1
+                for t in range(4):
+                    slot = 32 * j + 8 * rg + 4 * g + t
+                    if Wp >= 4:
+                        bh[slot] = min(hh if t < Wp - ww else hh + 1, Hp - 1)
+                        bw[slot] = (ww + t) % Wp                    # (the column part repeats its first three entries behind its end)
+                    else:
+                        bh[slot], bw[slot] = min(hh, Hp - 1), ww
+                        ww += 1
+                        if ww == Wp:
+                            ww, hh = 0, hh + 1
+            hh, ww = kh8[rg], kw8[rg]
+            w2 = ww
+            for t in range(8):
+                slot = 32 * j + 8 * rg + t
+                if Wp >= 8:
+                    if t < Wp - kw8[rg]:
+                        rh[slot] = min(hh, Hp - 1)
+                    else:
+                        rh[slot] = Hp if hh + 1 >= Hp else (min(hh, Hp - 1) if fault == "row_carry_lost_in_group" else hh + 1)
+                else:
+                    rh[slot] = min(hh, Hp - 1)
+                    ww += 1
+                    if ww == Wp:
+                        ww, hh = 0, hh + 1
+                cw[slot] = w2
+                w2 += 1
+                if w2 == Wp and fault != "column_wrap_lost":
+                    w2 = 0
+            kh8[rg] += 32 // Wp
+            kw8[rg] += 32 % Wp
+            if kw8[rg] >= Wp:
+                kw8[rg] -= Wp
+                kh8[rg] += 0 if fault == "tile_carry_lost" else 1
+    return bh, bw, rh, cw
+
+
+def any_bwd_algebra(case, fault=None, base=None):
+    """The any-grid backward written out in fp64 over kernel A's own key walk (any_bwd_key_walk), kernel B and the dG emit
+    (attn_any_bwd.hip:254-270) -> dict(dS [B*H, L, L], tab_h [B*H, L, Hp], tab_w [B*H, L, Wp], dG_h, dG_w, dq, dk, dv [B*L, H*hd], drh, drw,
+    drcat), from the right forward (`base` = tie_algebra(case): lse, Delta, dP).  Without `fault` it is tie_algebra's backward once more;
+    with one it is what a named wrong kernel would return (inf and NaN included: an fp64 exp() overflows later than fp32's).  The walk
+    faults: any_bwd_key_walk.  The others:
+      tail_keys_alive_dq    kernel A, keys >= L keep p = exp2(bias - lse2) with their zeroed K and V rows: dS = -p Delta into the clamped
+                            row entry and a column entry
+      tail_keys_alive_dkv   kernel B computes and stores keys >= L (zeroed K and V, the table rows of key L - 1): their dK and dV rows land
+                            where they point, on the next sample's first rows
+      tail_rows_alive_dkv   kernel B counts the query rows >= L of the last tile as copies of row L - 1
+      aux_row_shift         kernel B reads the lse and Delta of the next query (of the head's first for its last)
+      dg_emit_off_by_one    khh = qh + Hp - r: the emitted dG_h is one table row off, in dQ's bias part and in the table gradient
+      last_tile_skipped_in_table_gradient   the contraction stops at floor(B L / 32) * 32 token rows"""
+    assert fault is None or fault in ANY_BWD_FAULTS
+    B, H, L, hd, Hp, Wp, s = case.B, case.H, case.L, case.hd, case.Hp, case.Wp, case.scale
+    base = base if base is not None else tie_algebra(case)
+    q, k, v = case.qkv.double().reshape(B, L, 3, H, hd).permute(2, 0, 3, 1, 4).reshape(3, B * H, L, hd).unbind(0)
+    do = case.dout.double().reshape(B, L, H, hd).permute(0, 2, 1, 3).reshape(B * H, L, hd)
+    Rh, Rw = case.rel_h.double(), case.rel_w.double()
+    bh, bw, rh, cw = any_bwd_key_walk(L, Hp, Wp, fault)
+    Lp, BH = bh.numel(), B * H
+    pad = torch.zeros(BH, Lp - L, hd, dtype=torch.float64)
+    kx, vx = torch.cat([k, pad], 1), torch.cat([v, pad], 1)
+    qi = torch.arange(L)
+    qh, qw = qi // Wp, qi % Wp
+    lse, delta, Gh, Gw = base["lse"], base["delta"], base["Gh"], base["Gw"]
+    # kernel A
+    ih = (qh[:, None] - bh[None, :] + Hp - 1).expand(BH, L, Lp)
+    iw = (qw[:, None] - bw[None, :] + Wp - 1).expand(BH, L, Lp)
+    logits = (s * q) @ kx.transpose(1, 2) + torch.gather(Gh, 2, ih) + torch.gather(Gw, 2, iw)
+    true = torch.cat([base["logits"], torch.full((BH, L, Lp - L), float("-inf"), dtype=torch.float64)], 2)
+    P = torch.where(logits == true, torch.cat([base["P"], torch.zeros(BH, L, Lp - L, dtype=torch.float64)], 2),
+                    torch.exp(logits - lse[..., None]))
+    alive = torch.arange(Lp) < (Lp if fault == "tail_keys_alive_dq" else L)
+    dS = torch.where(alive[None, None, :], P * (do @ vx.transpose(1, 2) - delta[..., None]), torch.zeros((), dtype=torch.float64))
+    tab_h = torch.zeros(BH, L, Hp + 1, dtype=torch.float64).index_add_(2, rh, dS)[..., :Hp]
+    tab_w = torch.zeros(BH, L, Wp + 8, dtype=torch.float64).index_add_(2, cw, dS)[..., :Wp]
+    khh = qh[:, None] + Hp - 1 - torch.arange(2 * Hp - 1)[None, :] + (1 if fault == "dg_emit_off_by_one" else 0)
+    kww = qw[:, None] + Wp - 1 - torch.arange(2 * Wp - 1)[None, :]
+    dG_h = torch.gather(tab_h, 2, khh.clamp(0, Hp - 1).expand(BH, L, -1)) * ((khh >= 0) & (khh < Hp))[None]
+    dG_w = torch.gather(tab_w, 2, kww.clamp(0, Wp - 1).expand(BH, L, -1)) * ((kww >= 0) & (kww < Wp))[None]
+    dq = s * dS @ kx + dG_h @ Rh + dG_w @ Rw
+    tok = (torch.arange(B)[:, None, None] * L + qi[None, None, :]).expand(B, H, L).reshape(BH, L)
+    live = (tok < (B * L // 32 * 32 if fault == "last_tile_skipped_in_table_gradient" else B * L)).double()[..., None]
+    drh, drw = torch.einsum("bqj,bqc->jc", dG_h * live, q), torch.einsum("bqj,bqc->jc", dG_w * live, q)
+    # kernel B: each key's own (row, column), lse2 and Delta from the aux tile
+    lse_b, delta_b = (lse.roll(-1, 1), delta.roll(-1, 1)) if fault == "aux_row_shift" else (lse, delta)
+    Pb = base["P"] * torch.exp(lse - lse_b)[..., None]
+    dSb = Pb * (base["dP"] - delta_b[..., None])
+    dk, dv = s * dSb.transpose(1, 2) @ q, Pb.transpose(1, 2) @ do
+    if fault == "tail_rows_alive_dkv":
+        dk = dk + (Lp - L) * s * dSb[:, L - 1, :, None] * q[:, L - 1, None, :]
+        dv = dv + (Lp - L) * Pb[:, L - 1, :, None] * do[:, L - 1, None, :]
+    rows = lambda t: t.reshape(B, H, L, hd).permute(0, 2, 1, 3).reshape(B * L, H * hd).contiguous()
+    dk, dv = rows(dk), rows(dv)
+    if fault == "tail_keys_alive_dkv" and Lp > L:
+        ihl, iwl = qh + Hp - 1 - (L - 1) // Wp, qw + Wp - 1 - (L - 1) % Wp
+        p = torch.exp(Gh[:, qi, ihl] + Gw[:, qi, iwl] - lse)                                   # [BH, L]
+        pk, pv = s * torch.einsum("bq,bqc->bc", -p * delta, q), torch.einsum("bq,bqc->bc", p, do)
+        n = min(Lp - L, L)
+        for b in range(B - 1):
+            dk.reshape(B, L, H, hd)[b + 1, :n] = pk.reshape(B, H, hd)[b][None]
+            dv.reshape(B, L, H, hd)[b + 1, :n] = pv.reshape(B, H, hd)[b][None]
+    return dict(dS=dS[..., :L], tab_h=tab_h, tab_w=tab_w, dG_h=dG_h, dG_w=dG_w, dq=rows(dq), dk=dk, dv=dv, drh=drh, drw=drw,
+                drcat=torch.cat([drh, drw], 0))
 
 
 # ------------------------------------------------------------------------------------------------ 3x3 convolution

@@ -59,6 +59,24 @@ def test_resize_adjoint_statement_is_torch_float64_autograd(n_src, n_dst):
     assert float((got - want).abs().max()) <= 1e-13 * float(want.abs().max())
 
 
+def test_the_exact_chain_case_is_exact_through_the_resize_adjoint():
+    """tests/test_attention_any_bwd_exact_gpu.py::test_exact_chain_through_the_resize_adjoint rests on this: the exact table gradient of its
+    tie case on 8 x 5 (lengths 15 and 9, multiples of 1/32) through the adjoint to the stored lengths 45 and 27 -- CPU torch's float32
+    autograd of the resize equals its float64 autograd and the statement, bit for bit."""
+    from tests import exact_cases as X
+    kind, grid, hd = X.ANY_BWD_CHAIN
+    case, exp = X.any_case(kind, *grid, hd)
+    nh, nw = 2 * case.Hp - 1, 2 * case.Wp - 1
+    assert (nh, nw) == (15, 9) and (45, 15) in DYADIC_PAIRS and (27, 9) in DYADIC_PAIRS
+    assert X.any_bwd_condition_failed(case, exp, X.tie_algebra(case), fp32=True) is None
+    assert torch.equal(exp.drcat.float().double(), exp.drcat)
+    for g, n_src in ((exp.drcat[:nh], 45), (exp.drcat[nh:], 27)):
+        assert float(g.abs().max()) > 0
+        want = resize_adjoint_statement(g, n_src)
+        assert torch.equal(torch_resize_grad(g, n_src, torch.float64), want)
+        assert torch.equal(torch_resize_grad(g.float(), n_src, torch.float32).double(), want)
+
+
 @pytest.mark.parametrize("n_src,n_dst", DYADIC_PAIRS + [(15, 5)])
 def test_dyadic_pairs_with_integer_gradients_are_exact_in_float32(n_src, n_dst):
     """The condition under which tests/test_any_size_grad_gpu.py may demand torch.equal of the kernel: on these length pairs, with integer

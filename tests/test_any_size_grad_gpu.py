@@ -49,7 +49,61 @@ GRIDS = [(2, 1, 1, 64),          # a single key: dS = 0
          (2, 8, 4, 64),          # an aligned grid through the any-grid kernel
          (2, 35, 17, 64),        # many tiles
          (1, 70, 35, 64),        # the evaluation recipe's grid
-         (2, 5, 2, 80), (2, 3, 11, 80), (2, 10, 5, 80)]
+         (2, 5, 2, 80), (2, 3, 11, 80), (2, 10, 5, 80),
+         # every wave count of kernel A (dq_kernel_waves; thin tall grids, L <= 250): S = Hp + Wp
+         (1, 108, 2, 64),        # S = 110: the last four-wave grid in fp32
+         (1, 120, 2, 64),        # S = 122: fp32 takes three waves
+         (1, 124, 2, 64),        # S = 126, the largest there is: four waves in bf16, three in fp32
+         (1, 90, 2, 80),         # S = 92: the last four-wave grid in fp32 at head dim 80
+         (1, 120, 2, 80),        # S = 122: fp32 takes three waves
+         (1, 122, 2, 80),        # S = 124: the last four-wave grid in bf16 at head dim 80; fp32 is refused
+         (1, 124, 2, 80),        # S = 126: bf16 takes three waves; fp32 is refused
+         (1, 70, 35, 80)]        # the evaluation recipe's grid at head dim 80: three waves in fp32
+
+
+def dq_kernel_waves(T, hd, Hp, Wp):
+    """Waves per workgroup of the dQ kernel (kernel A), restated from include/painter_anysize_grad.h: the most of 4, 3 or -- head dim 64
+    only -- 2 with 2 * stage + NW * max(128 * (TS + TG), 32 * hd * e) <= 160 KiB, TS = (Hp + Wp + 3) | 1, TG = (Hp + Wp) | 1 (the per-wave
+    region rounded up to 16 bytes), stage = 96 * hd * e at head dim 64 and 32 * (2 * (80 * e + 16) + 96 * e) at 80; 0 where none fits
+    or Hp + Wp > 126 (the dK / dV kernel's table tile): the grid is refused.  By S = Hp + Wp this gives
+        bf16, head dim 64   S <= 126: 4
+        fp32, head dim 64   S <= 110: 4   111 - 126: 3
+        bf16, head dim 80   S <= 124: 4   125 - 126: 3
+        fp32, head dim 80   S <=  92: 4    93 - 123: 3   124 - 126: refused
+    (test_dq_kernel_wave_counts).  TWO WAVES ARE UNREACHABLE: at head dim 64 three waves fit up to the S = 126 that kernel B allows, in
+    both builds, so the NW = 2 instantiation is never launched."""
+    e, S = (2 if T == BF16 else 4), Hp + Wp
+    per_wave = (max(128 * (((S + 3) | 1) + (S | 1)), 32 * hd * e) + 15) // 16 * 16
+    stage = 96 * hd * e if hd == 64 else 32 * (2 * (80 * e + 16) + 96 * e)
+    if S > 126:
+        return 0
+    return next((nw for nw in ((4, 3, 2) if hd == 64 else (4, 3)) if 2 * stage + nw * per_wave <= 160 * 1024), 0)
+
+
+def test_dq_kernel_wave_counts():
+    """The thresholds of dq_kernel_waves' docstring, the library's refusals at every S (it refuses exactly where no wave count fits), and
+    what GRIDS reaches: per (dtype, head dim) the largest four-wave S and, where there is one, a three-wave launch."""
+    runs = {}
+    for T in (BF16, F32):
+        for hd in (64, 80):
+            for S in range(3, 130):
+                w = dq_kernel_waves(T, hd, S - 2, 2)
+                assert dq_kernel_waves(T, hd, 2, S - 2) == w and dq_kernel_waves(T, hd, S // 2, S - S // 2) == w
+                assert (ops_anysize.lib.pa_attn_any_bwd_workspace_bytes(ops.code(T), 1, (S - 2) * 2, 2, S - 2, 2, hd) > 0) == (w > 0), (T, hd, S)
+                runs.setdefault((T, hd, w), []).append(S)
+    span = {k: (min(v), max(v)) for k, v in runs.items()}
+    assert span == {(BF16, 64, 4): (3, 126), (BF16, 64, 0): (127, 129),
+                    (F32, 64, 4): (3, 110), (F32, 64, 3): (111, 126), (F32, 64, 0): (127, 129),
+                    (BF16, 80, 4): (3, 124), (BF16, 80, 3): (125, 126), (BF16, 80, 0): (127, 129),
+                    (F32, 80, 4): (3, 92), (F32, 80, 3): (93, 123), (F32, 80, 0): (124, 129)}, span
+    assert not any(k[2] == 2 for k in span)                                # two waves: unreachable
+    reached = {(T, hd, dq_kernel_waves(T, hd, Hp, Wp), Hp + Wp) for _, Hp, Wp, hd in GRIDS for T in (BF16, F32)}
+    for (T, hd, w), (lo, hi) in span.items():
+        if w == 4:
+            assert (T, hd, 4, hi) in reached, (T, hd, hi)                  # the largest four-wave S
+        elif w == 3:
+            assert any(r[:3] == (T, hd, 3) for r in reached), (T, hd)      # a three-wave launch
+    assert dq_kernel_waves(F32, 80, 70, 35) == 3 and dq_kernel_waves(F32, 64, 70, 35) == 4 and dq_kernel_waves(F32, 80, 124, 2) == 0
 
 
 @pytest.mark.parametrize("T", [F32, BF16], ids=["fp32", "bf16"])
@@ -58,6 +112,22 @@ def test_attn_any_bwd_vs_float64_autograd(T, B, Hp, Wp, hd):
     H, L = 2, Hp * Wp
     nh, nw = 2 * Hp - 1, 2 * Wp - 1
     scale = hd ** -0.5
+    if dq_kernel_waves(T, hd, Hp, Wp) == 0:
+        # a grid whose tables fit LDS in the other build only: refused before any launch, workspace bytes 0
+        assert ops_anysize.lib.pa_attn_any_bwd_workspace_bytes(ops.code(T), B, L, H, Hp, Wp, hd) == 0
+        assert ops_anysize.lib.pa_attn_any_bwd_workspace_bytes(ops.code(BF16), B, L, H, Hp, Wp, hd) > 0
+        qkv, rcat, rcatT, dout, out, lse = operands(T, B, H, Hp, Wp, hd)     # (the forward takes the grid)
+        n0 = ops_anysize.attn_any_bwd_launches()
+        with pytest.raises(RuntimeError, match="do not fit LDS"):
+            ops_anysize.attn_any_bwd(qkv, rcat, rcatT, out, dout, lse, B, L, H, Hp, Wp, scale)
+        dq = torch.full_like(qkv, 7.0)
+        ws = torch.empty(1 << 20, dtype=torch.uint8, device="cuda")
+        err = ops_anysize.lib.pa_attn_any_bwd(ops.code(T), qkv.data_ptr(), qkv.stride(0), rcat.data_ptr(), rcatT.data_ptr(), out.data_ptr(),
+                                              out.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(), dq.data_ptr(), 0, ws.data_ptr(), B, L,
+                                              H, Hp, Wp, hd, scale, ops.stream())
+        torch.cuda.synchronize()
+        assert err == 1 and ops_anysize.attn_any_bwd_launches() == n0 and bool((dq == 7.0).all())
+        return
     qkv, rcat, rcatT, dout, out, lse = operands(T, B, H, Hp, Wp, hd)
     n0, f0, c0 = ops_anysize.attn_any_bwd_launches(), ops_anysize.attn_any_launches(), ops.attn_launch_counts()
     dqkv, drcat = ops_anysize.attn_any_bwd(qkv, rcat, rcatT, out, dout, lse, B, L, H, Hp, Wp, scale)
@@ -85,7 +155,8 @@ def test_attn_any_bwd_vs_float64_autograd(T, B, Hp, Wp, hd):
     errs = dict(dq=err(dqkv[:, :D], gq[:, :D], L == 1, whole_q), dk=err(dqkv[:, D:2 * D], gq[:, D:2 * D], L == 1, whole_q),
                 dv=err(dqkv[:, 2 * D:], gq[:, 2 * D:], False, whole_q), drh=err(drcat[:nh], rh64.grad, Hp == 1 or L == 1, whole_r),
                 drw=err(drcat[nh:nh + nw], rw64.grad, Wp == 1, whole_r))
-    print("attn_any_bwd %s B=%d %dx%d hd=%d: %s" % (str(T)[6:], B, Hp, Wp, hd, " ".join("%s %.2e" % kv for kv in errs.items())))
+    print("attn_any_bwd %s B=%d %dx%d hd=%d (%d waves in the dQ kernel): %s"
+          % (str(T)[6:], B, Hp, Wp, hd, dq_kernel_waves(T, hd, Hp, Wp), " ".join("%s %.2e" % kv for kv in errs.items())))
     assert max(errs.values()) < BWD_GATE[T], errs
     assert torch.isfinite(dqkv.float()).all() and torch.isfinite(drcat).all()
     assert not drcat[nh + nw:].any()                                      # the pad rows are exact zeros

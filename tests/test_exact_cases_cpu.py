@@ -456,3 +456,256 @@ ANY_BIAS_SHAPES = [s for s in ANY_SHAPES if s[0] == "bias_rank" and s not in ATT
 def test_bias_rank_tables_decide_alone_on_ragged_grids(kind, B, H, Hp, Wp, hd):
     """test_bias_rank_tables_decide_alone on the grids only the any-grid kernel takes: one right (kh, kw) per query, margin a multiple of 256."""
     test_bias_rank_tables_decide_alone(kind, B, H, Hp, Wp, hd)
+
+
+# ------------------------------------------------------------------------------------------------ attention on any token grid: the backward
+ANY_BWD_SHAPES = X.any_bwd_shapes()
+ANY_BWD_TIE_SHAPES = [s for s in ANY_BWD_SHAPES if s[0] in X.TIE_KINDS]
+ANY_BWD_NEW_GATHER_SHAPES = [s for s in ANY_BWD_SHAPES if s[0] not in X.TIE_KINDS and s not in ANY_SHAPES]
+_id6 = lambda s: "%s-%dx%dx%dx%d-hd%d" % s
+# sha256 over the bytes of qkv, rel_h, rel_w and dout of three tie cases with L % 4 == 0, one per placement, taken before tie_case admitted
+# ragged grids
+TIE_DIGESTS = {("tie_near", 2, 2, 8, 4, 64): "099de30c1da1bdd4c83087575973174fa52e72473069f2238c81d452f446cde0",
+               ("tie_quarter_sparse", 2, 2, 12, 6, 80): "cd8df4ddc2cbde662a66107f93758c4f120e62bae434356e38d0e00466d7d189",
+               ("tie_mirror", 2, 2, 8, 28, 64): "c3246b28191afaa61ac94c2cb8783f4cffe86a44322be48cbb31404589abf536"}
+
+
+@pytest.mark.parametrize("shape", sorted(TIE_DIGESTS), ids=_id6)
+def test_tie_cases_with_L_a_multiple_of_four_are_unchanged(shape):
+    """Lifting L % 4 == 0 from tie_case left the same seeds and the same draws where L % 4 == 0: the existing tie tests and their recorded
+    logs keep their meaning."""
+    import hashlib
+    case, _ = X.tie_attn_case(*shape)
+    h = hashlib.sha256()
+    for name in ("qkv", "rel_h", "rel_w", "dout"):
+        h.update(getattr(case, name).contiguous().numpy().tobytes())
+    assert h.hexdigest() == TIE_DIGESTS[shape]
+    assert X.tie_loners(case.L, case.Wp) == [] and torch.equal(X.tie_members("near", 32), (4 * torch.arange(8)[:, None] + 2 + torch.arange(4)) % 32)
+
+
+@pytest.mark.parametrize("Hp,Wp", sorted({s[3:5] for s in ANY_BWD_SHAPES} | {(5, 2), (7, 1), (4, 3), (70, 35)}), ids=lambda v: str(v))
+def test_loners_and_groups_on_any_grid(Hp, Wp):
+    """tie_loners: L % 4 keys, valid, distinct, off key 0 and key L - 1, outside the last 32-key tile wherever there is a second tile, and
+    inside neither border key row nor border tile where the grid has such keys; the groups of four cover every other key exactly once."""
+    L = Hp * Wp
+    if L < 4:                             # (5 x 2 gave a negative key in the first draft of this; 1 x 1 and 2 x 1 have no room at all)
+        with pytest.raises(ValueError, match="gather kinds"):
+            X.tie_loners(L, Wp)
+        return
+    loners = X.tie_loners(L, Wp)
+    assert len(loners) == len(set(loners)) == L % 4 and all(0 < k < L - 1 for k in loners)
+    last = (L - 1) // 32 * 32
+    if L > 32:
+        assert all(k < last for k in loners)
+    if len([k for k in range(L) if Wp <= k < L - Wp and 32 <= k < last]) >= L % 4:
+        assert all(Wp <= k < L - Wp and 32 <= k < last for k in loners)
+    if L >= 4:
+        for placement in X.TIE_PLACEMENTS:
+            m = X.tie_members(placement, L, Wp)
+            assert m.shape == (L // 4, 4) and sorted(m.flatten().tolist() + loners) == list(range(L))
+        assert L < 8 or {L - 2, L - 1, 0, 1} == set(X.tie_members("near", L, Wp)[-1].tolist())      # the last keys pair up with the first
+
+
+def test_the_any_grid_backward_parametrisation_covers_what_it_says():
+    """Four routes on the backward's own launch counter; the gather kinds and below_zero on every grid; the tie kinds on the ten tie grids,
+    minus the kinds ANY_BWD_LEFT_OUT names; and the caps: every tie grid keeps a dense kind at head dim 64 or all three sparse placements,
+    every route all three placements on at least three ragged grids."""
+    params = X.any_bwd_route_params()
+    assert set(X.ANY_BWD_ROUTES) == {"any_bwd_%s_hd%d" % (t, hd) for t in ("bf16", "fp32") for hd in (64, 80)}
+    assert set(X.ANY_BWD_TIE_GRIDS) == {(2, 2, 12, 3), (2, 2, 6, 3), (2, 2, 9, 7), (2, 2, 10, 5), (2, 2, 12, 6), (1, 2, 3, 11), (2, 2, 5, 13),
+                                        (2, 2, 4, 33), (2, 2, 8, 4), (2, 2, 31, 19)}
+    assert X.ANY_BWD_GATHER_ONLY == [(2, 2, 1, 1), (2, 2, 2, 1), (2, 2, 11, 2), (2, 2, 5, 2)]
+    assert {g[2] * g[3] for g in X.ANY_BWD_TIE_GRIDS} >= {18, 33, 36, 50, 63, 65} and max(g[2] * g[3] for g in X.ANY_BWD_TIE_GRIDS) == 589
+    assert {len(X.tie_loners(g[2] * g[3], g[3])) for g in X.ANY_BWD_TIE_GRIDS} == {0, 1, 2, 3}
+    assert all(ops_takes(g) == (g == X.ANY_BWD_ALIGNED) for g in X.ANY_BWD_TIE_GRIDS + X.ANY_BWD_GATHER_ONLY)
+    placements = lambda kinds: {k.replace("tie_", "").replace("_sparse", "") for k in kinds if k in X.TIE_KINDS}
+    for route, (tname, hd, counter, grids) in X.ANY_BWD_ROUTES.items():
+        assert counter == "pa_attn_any_bwd_launches" and route == "any_bwd_%s_hd%d" % (tname, hd)
+        assert grids == X.ANY_BWD_TIE_GRIDS + X.ANY_BWD_GATHER_ONLY
+        full = 0
+        for grid in grids:
+            kinds = [p[1] for p in params if p[0] == route and p[2:] == grid]
+            assert len(kinds) == len(set(kinds)) and set(X.ANY_KINDS) <= set(kinds)
+            if grid in X.ANY_BWD_GATHER_ONLY:
+                assert set(kinds) == set(X.ANY_KINDS)
+                continue
+            left = dict(X.ANY_BWD_LEFT_OUT.get((hd, grid), {}), **(X.ANY_BWD_LEFT_OUT_FP32.get((hd, grid), {}) if tname == "fp32" else {}))
+            assert set(kinds) == set(X.ANY_KINDS) | (set(X.TIE_KINDS) - set(left)) and all(left.values())
+            full += placements(kinds) == set(X.TIE_PLACEMENTS) and not ops_takes(grid)
+            if hd == 64:                  # the cap of a grid
+                assert set(kinds) & set(X.TIE_KINDS[:3]) or set(X.TIE_KINDS[3:]) <= set(kinds), (route, grid, kinds)
+        assert full >= 3, (route, full)   # the cap of a route
+    kind, grid, hd = X.ANY_BWD_CHAIN
+    assert (2 * grid[2] - 1, 2 * grid[3] - 1) == (15, 9) and kind in X.TIE_KINDS and len(ANY_BWD_SHAPES) == len(set(ANY_BWD_SHAPES))
+
+
+@pytest.mark.parametrize("Hp,Wp", sorted({s[3:5] for s in ANY_BWD_SHAPES}), ids=lambda v: str(v))
+def test_any_bwd_key_walk_without_a_fault_is_row_major(Hp, Wp):
+    """Kernel A's walk restated (exact_cases.any_bwd_key_walk) reads and adds key k at (k // Wp, k % Wp); each walk fault moves some key
+    < L, or the grid has no key that could show it."""
+    L = Hp * Wp
+    bh, bw, rh, cw = X.any_bwd_key_walk(L, Hp, Wp)
+    k = torch.arange(bh.numel())
+    live = k < L
+    assert torch.equal(bh, (k // Wp).clamp_max(Hp - 1)) and torch.equal(bw, k % Wp) and torch.equal(cw, k % Wp)
+    assert torch.equal(rh[live], (k // Wp)[live]) and bool((rh[~live] >= Hp - 1).all())
+    moved = {}
+    for fault in ("row_carry_lost_in_group", "half1_offset_no_wrap", "tile_carry_lost", "column_wrap_lost"):
+        f = X.any_bwd_key_walk(L, Hp, Wp, fault)
+        moved[fault] = int(sum(((a != b) & live).sum() for a, b in zip(f, (bh, bw, rh, cw))))
+    crossing8 = (k // Wp != (k - k % 8) // Wp) & live
+    assert moved["row_carry_lost_in_group"] == (int(crossing8.sum()) if Wp >= 8 else 0)
+    assert (moved["column_wrap_lost"] > 0) == (L > 1 and bool(crossing8.any() or Wp < 8 and L > Wp))
+    grp = torch.arange(bh.numel() // 8)                                      # (tile, register group): a carry its first key has seen by then
+    first = 32 * (grp // 4) + 8 * (grp % 4)
+    carried = (first // Wp != (8 * (grp % 4)) // Wp + (grp // 4) * (32 // Wp)) & (first < L)
+    assert (moved["tile_carry_lost"] > 0) == bool(carried.any()) and (not carried.any() or (32 % Wp != 0 and L > 32))
+    print("%dx%d: key slots each walk fault moves: %s" % (Hp, Wp, moved))
+
+
+@functools.lru_cache(maxsize=None)
+def any_bwd_base(shape):
+    """-> (case, expectation, tie_algebra, {name: expected tensor}, {name: quantum}, {name: fp32 bound}) of one built shape."""
+    case, exp = X.any_case(*shape)
+    alg = X.tie_algebra(case)
+    if shape[0] in X.TIE_KINDS:
+        want = dict(dq=exp.dq, dk=exp.dk, dv=exp.dv, drcat=exp.drcat)
+        return case, exp, alg, want, {n: X.tie_quantum(t) for n, t in want.items()}, X.any_bwd_fp32_bounds(case, alg)
+    zero = torch.zeros_like(exp.dv, dtype=torch.float64)
+    want = dict(dq=zero, dk=zero, dv=exp.dv.double(), drcat=torch.zeros(2 * case.Hp + 2 * case.Wp - 2, case.hd, dtype=torch.float64))
+    bound = dict(dq=zero, dk=zero, dv=X.dv_fp32_bound(case, exp), drcat=want["drcat"])
+    return case, exp, alg, want, dict.fromkeys(want, 1.0), bound
+
+
+@pytest.mark.parametrize("shape", ANY_BWD_TIE_SHAPES, ids=_id6)
+def test_any_bwd_tie_case_conditions(shape):
+    """What tests/test_attention_any_bwd_exact_gpu.py rests on, for every tie case it builds: the conditions of
+    test_tie_case_conditions_and_sensitivity as exact_cases.any_bwd_condition_failed states them for ragged grids (winner counts from the
+    logits with 1, 2 and 4 present, four winners in the last row, the last key tile in full groups with a non-zero dS in every key, a
+    non-zero dS in every tie row of the last query tile, the margin, fp32 sums below 2^24 units, out / P / dS / dG bf16-exact, expectations
+    dyadic to 1/32, the fp32 bound below half a quantum), and here: integer operands, zero bias tables in the forward, Delta exact as
+    hi + lo, the non-zero fractions, autograd == the hand algebra == the algebra over the kernel's own walk."""
+    kind, B, H, Hp, Wp, hd = shape
+    case, exp, alg, want, quanta, bound = any_bwd_base(shape)
+    L, nh = Hp * Wp, 2 * Hp - 1
+    assert X.any_bwd_condition_failed(case, exp, alg, fp32=True) is None
+    assert torch.equal(exp.nwin, X.tie_winner_count(L)[None, None].expand(B, H, L))          # the loners went to one-winner rows
+    offset = X.tie_layout(hd)[4]
+    for name in ("qkv", "rel_h", "rel_w", "dout"):
+        assert bf16_exact_integers(getattr(case, name)), name
+    q = case.qkv.reshape(B, L, 3, H, hd)[:, :, 0]
+    assert bf16_exact(q * case.scale) and case.scale == 0.125
+    assert float(alg["Gh"].abs().max()) == 0 and float(alg["Gw"].abs().max()) == 0
+    assert float(case.rel_h.abs().sum()) == float(case.rel_h[:, offset].sum()) == nh * (nh + 1) / 2
+    assert bf16_hi_lo_exact(alg["delta"]) and torch.equal(exp.lse, torch.log(exp.nwin.double()).reshape(B * H, L))
+    density = float((case.dout != 0).float().mean())
+    assert abs(density - (1 / 16 if kind.endswith("sparse") else 2 / 3)) < 0.02
+    for name, a, b in (("out", exp.out, alg["out"]), ("dq", exp.dq, alg["dq"]), ("dk", exp.dk, alg["dk"]), ("dv", exp.dv, alg["dv"]),
+                       ("drh", exp.drcat[:nh], alg["drh"]), ("drw", exp.drcat[nh:], alg["drw"])):
+        assert float((a - b).abs().max()) < 1e-9, name
+    # the non-zero fractions, as today (a loner's dK row is zero: at most 3 of L keys)
+    off_dq = exp.dq.reshape(B * L, H, hd)[:, :, offset]
+    assert bf16_exact(exp.out) and float((exp.dq != 0).double().mean()) > 0.02 and float((off_dq != 0).double().mean()) > 0.3
+    assert float((exp.dk != 0).double().mean()) > 0.4 and float((exp.drcat[:nh].abs().sum(1) != 0).double().mean()) > 0.5
+    if "quarter" not in kind:
+        assert float((exp.drcat[nh:].abs().sum(1) != 0).double().mean()) > 0.5
+    assert min(quanta.values()) >= 1 / 32
+    # the kernel's own walk, without a fault, is the hand algebra: dS, the tables, dG, dq, dk, dv and both table gradients
+    walk = X.any_bwd_algebra(case, base=alg)
+    for name in ("dS", "dG_h", "dG_w", "dq", "dk", "dv", "drh", "drw"):
+        assert torch.equal(walk[name], alg[name]), name
+    key = torch.arange(L)
+    for tab, idx, n in ((walk["tab_h"], key // Wp, Hp), (walk["tab_w"], key % Wp, Wp)):
+        assert torch.equal(tab, torch.zeros(B * H, L, n, dtype=torch.float64).index_add_(2, idx, alg["dS"]))
+    ratio = {n: float(bound[n].max()) / quanta[n] for n in bound}
+    print("%s %dx%dx%dx%d hd%d: loners %s; quanta %s; fp32 bound / quantum %s; largest fp32 sum 2^%.1f units"
+          % (shape + (X.tie_loners(L, Wp), quanta, {n: "%.3f" % r for n, r in ratio.items()},
+                      torch.log2(torch.tensor(max(X.tie_exact_sums(case, alg).values()))).item())))
+    assert max(ratio.values()) < 0.5, ratio
+
+
+LEFT_OUT = [(kind,) + grid + (hd,) for (hd, grid), kinds in list(X.ANY_BWD_LEFT_OUT.items()) + list(X.ANY_BWD_LEFT_OUT_FP32.items()) for kind in kinds]
+
+
+@pytest.mark.parametrize("shape", LEFT_OUT, ids=_id6)
+def test_every_kind_left_out_fails_the_condition_it_is_listed_with(shape):
+    kind, B, H, Hp, Wp, hd = shape
+    case, exp = X.tie_attn_case(*shape)
+    said = dict(X.ANY_BWD_LEFT_OUT.get((hd, (B, H, Hp, Wp)), {}), **X.ANY_BWD_LEFT_OUT_FP32.get((hd, (B, H, Hp, Wp)), {}))[kind]
+    assert X.any_bwd_condition_failed(case, exp, X.tie_algebra(case), fp32=True) == said
+
+
+@pytest.mark.parametrize("shape", ANY_BWD_NEW_GATHER_SHAPES, ids=_id6)
+def test_any_bwd_gather_case_conditions_on_the_new_grids(shape):
+    """The gather kinds on the grids tests/test_attention_any_exact_gpu.py does not run (the others: test_any_grid_case_conditions): the
+    margin, integer operands, an integer dV whose fp32 bound stays below 1/2, and a backward that is zero but for dV in the walk algebra."""
+    kind, B, H, Hp, Wp, hd = shape
+    case, exp, alg, want, _, bound = any_bwd_base(shape)
+    L = Hp * Wp
+    assert exp.margin.shape == (B, H, L) and float(exp.margin.min()) >= X.MIN_MARGIN, float(exp.margin.min())
+    for name in ("qkv", "rel_h", "rel_w", "dout"):
+        assert bf16_exact_integers(getattr(case, name)), name
+    assert bf16_exact_integers(exp.out) and bf16_exact_integers(exp.dv.float()) and float(bound["dv"].max()) < 0.5
+    assert torch.equal(exp.lse.reshape(B, H, L), exp.top) and torch.equal(exp.top, exp.top.round()) and float(exp.top.abs().max()) < 2 ** 24
+    walk = X.any_bwd_algebra(case, base=alg)
+    for name in ("dq", "dk", "drcat"):
+        assert float(walk[name].abs().max()) < 1e-50, name
+    assert float((walk["dv"] - want["dv"]).abs().max()) < 1e-50
+    if kind == "below_zero":
+        assert float(exp.top.max()) <= -150
+
+
+def _fault_effect(shape, fault):
+    """-> (largest move in quanta, the same in units of the fp32 bound at the element moved most, the max-norm measure of the tolerance
+    test) of one wrong backward on one built case; non-finite values count as infinitely far."""
+    case, exp, alg, want, quanta, bound = any_bwd_base(shape)
+    got = X.any_bwd_algebra(case, fault, base=alg)
+    nh = 2 * case.Hp - 1
+    seen = beyond = measure = 0.0
+    for n in want:
+        diff = torch.nan_to_num((got[n] - want[n]).abs(), nan=float("inf"), posinf=float("inf"))
+        top = float(diff.max())
+        if top < quanta[n]:
+            continue
+        seen = max(seen, top / quanta[n])
+        at = int(diff.argmax())
+        b = float(bound[n].flatten()[at])
+        beyond = max(beyond, top / b if b > 0 else float("inf"))
+    whole = max(float(want[n].abs().max()) for n in ("dq", "dk", "dv"))
+    parts = [(got[n], want[n], whole) for n in ("dq", "dk", "dv")]
+    whole_r = float(want["drcat"].abs().max())
+    parts += [(got["drcat"][:nh], want["drcat"][:nh], whole_r), (got["drcat"][nh:], want["drcat"][nh:], whole_r)]
+    for g, w, wh in parts:
+        d = float(torch.nan_to_num((g - w).abs(), nan=float("inf"), posinf=float("inf")).max())
+        scale = float(w.abs().max()) or wh
+        measure = max(measure, d / scale if scale else (float("inf") if d else 0.0))
+    return seen, beyond, measure
+
+
+# the shapes the sensitivity test walks: every tie case, and the two gather kinds whose logits a wrong walk or a live tail key can move
+FAULT_SHAPES = ANY_BWD_TIE_SHAPES + [s for s in ANY_BWD_SHAPES if s[0] in ("bias_rank", "below_zero")]
+
+
+@pytest.mark.parametrize("fault", X.ANY_BWD_FAULTS)
+def test_every_named_wrong_backward_is_caught(fault):
+    """Each wrong backward of exact_cases.any_bwd_algebra moves some element of dq, dk, dv or drcat of some built case by at least one
+    quantum, and by at least 16 times the fp32 build's bound at that element (every built case runs in both builds).  A condition, not a
+    measurement: a fault no case sees wants another case.  Printed per fault: how many cases catch it, and the max-norm measure
+    (max|a - b| / max|b| per tensor, the tolerance test's, gates 5e-5 fp32 and 1.6e-2 bf16) the fault has on the cases that catch it --
+    where the smallest is below the gate, a case of that size would have hidden it."""
+    caught = []
+    for s in FAULT_SHAPES:
+        seen, beyond, measure = _fault_effect(s, fault)
+        if seen >= 1 and beyond >= 16:
+            caught.append((measure, seen, s))
+    assert caught, fault
+    tie = [c for c in caught if c[2][0] in X.TIE_KINDS]
+    lo, hi = min(caught), max(caught)
+    print("%s: caught by %d of %d cases (%d tie cases); old measure between %.2g (%s, %.0f quanta) and %.2g (%s); below the bf16 gate 1.6e-2 on %d"
+          % (fault, len(caught), len(FAULT_SHAPES), len(tie), lo[0], _id6(lo[2]), lo[1], hi[0], _id6(hi[2]), sum(c[0] < OLD_GATE_BF16 for c in caught)))
+    if fault == "half1_offset_no_wrap":
+        assert all(c[2][0] == "bias_rank" for c in caught)         # the tie cases' bias tables are zero in the forward: the read cannot show
+    else:
+        assert tie, fault
+    if fault in ("row_carry_lost_in_group", "column_wrap_lost", "tile_carry_lost", "dg_emit_off_by_one", "aux_row_shift"):
+        assert {c[2][5] for c in caught} == {64, 80}
