@@ -112,8 +112,13 @@ def gelu_aux_dtype(T):
 
 
 def gelu_aux_decode(aux):
-    """uint8 code -> gelu' (float32), as the fc2 data-gradient epilogue decodes it (include/painter_hip.h, PA_EPI_BIAS_GELU); tests / tools."""
-    return aux.to(torch.float32) * (G8_RANGE / 255.0) - G8_OFF
+    """uint8 code -> gelu' (float32), the BITS the fc2 data-gradient epilogue decodes it to (csrc/gemm.hip: g8_value(q) =
+    fmaf((float)q, 1.26f / 255.f, -0.13f); include/painter_hip.h, PA_EPI_BIAS_GELU); tests / tools.
+    q times the fp32 quotient minus the fp32 offset is exact in fp64, so one rounding of that to fp32 is the fused multiply-add; an fp32
+    multiply followed by an fp32 subtraction is another number in the last bit for 55 of the 256 codes."""
+    one = torch.ones((), dtype=torch.float32)
+    step, off = float(one * G8_RANGE / (one * 255.0)), float(one * G8_OFF)      # the fp32 constants, G8_STEP by an fp32 division
+    return (aux.to(torch.float64) * step - off).to(torch.float32)
 
 
 def gelu_aux_encode(g):

@@ -16,7 +16,9 @@ wgrad_fast_splits): 128 and 256 give one split at every value of knob 3; a contr
 fp32 output -- gives two, at both values of the knob too.
 
 The last test repeats the fp64 gates of test_kernels_gpu.py::test_gemm256_bf16_tight_gates_against_fp64 (5e-6 sqrt(K) for fp32 outputs,
-2^-8 for bf16 outputs) on random operands, per layout."""
+2^-8 for bf16 outputs) on random operands, per layout.
+
+tests/test_gemm_exact_gpu.py does the same for what this file leaves out: the generic engine, split plans, the other epilogues, the reductions."""
 import math
 
 import pytest
